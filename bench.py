@@ -2,7 +2,7 @@
 """Headline benchmark: sequence-frames/s through the denominator forward-backward
 (BASELINE.json: batch 256 x 150 frames x 4096 pdfs, CHiME5-like den graph H=8192 / A=65536).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one pass of the hot path -- tc_den_forward_backward, i.e. [K] DenominatorComputation
 Forward() + Backward() writing d/dy, with the batch's denominator log-prob and the t=0 status reduced on
@@ -11,7 +11,8 @@ by the driver through torch.distributed.run, or, when this script is started pla
 this script itself as N fresh children (before anything here touches the GPU).  Each rank owns its own
 256-sequence shard (weak scaling, no data-path collective) and every step ends with the path's only
 exchange, one RCCL all-reduce of four float64 (objf, l2_term, weight, xent objective) of the rank's shard.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  With --dump-outputs DIR, rank 0 also writes what the last timed step computed
+to DIR/*.npy (see dump_outputs), so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import ctypes as C
@@ -35,7 +36,51 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the oracle check")
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed full-objective / layout measurements")
     ap.add_argument("--cpu-seqs", type=int, default=256, help="sequences in the CPU-baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE_BYTES = 32 * 10 ** 6  # the derivative's sample; the whole dump stays well under 64 MB
+DUMP_SAMPLE_SEED = 20240531
+
+
+def snapshot_outputs(deriv, lp, st, red):
+    """Device-side copies of what one call of the timed path hands its caller: the derivative d/dy (T*S x P), the
+    batch's denominator log-prob, the status word, and with several ranks the all-reduced (objf, l2_term, weight,
+    xent) of the exchange.  The derivative is larger than the dump may be (C3: 629 MB), so it is kept as a fixed,
+    seeded sample of whole rows next to the float64 sum of every row.  Taken right after the timed region, before
+    anything else launches on the buffers."""
+    import numpy as np
+    import torch
+    rows, cols = deriv.shape
+    n = max(1, min(rows, DUMP_SAMPLE_BYTES // (4 * cols)))
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=n, replace=False))
+    idx_dev = torch.from_numpy(idx).to(deriv.device)
+    snap = {"deriv_sample": deriv.index_select(0, idx_dev),
+            "deriv_sample_rows": torch.from_numpy(idx.astype(np.float64)),
+            "deriv_row_sums": deriv.sum(dim=1, dtype=torch.float64),
+            "den_logprob": lp.clone(),
+            "status": st.clone()}
+    if red is not None:
+        snap["exchange_results"] = red.clone()
+    return snap
+
+
+def dump_outputs(out_dir, snap):
+    """Writes the snapshot as DIR/<name>.npy: float32 for the derivative's rows, float64 for everything else."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, t in snap.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = list(a.shape)
+    return files
 
 
 def launch_ranks(args):
@@ -376,6 +421,7 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
         assert float(red.cpu()[2]) == float(world * S * T)
+    snap = snapshot_outputs(deriv, lp, st, red) if args.dump_outputs and rank == 0 else None
 
     # ---- per-launch duration of the dominant kernel, HIP events on the launch stream
     kern_ms = []
@@ -456,6 +502,8 @@ def main():
             chk["tolerance"] = 1e-4
             chk["pass"] = bool(chk["deriv_rel_err_vs_oracle"] <= 1e-4 and
                                chk.get("logprob_rel_err_vs_oracle", 0.0) <= 1e-4 and status == 0)
+        if snap is not None:
+            out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dump_outputs(args.dump_outputs, snap)}
         if world == 1 and not args.no_extras:
             out["extras"] = extras(graph, fst, cfg, S, T, P, dev)
         print(json.dumps(out))
