@@ -91,6 +91,29 @@ int tc_supervision_create(tc_supervision **out, float weight, int32_t num_sequen
                           const int32_t *arc_begin, const int32_t *arc_ilabel, const float *arc_weight,
                           const int32_t *arc_nextstate, const float *final_weight);
 
+/* End-to-end ("flat-start") supervision: [K] Supervision::e2e_fsts, one epsilon-free acceptor per sequence, not
+ * unfolded in time (self-loops and cycles allowed; every arc consumes one frame).  The per-sequence CSRs are
+ * concatenated: sequence s owns states [seq_state_begin[s], seq_state_begin[s+1]) (seq_state_begin[0] = 0), its
+ * local state i owns arcs [arc_begin[g], arc_begin[g+1]) of g = seq_state_begin[s] + i, arc_begin has
+ * seq_state_begin[S] + 1 entries starting at 0; start[s] and arc_nextstate are local to the sequence;
+ * ilabel = pdf_id + 1; arc_weight / final_weight are tropical costs (+inf final: not final).  The numerator is
+ * [K] GenericNumeratorComputation (num_e2e_kernels.hip); the denominator, the workspace sizes and every entry point
+ * taking a supervision are those of the regular one.  TC_ERR_BAD_FST: label 0 or > label_dim, next state or start out
+ * of range, NaN or -inf cost, a sequence without a final state;  TC_ERR_UNSUPPORTED: a sequence beyond
+ * TC_E2E_MAX_STATES states, TC_E2E_MAX_ARCS arcs or TC_E2E_MAX_PDFS distinct pdfs,
+ * num_sequences * frames_per_sequence above 2^26, or a kernel scratch -- (T + 1) x total states x 8 bytes of alpha
+ * history + T x total distinct pdfs (summed over sequences) x 4 bytes, held with the supervision's device tables --
+ * above 4 GiB. */
+#define TC_E2E_MAX_STATES 2048
+#define TC_E2E_MAX_ARCS 8192
+#define TC_E2E_MAX_PDFS 1024
+int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t num_sequences, int32_t frames_per_sequence,
+                              int32_t label_dim, const int32_t *seq_state_begin, const int32_t *start,
+                              const int32_t *arc_begin, const int32_t *arc_ilabel, const float *arc_weight,
+                              const int32_t *arc_nextstate, const float *final_weight);
+/* 1 for a handle of tc_supervision_create_e2e, else 0. */
+int32_t tc_supervision_is_e2e(const tc_supervision *supervision);
+
 /* Merges the supervision FSTs of a minibatch's examples into the one acceptor tc_supervision_create takes: what the
  * reference reaches natively through kaldi::nnet3::MergeChainExamples -> [K] chain::AppendSupervision
  * (src/my_lib_example_rand.cpp:160).  Host memory only, no GPU needed.  The pieces arrive concatenated: piece k has
@@ -143,6 +166,13 @@ int tc_example_output(const tc_example *example, int32_t j, const char **name, i
                       const int32_t **indexes, const float **deriv_weights, float *weight, int32_t *dims5,
                       const int32_t **arc_begin, const int32_t **ilabel, const float **arc_weight,
                       const int32_t **nextstate, const float **final_weight);
+/* Output j's kind: *is_e2e = 1 for an end-to-end supervision ([K] Supervision::e2e_fsts, `<End2End>` true in the egs).
+ * Then tc_example_output's arrays hold the per-sequence FSTs concatenated (dims5[3] = their total states, dims5[4] =
+ * their total arcs) and seq_state_begin (num_sequences + 1) / start (num_sequences) complete what
+ * tc_supervision_create_e2e takes; both are NULL for a regular output.  A minibatch that mixes e2e and regular
+ * examples does not merge (tc_example_read: TC_ERR_INVALID_ARGUMENT). */
+int tc_example_output_e2e(const tc_example *example, int32_t j, int32_t *is_e2e, const int32_t **seq_state_begin,
+                          const int32_t **start);
 
 /* Random-access minibatch reader: my_lib_example_rand_reader_new / _reset / _num_batch / _num_data / _next / _free,
  * my_lib_example_rand_feats and my_lib_supervision_rand_new of the reference (src/my_lib.h:8-17 over RandReader,
@@ -416,7 +446,8 @@ int tc_debug_set(const char *key, int value);
  * those with a backward recursion / (B, C, T) <-> (T*B, C) copies, process-wide since the library was loaded;
  * (tc_den_graph_prepare's one-off timing launches of a graph's two kernels are counted like any other);
  * "den_long_utterance_launches" = on-chip denominator launches whose frame sums did not fit LDS and went through the
- * workspace (utterances of many hundred frames on the largest on-chip graphs).
+ * workspace (utterances of many hundred frames on the largest on-chip graphs); "num_e2e_staged_launches" = end-to-end
+ * numerator launches that ran beside the denominator and left their posteriors for the scatter kernel.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

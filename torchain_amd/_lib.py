@@ -102,6 +102,12 @@ def _load():
     L.tc_from2d.argtypes = [vp, i64, i32, i32, i32, f32, vp, C.c_int, vp]
     L.tc_supervision_create.restype = C.c_int
     L.tc_supervision_create.argtypes = [C.POINTER(vp), f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.tc_supervision_create_e2e.restype = C.c_int
+    L.tc_supervision_create_e2e.argtypes = [C.POINTER(vp), f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tc_supervision_is_e2e.restype = i32
+    L.tc_supervision_is_e2e.argtypes = [vp]
+    L.tc_example_output_e2e.restype = C.c_int
+    L.tc_example_output_e2e.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.tc_rand_reader_new.restype = C.c_int
     L.tc_rand_reader_new.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, vp]
     L.tc_rand_reader_new_ordered.restype = C.c_int

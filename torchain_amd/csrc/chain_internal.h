@@ -312,6 +312,36 @@ struct NumTables {
   int32_t max_states = 0, max_arcs = 0, max_uniq = 0;
 };
 
+// End-to-end supervision ([K] Supervision::e2e_fsts, supervision_e2e.cpp): per-sequence acceptors with cycles, walked
+// frame by frame by num_e2e_kernels.hip.  Per sequence: states [state_off[s], state_off[s+1]), arcs [arc_off[s], ...),
+// distinct pdfs [pdf_off[s], ...).  An arc's key packs its other state (source for in-arcs, destination for out-arcs) in
+// the low 16 bits and the sequence-local pdf number ("upid") in the high 16 bits; its weight is the log-probability
+// -cost.  Out-arcs are sorted by source (the order of the input); an arc's posterior slot is its out-arc position.
+struct E2eTables {
+  std::vector<int32_t> state_off, arc_off, pdf_off, start;  // S + 1 (start: S)
+  std::vector<int32_t> in_begin, out_begin;                 // per state + 1 per sequence, local arc positions
+  std::vector<uint32_t> in_key, out_key;                    // per arc
+  std::vector<float> in_lw, out_lw;                         // per arc: -cost
+  std::vector<int32_t> pdf_begin, pdf_arc;                  // per upid + 1 per sequence; out-arc positions, increasing
+  std::vector<int32_t> pdf_of;                              // per upid: the pdf (label - 1)
+  std::vector<float> final_lw;                              // per state: -final cost, -inf when not final
+  int32_t max_states = 0, max_arcs = 0, max_pdfs = 0;
+  int64_t total_states = 0, total_pdfs = 0;
+};
+
+// bound on an e2e supervision's kernel scratch ((T + 1) x states x 8 + T x distinct pdfs x 4 bytes): tc_supervision_create_e2e
+constexpr int64_t kE2eMaxScratchBytes = (int64_t)4 << 30;
+struct E2eDev {
+  const int32_t *state_off, *arc_off, *pdf_off, *start, *in_begin, *out_begin, *pdf_begin, *pdf_arc, *pdf_of;
+  const uint32_t *in_key, *out_key;
+  const float *in_lw, *out_lw, *final_lw;
+  // scratch in the same pool slot, not uploaded: the log-alpha history (double) [(T + 1) x state] per sequence (at
+  // (T + 1) * state_off[s]), and per (frame, upid) y from the forward pass, overwritten by the backward pass with
+  // weight * posterior (stage, [T x upid] per sequence at T * pdf_off[s])
+  double *alpha_hist;
+  int32_t max_states, max_arcs, max_pdfs;
+};
+
 // One slot of the per-device supervision pool (supervision.cpp): device blob, pinned staging of the same size,
 // `ready` = the upload has landed, `done` = the last launch that reads the blob has finished.
 struct PoolSlot {
@@ -328,6 +358,8 @@ struct NumDev {
   PoolSlot *slot = nullptr;
   size_t upload_bytes = 0;  // of the slot's pinned staging, to be copied to the device
   bool uploaded = false;    // the copy has been enqueued (tc_supervision_prepare); staged only: tc_supervision_stage
+  int e2e = 0;  // end-to-end supervision: launch_num / launch_num_scatter take num_e2e_kernels.hip with these tables
+  E2eDev e2e_tab = {};
 };
 
 struct NumParams {
@@ -362,7 +394,9 @@ struct NumParams {
 struct tc_supervision {
   float weight = 1.f;
   int32_t S = 0, T = 0, P = 0;
+  bool e2e = false;  // tc_supervision_create_e2e: `e2e_tab` holds the tables, `tab` is empty
   tc::NumTables tab;
+  tc::E2eTables e2e_tab;
   std::vector<size_t> blob_off;    // offsets of the tables inside a pool slot
   std::mutex mu;
   std::map<int, tc::NumDev> dev;
@@ -427,6 +461,9 @@ inline size_t pair_stamp_bytes(int T) { return ((size_t)2 * kWaves * (T + 2) * 8
 int64_t big_small_floats(int hb, int P, int T, int Sp);
 int launch_num(const NumParams &p, hipStream_t stream);
 int launch_num_scatter(const NumParams &p, hipStream_t stream);
+int launch_num_e2e(const NumParams &p, hipStream_t stream);          // num_e2e_kernels.hip (via launch_num)
+int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via launch_num_scatter)
+size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs);
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
 // the denominator leaves CUs idle (api.cpp).
@@ -473,9 +510,11 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
+int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)
+int supervision_from_example(const tc_example *ex, tc_supervision **out);  // egs_reader.cpp: regular or e2e
 #define TC_HIP_CHECK(expr)                        \
   do {                                            \
     hipError_t e__ = (expr);                      \

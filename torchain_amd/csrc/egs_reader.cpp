@@ -99,6 +99,11 @@ struct Sup {
   int32_t S = 0, T = 0, P = 0, nstates = 0;
   std::vector<int32_t> ab, il, nx;
   std::vector<float> w, fin;
+  // end-to-end supervision ([K] Supervision::e2e_fsts): the S per-sequence FSTs concatenated in the arrays above as
+  // tc_supervision_create_e2e takes them -- sequence s owns states [seq_begin[s], seq_begin[s+1]), next states and
+  // start[s] are local to it
+  bool e2e = false;
+  std::vector<int32_t> seq_begin, start;
 };
 
 struct Out {
@@ -204,8 +209,9 @@ void read_general_matrix(In &in, Io *io) {
   throw FormatError{"unsupported matrix type (sparse features are not used by chain egs)"};
 }
 
-// OpenFst CompactFst<StdArc, AcceptorCompactor> as [K] Supervision::Write stores the numerator FST
-void read_compact_acceptor(In &in, Sup *s) {
+// OpenFst CompactFst<StdArc, AcceptorCompactor> as [K] Supervision::Write stores the numerator FST (the merged one of a
+// regular supervision, or one of the per-sequence FSTs of an end-to-end one).  Returns the header's start state.
+int64_t read_compact_acceptor(In &in, Sup *s) {
   int32_t magic;
   in.read(&magic, 4);
   if (magic != 2125659606) throw FormatError{"bad FST magic"};
@@ -227,8 +233,8 @@ void read_compact_acceptor(In &in, Sup *s) {
   in.read(&start, 8);
   in.read(&nstates, 8);
   in.read(&narcs, 8);
-  if (fsttype != "compact_acceptor" || arctype != "standard" || (flags & 4) || (start != 0 && start != -1))
-    throw FormatError{"supervision FST must be an unaligned compact_acceptor over StdArc starting at state 0"};
+  if (fsttype != "compact_acceptor" || arctype != "standard" || (flags & 4))
+    throw FormatError{"supervision FST must be an unaligned compact_acceptor over StdArc"};
   if (flags & 3) throw FormatError{"symbol tables inside a supervision FST are not supported"};
   if (nstates < 0 || nstates > (1 << 28)) throw FormatError{"bad FST state count"};
   std::vector<uint32_t> states;
@@ -264,6 +270,7 @@ void read_compact_acceptor(In &in, Sup *s) {
     }
     s->ab[(size_t)st + 1] = (int32_t)s->il.size();
   }
+  return start;
 }
 
 void read_supervision(In &in, Sup *s) {
@@ -278,11 +285,47 @@ void read_supervision(In &in, Sup *s) {
   s->P = in.basic<int32_t>();
   if (s->S < 1 || s->T < 1 || s->P < 1 || (int64_t)s->S * s->T > ((int64_t)1 << 26) || !(s->weight == s->weight))
     throw FormatError{"bad supervision dimensions"};
-  if (in.peek() == '<') {  // later Kaldi: <End2End> flag (the FST otherwise starts with its magic number, never '<')
+  // Later Kaldi writes <End2End> and a bool behind <LabelDim> (the FST otherwise starts with its magic number, never
+  // '<').  True: [K] Supervision::Write then writes <Fsts>, num_sequences FSTs in the same compact_acceptor form (each
+  // with its own start state, not necessarily 0), </Fsts>, and goes on as for a regular supervision (<AlignmentPdfs>,
+  // </Supervision>).  Restated from the published chain-supervision.cc (Supervision::Write / Read); the tokens and their
+  // order are what that source writes as far as it is remembered here -- no file written by Kaldi was available to
+  // check them against, only this repository's writer (tests/e2e_egs_writer.py), which follows the same statement.
+  s->e2e = false;
+  s->seq_begin.clear();
+  s->start.clear();
+  if (in.peek() == '<') {
     in.expect("<End2End>");
-    if (in.boolean()) throw FormatError{"end-to-end (e2e) supervisions are outside this path"};
+    s->e2e = in.boolean();
   }
-  read_compact_acceptor(in, s);
+  if (s->e2e) {
+    in.expect("<Fsts>");
+    Sup one;
+    s->seq_begin.assign(1, 0);
+    s->ab.assign(1, 0);
+    s->il.clear();
+    s->w.clear();
+    s->nx.clear();
+    s->fin.clear();
+    for (int32_t q = 0; q < s->S; ++q) {
+      const int64_t start = read_compact_acceptor(in, &one);
+      if (start < 0 || start >= one.nstates) throw FormatError{"e2e supervision FST: start state out of range"};
+      if ((int64_t)s->fin.size() + one.nstates > (1 << 28)) throw FormatError{"bad FST state count"};
+      const int32_t base = (int32_t)s->il.size();
+      for (int32_t i = 1; i <= one.nstates; ++i) s->ab.push_back(base + one.ab[(size_t)i]);
+      s->il.insert(s->il.end(), one.il.begin(), one.il.end());
+      s->w.insert(s->w.end(), one.w.begin(), one.w.end());
+      s->nx.insert(s->nx.end(), one.nx.begin(), one.nx.end());
+      s->fin.insert(s->fin.end(), one.fin.begin(), one.fin.end());
+      s->seq_begin.push_back(s->seq_begin.back() + one.nstates);
+      s->start.push_back((int32_t)start);
+    }
+    s->nstates = s->seq_begin.back();
+    in.expect("</Fsts>");
+  } else {
+    const int64_t start = read_compact_acceptor(in, s);
+    if (start != 0 && start != -1) throw FormatError{"supervision FST must start at state 0"};
+  }
   // later Kaldi: alignment pdfs of the supervision, written behind the FST when the vector is not empty
   // ([K] Supervision::Write: WriteToken("<AlignmentPdfs>"), WriteIntegerVector).  The path does not use them: skipped.
   std::string tok = in.token();
@@ -351,6 +394,8 @@ void read_example(In &in, Example *eg) {
   in.expect("</Nnet3ChainEg>");
 }
 
+int merge_output_indexes(const std::vector<Example> &egs, Out *o);
+
 // [K] MergeChainExamples for examples with one output (egs.py: merge_chain_examples)
 int merge(const std::vector<Example> &egs, Example *m) {
   const Example &first = egs[0];
@@ -390,6 +435,30 @@ int merge(const std::vector<Example> &egs, Example *m) {
   // supervisions: AppendSupervision through the library's own entry point
   const Sup &s0 = first.out[0].sup;
   const int K = (int)egs.size();
+  for (const Example &eg : egs)
+    if (eg.out[0].sup.e2e != s0.e2e) return TC_ERR_INVALID_ARGUMENT;  // e2e and regular supervisions do not merge
+  if (s0.e2e) {
+    // [K] MergeSupervisionE2e: equal weight, frames_per_sequence and label_dim; the FST lists are concatenated
+    Out &o = (m->out.resize(1), m->out[0]);
+    o.name = first.out[0].name;
+    Sup &ms = o.sup;
+    ms = s0;
+    for (int k = 1; k < K; ++k) {
+      const Sup &s = egs[(size_t)k].out[0].sup;
+      if (s.weight != s0.weight || s.T != s0.T || s.P != s0.P) return TC_ERR_INVALID_ARGUMENT;
+      const int32_t sbase = ms.nstates, abase = (int32_t)ms.il.size();
+      for (int32_t q = 1; q <= s.S; ++q) ms.seq_begin.push_back(sbase + s.seq_begin[(size_t)q]);
+      ms.start.insert(ms.start.end(), s.start.begin(), s.start.end());
+      for (int32_t i = 1; i <= s.nstates; ++i) ms.ab.push_back(abase + s.ab[(size_t)i]);
+      ms.il.insert(ms.il.end(), s.il.begin(), s.il.end());
+      ms.w.insert(ms.w.end(), s.w.begin(), s.w.end());
+      ms.nx.insert(ms.nx.end(), s.nx.begin(), s.nx.end());
+      ms.fin.insert(ms.fin.end(), s.fin.begin(), s.fin.end());
+      ms.nstates += s.nstates;
+      ms.S += s.S;
+    }
+    return merge_output_indexes(egs, &o);
+  }
   std::vector<int32_t> nst((size_t)K), frames((size_t)K), ab, il, nx;
   std::vector<float> aw, fin;
   int64_t cap_states = 0, cap_arcs = 0, total_S = 0;
@@ -417,6 +486,9 @@ int merge(const std::vector<Example> &egs, Example *m) {
   Out &o = (m->out.resize(1), m->out[0]);
   o.name = first.out[0].name;
   Sup &ms = o.sup;
+  ms.e2e = false;  // (a pooled example may have held an e2e minibatch before)
+  ms.seq_begin.clear();
+  ms.start.clear();
   ms.weight = s0.weight;
   ms.S = (int32_t)total_S;
   ms.T = s0.T;
@@ -442,8 +514,15 @@ int merge(const std::vector<Example> &egs, Example *m) {
     ms.nx.resize((size_t)na);
     ms.fin.resize((size_t)ns);
   }
-  // output indexes and deriv_weights: frame-major over the merged sequences
-  const int T = s0.T;
+  return merge_output_indexes(egs, &o);
+}
+
+// output indexes and deriv_weights of a merged minibatch: frame-major over the merged sequences
+int merge_output_indexes(const std::vector<Example> &egs, Out *op) {
+  Out &o = *op;
+  const int T = egs[0].out[0].sup.T;
+  int64_t total_S = 0;
+  for (const Example &eg : egs) total_S += eg.out[0].sup.S;
   o.idx.resize((size_t)T * total_S * 3);
   o.dw.resize((size_t)T * total_S);
   int64_t base = 0;
@@ -730,4 +809,31 @@ int tc_example_output(const tc_example *ex, int32_t j, const char **name, int32_
   return TC_OK;
 }
 
+int tc_example_output_e2e(const tc_example *ex, int32_t j, int32_t *is_e2e, const int32_t **seq_state_begin,
+                          const int32_t **start) {
+  if (!ex || j < 0 || j >= (int32_t)ex->eg.out.size()) return TC_ERR_INVALID_ARGUMENT;
+  const Sup &s = ex->eg.out[(size_t)j].sup;
+  if (is_e2e) *is_e2e = s.e2e ? 1 : 0;
+  if (seq_state_begin) *seq_state_begin = s.e2e ? s.seq_begin.data() : nullptr;
+  if (start) *start = s.e2e ? s.start.data() : nullptr;
+  return TC_OK;
+}
+
+
 }  // extern "C"
+
+namespace tc {
+// The supervision handle of output 0 of a minibatch, regular or end-to-end (the rand reader's look-ahead and
+// tc_rand_reader_supervision_new).
+int supervision_from_example(const tc_example *ex, tc_supervision **out) {
+  int32_t dims[5] = {0, 0, 0, 0, 0}, e2e = 0;
+  const int32_t *ab = nullptr, *il = nullptr, *nx = nullptr, *sb = nullptr, *st = nullptr;
+  const float *aw = nullptr, *fin = nullptr;
+  float weight = 0.f;
+  int rc = tc_example_output(ex, 0, nullptr, nullptr, nullptr, nullptr, &weight, dims, &ab, &il, &aw, &nx, &fin);
+  if (rc == TC_OK) rc = tc_example_output_e2e(ex, 0, &e2e, &sb, &st);
+  if (rc != TC_OK) return rc;
+  if (e2e) return tc_supervision_create_e2e(out, weight, dims[0], dims[1], dims[2], sb, st, ab, il, aw, nx, fin);
+  return tc_supervision_create(out, weight, dims[0], dims[1], dims[2], dims[3], ab, il, aw, nx, fin);
+}
+}  // namespace tc

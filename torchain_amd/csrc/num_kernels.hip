@@ -205,6 +205,7 @@ __global__ __launch_bounds__(128) void num_scatter_kernel(const NumParams p) {
 }
 
 int launch_num_scatter(const NumParams &p, hipStream_t stream) {
+  if (p.t.e2e) return launch_num_e2e_scatter(p, stream);  // end-to-end supervision: num_e2e_kernels.hip
   if (!p.deriv && !p.xent && !p.seq_xent) return TC_OK;
   hipLaunchKernelGGL(num_scatter_kernel, dim3(p.S), dim3(128), 0, stream, p);
   TC_HIP_CHECK(hipGetLastError());
@@ -212,6 +213,7 @@ int launch_num_scatter(const NumParams &p, hipStream_t stream) {
 }
 
 int launch_num(const NumParams &p, hipStream_t stream) {
+  if (p.t.e2e) return launch_num_e2e(p, stream);  // end-to-end supervision: num_e2e_kernels.hip
   count_launch(kCntNum);
   if (p.deriv || p.xent || p.seq_xent) count_launch(kCntNumBackward);
   const size_t lds = (size_t)p.lds_states * 16 + (size_t)p.lds_uniq * 4 + (size_t)p.lds_arcs * 4;

@@ -31,6 +31,10 @@
 
 #include "torchain_hip.h"
 
+namespace tc {
+int supervision_from_example(const tc_example *ex, tc_supervision **out);  // egs_reader.cpp: regular or e2e
+}
+
 namespace {
 
 struct Entry {
@@ -156,14 +160,8 @@ struct tc_rand_reader {
       r.error = tc_example_last_error();
       return;
     }
-    const char *name = nullptr;
-    int32_t nidx = 0, dims[5] = {0, 0, 0, 0, 0};
-    const int32_t *idx = nullptr, *ab = nullptr, *il = nullptr, *nx = nullptr;
-    const float *dw = nullptr, *aw = nullptr, *fin = nullptr;
-    float weight = 0.f;
-    r.rc = tc_example_output(r.example, 0, &name, &nidx, &idx, &dw, &weight, dims, &ab, &il, &aw, &nx, &fin);
-    if (r.rc == TC_OK) r.rc = tc_supervision_create(&r.sup, weight, dims[0], dims[1], dims[2], dims[3], ab, il, aw, nx, fin);
-    if (r.rc != TC_OK) r.error = "the minibatch's supervision does not build (tc_supervision_create)";
+    r.rc = tc::supervision_from_example(r.example, &r.sup);  // (regular or end-to-end)
+    if (r.rc != TC_OK) r.error = "the minibatch's supervision does not build (tc_supervision_create / _create_e2e)";
     if (r.rc == TC_OK && dev >= 0) (void)tc_supervision_stage(r.sup, dev);  // (a failure shows at the first use)
   }
 
@@ -384,13 +382,7 @@ int tc_rand_reader_supervision_new(tc_rand_reader *r, tc_supervision **out) {
   }
   lock.unlock();
   if (!r->cur.example) return TC_ERR_INVALID_ARGUMENT;  // (both already taken)
-  int32_t dims[5] = {0, 0, 0, 0, 0};
-  const int32_t *ab = nullptr, *il = nullptr, *nx = nullptr;
-  const float *aw = nullptr, *fin = nullptr;
-  float weight = 0.f;
-  int rc = tc_example_output(r->cur.example, 0, nullptr, nullptr, nullptr, nullptr, &weight, dims, &ab, &il, &aw, &nx, &fin);
-  if (rc == TC_OK) rc = tc_supervision_create(out, weight, dims[0], dims[1], dims[2], dims[3], ab, il, aw, nx, fin);
-  return rc;
+  return tc::supervision_from_example(r->cur.example, out);
 }
 
 int tc_rand_reader_batch_keys(const tc_rand_reader *r, int32_t batch, char *buf, int32_t cap) {

@@ -331,6 +331,7 @@ float tc_supervision_weight(const tc_supervision *s) { return s ? s->weight : 0.
 // training thread's first use of the supervision only enqueues the copy.  Caller holds sup->mu.
 static int stage_locked(tc_supervision *sup, int device) {
   if (sup->dev.count(device)) return TC_OK;
+  if (sup->e2e) return stage_e2e_locked(sup, device);  // supervision_e2e.cpp
   NumTables &tb = sup->tab;
   struct Part { const void *src; size_t bytes; };
   const Part parts[] = {

@@ -1,0 +1,223 @@
+// Host side of the end-to-end supervision ([K] Supervision::e2e_fsts, chain-supervision.h): one acceptor per sequence,
+// not unfolded in time, whose numerator is [K] GenericNumeratorComputation (chain-generic-numerator.cc).  Kaldi walks
+// these FSTs on the CPU after copying the numerator's rows of nnet_output to the host; here the host only validates them
+// and lays out the tables the kernel (num_e2e_kernels.hip) walks: in-arcs by destination (forward), out-arcs by source
+// (backward), the distinct pdfs of each sequence and, per pdf, its out-arcs in a fixed order (a deterministic posterior
+// sum).  The tables and the kernel's scratch share one slot of the per-device supervision pool (supervision.cpp).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+
+#include "chain_internal.h"
+
+using namespace tc;
+
+namespace tc {
+
+// The host half of an upload (tc_supervision_stage) for an end-to-end supervision.  Caller holds sup->mu and has checked
+// that the device has no slot yet.
+int stage_e2e_locked(tc_supervision *sup, int device) {
+  const E2eTables &tb = sup->e2e_tab;
+  const int T = sup->T;
+  struct Part { const void *src; size_t bytes; };
+  const Part parts[] = {
+      {tb.state_off.data(), tb.state_off.size() * 4}, {tb.arc_off.data(), tb.arc_off.size() * 4},
+      {tb.pdf_off.data(), tb.pdf_off.size() * 4},     {tb.start.data(), tb.start.size() * 4},
+      {tb.in_begin.data(), tb.in_begin.size() * 4},   {tb.out_begin.data(), tb.out_begin.size() * 4},
+      {tb.pdf_begin.data(), tb.pdf_begin.size() * 4}, {tb.pdf_arc.data(), tb.pdf_arc.size() * 4},
+      {tb.pdf_of.data(), tb.pdf_of.size() * 4},       {tb.in_key.data(), tb.in_key.size() * 4},
+      {tb.out_key.data(), tb.out_key.size() * 4},     {tb.in_lw.data(), tb.in_lw.size() * 4},
+      {tb.out_lw.data(), tb.out_lw.size() * 4},       {tb.final_lw.data(), tb.final_lw.size() * 4},
+  };
+  const int nparts = (int)(sizeof(parts) / sizeof(parts[0]));
+  size_t total = 0;
+  sup->blob_off.clear();
+  for (int i = 0; i < nparts; ++i) {
+    sup->blob_off.push_back(total);
+    total += (parts[i].bytes + 255) & ~(size_t)255;
+  }
+  total += 256;
+  const size_t upload = total;
+  // the kernel's scratch, sized with the slot (so tc_chain_workspace_bytes does not depend on the supervision's kind)
+  const size_t alpha_off = total;
+  total += ((size_t)(T + 1) * tb.total_states * 8 + 255) & ~(size_t)255;
+  const size_t stage_off = total;
+  total += ((size_t)T * tb.total_pdfs * 4 + 255) & ~(size_t)255;
+  PoolSlot *slot = nullptr;
+  int rc = pool_acquire(device, total, &slot);
+  if (rc != TC_OK) return rc;
+  for (int i = 0; i < nparts; ++i)
+    if (parts[i].bytes) memcpy(slot->host + sup->blob_off[i], parts[i].src, parts[i].bytes);
+  NumDev d;
+  d.slot = slot;
+  d.upload_bytes = upload;
+  d.uploaded = false;
+  d.e2e = 1;
+  char *blob = slot->blob;
+  auto P = [&](int i) { return (const int32_t *)(blob + sup->blob_off[i]); };
+  E2eDev &e = d.e2e_tab;
+  e.state_off = P(0); e.arc_off = P(1); e.pdf_off = P(2); e.start = P(3); e.in_begin = P(4); e.out_begin = P(5);
+  e.pdf_begin = P(6); e.pdf_arc = P(7); e.pdf_of = P(8);
+  e.in_key = (const uint32_t *)P(9);
+  e.out_key = (const uint32_t *)P(10);
+  e.in_lw = (const float *)P(11);
+  e.out_lw = (const float *)P(12);
+  e.final_lw = (const float *)P(13);
+  e.alpha_hist = (double *)(blob + alpha_off);
+  e.max_states = tb.max_states;
+  e.max_arcs = tb.max_arcs;
+  e.max_pdfs = tb.max_pdfs;
+  d.stage = (float *)(blob + stage_off);
+  sup->dev[device] = d;
+  return TC_OK;
+}
+
+}  // namespace tc
+
+extern "C" {
+
+int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t S, int32_t T, int32_t label_dim,
+                              const int32_t *seq_state_begin, const int32_t *start, const int32_t *arc_begin,
+                              const int32_t *ilabel, const float *arc_weight, const int32_t *nextstate,
+                              const float *final_weight) {
+  if (!out) return TC_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (S <= 0 || T <= 0 || label_dim <= 0 || !seq_state_begin || !start || !arc_begin || !final_weight)
+    return TC_ERR_INVALID_ARGUMENT;
+  if ((int64_t)S * T > ((int64_t)1 << 26)) return TC_ERR_UNSUPPORTED;  // the egs readers' bound on a minibatch
+  if (seq_state_begin[0] != 0) return TC_ERR_BAD_FST;
+  for (int32_t s = 0; s < S; ++s)
+    if (seq_state_begin[s + 1] < seq_state_begin[s]) return TC_ERR_BAD_FST;
+  const int32_t num_states = seq_state_begin[S];
+  if (arc_begin[0] != 0) return TC_ERR_BAD_FST;
+  for (int32_t g = 0; g < num_states; ++g)
+    if (arc_begin[g + 1] < arc_begin[g]) return TC_ERR_BAD_FST;
+  const int32_t num_arcs = arc_begin[num_states];
+  if (num_arcs > 0 && (!ilabel || !arc_weight || !nextstate)) return TC_ERR_INVALID_ARGUMENT;
+
+  // structure first (TC_ERR_BAD_FST), then the kernel's size limits (TC_ERR_UNSUPPORTED)
+  bool too_large = false;
+  std::vector<int32_t> upid_of(label_dim, -1), touched;
+  for (int32_t s = 0; s < S; ++s) {
+    const int32_t sb = seq_state_begin[s], n = seq_state_begin[s + 1] - sb;
+    if (start[s] < 0 || start[s] >= n) return TC_ERR_BAD_FST;
+    bool any_final = false;
+    for (int32_t i = 0; i < n; ++i) {
+      const float f = final_weight[sb + i];
+      if (std::isnan(f) || f == -std::numeric_limits<float>::infinity()) return TC_ERR_BAD_FST;
+      if (!std::isinf(f)) any_final = true;
+    }
+    if (!any_final) return TC_ERR_BAD_FST;
+    int32_t npdf = 0;
+    for (int32_t a = arc_begin[sb]; a < arc_begin[sb + n]; ++a) {
+      if (ilabel[a] < 1 || ilabel[a] > label_dim) return TC_ERR_BAD_FST;  // 0: epsilon
+      if (nextstate[a] < 0 || nextstate[a] >= n) return TC_ERR_BAD_FST;
+      if (std::isnan(arc_weight[a]) || arc_weight[a] == -std::numeric_limits<float>::infinity()) return TC_ERR_BAD_FST;
+      if (upid_of[ilabel[a] - 1] < 0) {
+        upid_of[ilabel[a] - 1] = npdf++;
+        touched.push_back(ilabel[a] - 1);
+      }
+    }
+    for (int32_t p : touched) upid_of[p] = -1;
+    touched.clear();
+    if (n > TC_E2E_MAX_STATES || arc_begin[sb + n] - arc_begin[sb] > TC_E2E_MAX_ARCS || npdf > TC_E2E_MAX_PDFS)
+      too_large = true;
+  }
+  if (too_large) return TC_ERR_UNSUPPORTED;
+  // the kernel's scratch in the supervision's pool slot (stage_e2e_locked): the log-alpha history, (T + 1) x states
+  // doubles, and y / the posteriors, T x distinct pdfs floats -- bounded here, not at the first step's allocation
+  {
+    int64_t pdfs = 0;
+    for (int32_t s = 0; s < S; ++s) {
+      for (int32_t a = arc_begin[seq_state_begin[s]]; a < arc_begin[seq_state_begin[s + 1]]; ++a)
+        if (upid_of[ilabel[a] - 1] < 0) upid_of[ilabel[a] - 1] = 0, touched.push_back(ilabel[a] - 1), ++pdfs;
+      for (int32_t p : touched) upid_of[p] = -1;
+      touched.clear();
+    }
+    if ((double)(T + 1) * num_states * 8 + (double)T * pdfs * 4 > (double)kE2eMaxScratchBytes) return TC_ERR_UNSUPPORTED;
+  }
+
+  tc_supervision *sup = new tc_supervision();
+  sup->e2e = true;
+  sup->weight = weight;
+  sup->S = S;
+  sup->T = T;
+  sup->P = label_dim;
+  E2eTables &tb = sup->e2e_tab;
+  tb.state_off.assign(seq_state_begin, seq_state_begin + S + 1);
+  tb.start.assign(start, start + S);
+  tb.arc_off.push_back(0);
+  tb.pdf_off.push_back(0);
+  tb.in_key.reserve(num_arcs);
+  tb.in_lw.reserve(num_arcs);
+  tb.out_key.reserve(num_arcs);
+  tb.out_lw.reserve(num_arcs);
+  tb.pdf_arc.reserve(num_arcs);
+  tb.final_lw.reserve(num_states);
+  std::vector<int32_t> cnt, fill, arc_upid;
+  for (int32_t s = 0; s < S; ++s) {
+    const int32_t sb = seq_state_begin[s], n = seq_state_begin[s + 1] - sb;
+    const int32_t a0 = arc_begin[sb], na = arc_begin[sb + n] - a0;
+    for (int32_t i = 0; i < n; ++i) {
+      const float f = final_weight[sb + i];
+      tb.final_lw.push_back(-f);  // (+inf: not final -> -inf)
+    }
+    // distinct pdfs in first-occurrence order over the out-arcs
+    const int32_t ubase = (int32_t)tb.pdf_of.size();
+    arc_upid.resize(na);
+    for (int32_t k = 0; k < na; ++k) {
+      const int32_t pdf = ilabel[a0 + k] - 1;
+      if (upid_of[pdf] < 0) {
+        upid_of[pdf] = (int32_t)tb.pdf_of.size() - ubase;
+        tb.pdf_of.push_back(pdf);
+      }
+      arc_upid[k] = upid_of[pdf];
+    }
+    const int32_t npdf = (int32_t)tb.pdf_of.size() - ubase;
+    for (int32_t u = 0; u < npdf; ++u) upid_of[tb.pdf_of[ubase + u]] = -1;
+    // out-arcs: the input's order (by source)
+    for (int32_t i = 0; i <= n; ++i) tb.out_begin.push_back(arc_begin[sb + i] - a0);
+    for (int32_t k = 0; k < na; ++k) {
+      tb.out_key.push_back((uint32_t)nextstate[a0 + k] | ((uint32_t)arc_upid[k] << 16));
+      tb.out_lw.push_back(-arc_weight[a0 + k]);
+    }
+    // in-arcs by destination, stable by arc position
+    cnt.assign(n + 1, 0);
+    for (int32_t k = 0; k < na; ++k) cnt[nextstate[a0 + k] + 1]++;
+    for (int32_t i = 0; i < n; ++i) cnt[i + 1] += cnt[i];
+    for (int32_t i = 0; i <= n; ++i) tb.in_begin.push_back(cnt[i]);
+    fill.assign(cnt.begin(), cnt.end() - 1);
+    std::vector<int32_t> order(na);
+    for (int32_t k = 0; k < na; ++k) order[fill[nextstate[a0 + k]]++] = k;
+    std::vector<int32_t> src_of(na);
+    for (int32_t i = 0; i < n; ++i)
+      for (int32_t k = arc_begin[sb + i] - a0; k < arc_begin[sb + i + 1] - a0; ++k) src_of[k] = i;
+    for (int32_t j = 0; j < na; ++j) {
+      const int32_t k = order[j];
+      tb.in_key.push_back((uint32_t)src_of[k] | ((uint32_t)arc_upid[k] << 16));
+      tb.in_lw.push_back(tb.out_lw[tb.out_lw.size() - na + k]);
+    }
+    // per pdf: its out-arc positions, increasing
+    cnt.assign(npdf + 1, 0);
+    for (int32_t k = 0; k < na; ++k) cnt[arc_upid[k] + 1]++;
+    for (int32_t u = 0; u < npdf; ++u) cnt[u + 1] += cnt[u];
+    for (int32_t u = 0; u <= npdf; ++u) tb.pdf_begin.push_back(cnt[u]);
+    const size_t pb = tb.pdf_arc.size();
+    tb.pdf_arc.resize(pb + na);
+    for (int32_t k = 0; k < na; ++k) tb.pdf_arc[pb + cnt[arc_upid[k]]++] = k;
+    tb.arc_off.push_back(tb.arc_off.back() + na);
+    tb.pdf_off.push_back(tb.pdf_off.back() + npdf);
+    tb.max_states = std::max(tb.max_states, n);
+    tb.max_arcs = std::max(tb.max_arcs, na);
+    tb.max_pdfs = std::max(tb.max_pdfs, npdf);
+  }
+  tb.total_states = num_states;
+  tb.total_pdfs = tb.pdf_off.back();
+  *out = sup;
+  return TC_OK;
+}
+
+int32_t tc_supervision_is_e2e(const tc_supervision *s) { return s && s->e2e ? 1 : 0; }
+
+}  // extern "C"

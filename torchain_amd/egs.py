@@ -37,6 +37,17 @@ class EgsFormatError(ValueError):
     pass
 
 
+class E2eSup:
+    """An end-to-end supervision ([K] ``Supervision::e2e_fsts``, ``<End2End>`` true): ``fsts`` holds one
+    ``(start, arc_begin, ilabel, arc_weight, nextstate, final)`` per sequence, what ``io.Supervision.from_e2e_fsts``
+    takes."""
+
+    def __init__(self, weight, num_sequences, frames_per_sequence, label_dim, fsts):
+        self.weight, self.num_sequences = float(weight), int(num_sequences)
+        self.frames_per_sequence, self.label_dim = int(frames_per_sequence), int(label_dim)
+        self.fsts = list(fsts)
+
+
 # ---- Kaldi binary primitives (base/io-funcs-inl.h) -------------------------------------------------------
 class _Reader:
     def __init__(self, stream):
@@ -182,9 +193,9 @@ def _read_compact_acceptor(r):
     fsttype, arctype = fst_string(), fst_string()
     version, flags = struct.unpack("<ii", r.read(8))
     _props, _start, nstates, _narcs = struct.unpack("<Qqqq", r.read(32))
-    if fsttype != "compact_acceptor" or arctype != "standard" or (flags & 4) or _start not in (0, -1):
-        raise EgsFormatError("supervision FST must be an unaligned compact_acceptor over StdArc starting at state 0 "
-                             "(got %s/%s, start %d)" % (fsttype, arctype, _start))
+    if fsttype != "compact_acceptor" or arctype != "standard" or (flags & 4):
+        raise EgsFormatError("supervision FST must be an unaligned compact_acceptor over StdArc (got %s/%s)"
+                             % (fsttype, arctype))
     if flags & 1 or flags & 2:
         raise EgsFormatError("symbol tables inside a supervision FST are not supported")
     states = r.array(np.uint32, nstates + 1).astype(np.int64)
@@ -199,7 +210,7 @@ def _read_compact_acceptor(r):
     np.add.at(arc_begin, owner[arcs] + 1, 1)
     arc_begin = np.cumsum(arc_begin).astype(np.int32)
     return (arc_begin, comp["label"][arcs].astype(np.int32), comp["weight"][arcs].astype(np.float32),
-            comp["next"][arcs].astype(np.int32), final)
+            comp["next"][arcs].astype(np.int32), final), int(_start)
 
 
 def _read_supervision(r):
@@ -215,11 +226,25 @@ def _read_supervision(r):
     P = r.int32()
     # later Kaldi: <End2End> flag.  One byte decides: the FST that follows otherwise starts with its magic number
     # 2125659606 = d6 fd b2 7e, never '<' (and a buffered reader's peek may hold a single byte at a block boundary).
+    # True: <Fsts>, num_sequences compact acceptors (each with its own start state), </Fsts> ([K] Supervision::Write,
+    # restated from the published source; no Kaldi-written file was available to check it against).
+    e2e = False
     if r.peek(1) == b"<":
         r.expect("<End2End>")
-        if r.boolean():
-            raise EgsFormatError("end-to-end (e2e) supervisions are outside this path (SURVEY.md section 8a caveat 3)")
-    arc_begin, ilabel, w, nxt, final = _read_compact_acceptor(r)
+        e2e = r.boolean()
+    if e2e:
+        r.expect("<Fsts>")
+        fsts = []
+        for _ in range(S):
+            (ab_, il_, w_, nx_, fin_), start = _read_compact_acceptor(r)
+            if not 0 <= start < len(fin_):
+                raise EgsFormatError("e2e supervision FST: start state %d out of range" % start)
+            fsts.append((start, ab_, il_, w_, nx_, fin_))
+        r.expect("</Fsts>")
+    else:
+        (arc_begin, ilabel, w, nxt, final), start = _read_compact_acceptor(r)
+        if start not in (0, -1):
+            raise EgsFormatError("supervision FST must start at state 0 (got %d)" % start)
     tok = r.token()
     if tok == "<AlignmentPdfs>":  # later Kaldi, behind the FST when not empty ([K] WriteIntegerVector); unused here
         if r.read(1)[0] != 4:
@@ -231,6 +256,8 @@ def _read_supervision(r):
         tok = r.token()
     if tok != "</Supervision>":
         raise EgsFormatError("expected </Supervision>, got %s" % tok)
+    if e2e:
+        return E2eSup(float(weight), S, T, P, fsts)
     return SupFst(float(weight), S, T, P, len(final), arc_begin, ilabel, w, nxt, final)
 
 
@@ -588,6 +615,23 @@ def _wrap_native(handle):
             lib.tc_example_output(handle, j, ref(name), ref(nidx), ref(idx), ref(dw), ref(weight), C.cast(dims, C.c_void_p),
                                   ref(ab), ref(il), ref(aw), ref(nx), ref(fin))
             S, T, P, ns, na = (int(v) for v in dims)
+            is_e2e, seq_begin, starts = C.c_int32(), C.c_void_p(), C.c_void_p()
+            lib.tc_example_output_e2e(handle, j, ref(is_e2e), ref(seq_begin), ref(starts))
+            if is_e2e.value:
+                ab_all = arr(ab, C.c_int32, ns + 1, np.int32)
+                il_all, aw_all = arr(il, C.c_int32, na, np.int32), arr(aw, C.c_float, na, np.float32)
+                nx_all, fin_all = arr(nx, C.c_int32, na, np.int32), arr(fin, C.c_float, ns, np.float32)
+                sb, st = arr(seq_begin, C.c_int32, S + 1, np.int32), arr(starts, C.c_int32, S, np.int32)
+                fsts = []
+                for q in range(S):
+                    a0, a1 = ab_all[sb[q]], ab_all[sb[q + 1]]
+                    fsts.append((int(st[q]), (ab_all[sb[q]:sb[q + 1] + 1] - a0).astype(np.int32), il_all[a0:a1],
+                                 aw_all[a0:a1], nx_all[a0:a1], fin_all[sb[q]:sb[q + 1]]))
+                sup = E2eSup(float(weight.value), S, T, P, fsts)
+                outputs.append(dict(name=name.value.decode(),
+                                    indexes=arr(idx, C.c_int32, 3 * nidx.value, np.int32).reshape(-1, 3),
+                                    supervision=sup, deriv_weights=arr(dw, C.c_float, nidx.value, np.float32)))
+                continue
             sup = SupFst(float(weight.value), S, T, P, ns, arr(ab, C.c_int32, ns + 1, np.int32),
                          arr(il, C.c_int32, na, np.int32), arr(aw, C.c_float, na, np.float32),
                          arr(nx, C.c_int32, na, np.int32), arr(fin, C.c_float, ns, np.float32))
@@ -645,7 +689,20 @@ def merge_chain_examples(examples):
             idx.append(ix)
         inputs.append(dict(name=name, indexes=np.concatenate(idx), features=np.concatenate(feats)))
     outs = [eg["outputs"][0] for eg in examples]
-    sup = append_supervisions([o["supervision"] for o in outs])
+    sups = [o["supervision"] for o in outs]
+    kinds = {isinstance(s, E2eSup) for s in sups}
+    if len(kinds) > 1:
+        raise EgsFormatError("end-to-end and regular supervisions do not merge")
+    if True in kinds:
+        # [K] MergeSupervisionE2e: equal weight, frames_per_sequence and label_dim; the FST lists are concatenated
+        s0 = sups[0]
+        for s in sups:
+            if (s.weight, s.frames_per_sequence, s.label_dim) != (s0.weight, s0.frames_per_sequence, s0.label_dim):
+                raise EgsFormatError("e2e supervisions differ in weight, frames or label-dim")
+        sup = E2eSup(s0.weight, sum(s.num_sequences for s in sups), s0.frames_per_sequence, s0.label_dim,
+                     [f for s in sups for f in s.fsts])
+    else:
+        sup = append_supervisions(sups)
     T = sup.frames_per_sequence
     idx_seq, dw_seq = [], []
     n = 0

@@ -160,8 +160,51 @@ class Supervision:
         return cls(handle)
 
     @classmethod
+    def from_e2e_fsts(cls, weight, frames_per_sequence, label_dim, fsts):
+        """End-to-end supervision ([K] ``Supervision::e2e_fsts``): one acceptor per sequence, not unfolded in time.
+        ``fsts`` is a list of per-sequence ``(start, arc_begin, ilabel, arc_weight, nextstate, final)`` in CSR form
+        (``ilabel`` = pdf_id + 1, tropical costs, ``final`` = inf for a state that is not final)."""
+        fsts = list(fsts)
+        if not fsts:
+            raise ValueError("from_e2e_fsts: no FSTs")
+        seq_begin, starts, ab, il, aw, nx, fin = [0], [], [np.zeros(1, np.int32)], [], [], [], []
+        arcs = 0
+        for start, arc_begin, ilabel, arc_weight, nextstate, final in fsts:
+            arc_begin = np.asarray(arc_begin, dtype=np.int64)
+            final = np.asarray(final, dtype=np.float32).ravel()
+            if arc_begin.shape != (len(final) + 1,) or arc_begin[0] != 0:
+                raise ValueError("from_e2e_fsts: arc_begin must have len(final) + 1 entries starting at 0")
+            if any(np.asarray(x).size != arc_begin[-1] for x in (ilabel, arc_weight, nextstate)):
+                raise ValueError("from_e2e_fsts: sequence %d: ilabel, arc_weight and nextstate must have arc_begin[-1] "
+                                 "entries" % len(starts))
+            seq_begin.append(seq_begin[-1] + len(final))
+            starts.append(int(start))
+            ab.append((arc_begin[1:] + arcs).astype(np.int32))
+            arcs += int(arc_begin[-1])
+            il.append(np.asarray(ilabel, dtype=np.int32).ravel())
+            aw.append(np.asarray(arc_weight, dtype=np.float32).ravel())
+            nx.append(np.asarray(nextstate, dtype=np.int32).ravel())
+            fin.append(final)
+        sb, st = _i32(seq_begin), _i32(starts)
+        ab, il, nx = _i32(np.concatenate(ab)), _i32(np.concatenate(il)), _i32(np.concatenate(nx))
+        aw, fin = _f32(np.concatenate(aw)), _f32(np.concatenate(fin))
+        handle = C.c_void_p()
+        check(lib.tc_supervision_create_e2e(C.byref(handle), float(weight), len(fsts), int(frames_per_sequence),
+                                            int(label_dim), _p(sb), _p(st), _p(ab), _p(il), _p(aw), _p(nx), _p(fin)),
+              "tc_supervision_create_e2e")
+        return cls(handle)
+
+    @property
+    def is_e2e(self):
+        """True for an end-to-end supervision (``from_e2e_fsts``)."""
+        return bool(lib.tc_supervision_is_e2e(self.ptr))
+
+    @classmethod
     def from_synth(cls, sup):
-        """From a ``torchain_amd.synth.SupFst``."""
+        """From a ``torchain_amd.synth.SupFst``, or an ``egs.E2eSup`` (what the egs readers return for ``<End2End>``
+        egs)."""
+        if isinstance(sup, _egs.E2eSup):
+            return cls.from_e2e_fsts(sup.weight, sup.frames_per_sequence, sup.label_dim, sup.fsts)
         return cls.from_fst(sup.weight, sup.num_sequences, sup.frames_per_sequence, sup.label_dim, sup.arc_begin,
                             sup.ilabel, sup.arc_weight, sup.nextstate, sup.final)
 
