@@ -320,6 +320,39 @@ int tc_chain_step(tc_den_graph *graph, tc_supervision *supervision, const float 
                   float *loss_dev1, double *xent_objf_dev, void *workspace, int64_t workspace_bytes, int device,
                   void *stream);
 
+/* Element types of the tensors of tc_chain_step_typed. */
+#define TC_DTYPE_F32 0
+#define TC_DTYPE_BF16 1
+#define TC_DTYPE_F16 2
+
+/* tc_chain_step on tensors of element type `dtype` (TC_DTYPE_*; anything else: TC_ERR_INVALID_ARGUMENT): input,
+ * xent_input, grad and xent_grad are all of that type, in the layouts tc_chain_step takes (2-D grad and xent_grad
+ * contiguous).  TC_DTYPE_F32 is tc_chain_step itself, with its workspace.  For bfloat16 / float16 the values are those
+ * of tc_chain_step on the same tensors converted to float32 (an exact conversion), with each gradient element rounded
+ * once, to nearest even, from that call's float32 value; results_dev3, loss_dev1 and xent_objf_dev stay float32 / float64.
+ * Everything between the edges is the float32 computation:
+ *   three_d != 0 : the frame-major float32 copy of input (or of xent_input, kaldi_way == 0) that the denominator reads is
+ *                  widened from the 16-bit (B, C, T) tensor by the layout copy; the numerator reads the 16-bit tensors
+ *                  in place (input or xent_input at its (frame, pdf) pairs, xent_input for the cross-entropy objective)
+ *                  and widens in registers.  grad is rounded by the layout copy back, after the scale -1.  xent_grad
+ *                  is written into a cleared float32 (B, C, T) scratch and rounded into the caller's tensor in one pass.
+ *   three_d == 0 : input (and with the xent branch xent_input), with `row_stride`, are widened into contiguous float32
+ *                  matrices in the workspace, and the float32 2-D step runs on them; grad and xent_grad are written
+ *                  there in float32 and rounded into the caller's contiguous matrices in one pass each.
+ *   soft failure : the float32 scratch is reset as tc_chain_step resets its gradients, and then rounded: a zero gradient
+ *                  (-l2 * weight * y with l2 != 0) in the caller's 16-bit tensor.
+ * Workspace: tc_chain_step_typed_workspace_bytes(graph, B, T, three_d, xent branch, dtype).  For TC_DTYPE_F32 it equals
+ * tc_chain_step_workspace_bytes; for bfloat16 / float16 it adds M = B * T * num_pdfs * 4 bytes (float32 scratch,
+ * rounded up to 256 bytes) k times: three_d and the xent branch: k = 1 (the xent gradient); three_d without it: k = 0;
+ * 2-D: k = 2 (input and gradient), k = 4 with the xent branch (and xent_input and its gradient). */
+int64_t tc_chain_step_typed_workspace_bytes(const tc_den_graph *graph, int32_t num_sequences,
+                                            int32_t frames_per_sequence, int three_d, int with_xent, int dtype);
+int tc_chain_step_typed(tc_den_graph *graph, tc_supervision *supervision, const void *input, const void *xent_input,
+                        int three_d, int64_t row_stride, float l2_regularize, float leaky_hmm_coefficient,
+                        float xent_regularize, int kaldi_way, void *grad, void *xent_grad, float *results_dev3,
+                        float *loss_dev1, double *xent_objf_dev, int dtype, void *workspace, int64_t workspace_bytes,
+                        int device, void *stream);
+
 /* The benchmarked unit: [K] DenominatorComputation::Forward() + Backward(deriv_weight, deriv)
  * (direct use in the reference: src/chain-supervision-test.hpp:403-414).
  *   logprob_dev   : device double[1], sum over sequences of the denominator log-prob

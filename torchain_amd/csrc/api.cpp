@@ -453,7 +453,7 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
                       void *workspace, int64_t workspace_bytes, int device, void *stream_v,
                       const float *xent_out = nullptr, int64_t xent_out_stride = 0, double *xent_objf_dev = nullptr,
                       int xent_bct = 0, int xent_out_bct = 0, const float *bct_input = nullptr,
-                      bool xent_sums_ready = false, float *loss_dev1 = nullptr) {
+                      bool xent_sums_ready = false, float *loss_dev1 = nullptr, int bct_dtype = TC_DTYPE_F32) {
   if (!g || !sup || !y || !results_dev3) return TC_ERR_INVALID_ARGUMENT;
   if (sup->P != g->P) return TC_ERR_INVALID_ARGUMENT;
   if ((int64_t)sup->S * sup->T != rows) return TC_ERR_INVALID_ARGUMENT;
@@ -485,9 +485,10 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   if (bct_input) {
     np.y = bct_input;
     np.y_bct = 1;
+    np.elem = bct_dtype;  // (bct_input and a (B, C, T) xent_out: the caller's tensors, float32 or 16-bit)
   }
   auto fill_y = [&]() -> int {  // the frame-major copy the denominator reads
-    return bct_input ? launch_layout(true, bct_input, const_cast<float *>(y), sup->S, cols, sup->T, y_stride, 1.0f, stream) : TC_OK;
+    return bct_input ? launch_to2d(bct_dtype, bct_input, const_cast<float *>(y), sup->S, cols, sup->T, y_stride, stream) : TC_OK;
   };
 
   SideStreams *ss = nullptr;
@@ -574,14 +575,16 @@ int tc_chain_objf_and_grad(tc_den_graph *g, tc_supervision *sup, const float *y,
 
 // ---- one call per training step --------------------------------------------------------------------------------
 // Workspace of tc_chain_step: [tc_chain_workspace_bytes | scratch of the xent objective | for (B, C, T) tensors the
-// frame-major copies of input and gradient (and of xent_input and its gradient)].
+// frame-major copies of input and gradient (and of xent_input and its gradient)].  16-bit tensors (tc_chain_step_typed):
+// the float32 copies of input and gradient (and xent_input) in 2-D as well, then the float32 xent gradient.
 namespace {
 struct StepWorkspace {
   char *chain, *trace;
-  float *y2d, *g2d, *x2d;
+  float *y2d, *g2d, *x2d, *xg;
   size_t chain_bytes, total;
 };
-StepWorkspace carve_step(char *base, const tc_den_graph *g, int S, int T, int P, bool three_d, bool xent) {
+StepWorkspace carve_step(char *base, const tc_den_graph *g, int S, int T, int P, bool three_d, bool xent,
+                         int dtype = TC_DTYPE_F32) {
   StepWorkspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -593,24 +596,46 @@ StepWorkspace carve_step(char *base, const tc_den_graph *g, int S, int T, int P,
   w.chain = take(w.chain_bytes);
   w.trace = take((size_t)trace_workspace_bytes());
   const size_t mat = (size_t)S * T * P * sizeof(float);
-  w.y2d = three_d ? (float *)take(mat) : nullptr;
-  w.g2d = three_d ? (float *)take(mat) : nullptr;
-  w.x2d = three_d && xent ? (float *)take(mat) : nullptr;
+  const bool half = dtype != TC_DTYPE_F32, copies = three_d || half;
+  w.y2d = copies ? (float *)take(mat) : nullptr;
+  w.g2d = copies ? (float *)take(mat) : nullptr;
+  w.x2d = copies && xent ? (float *)take(mat) : nullptr;
+  w.xg = half && xent ? (float *)take(mat) : nullptr;
   w.total = off;
   return w;
 }
 }  // namespace
 
+static bool known_dtype(int dtype) { return dtype == TC_DTYPE_F32 || dtype == TC_DTYPE_BF16 || dtype == TC_DTYPE_F16; }
+
 int64_t tc_chain_step_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T, int three_d, int with_xent) {
-  if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
-  return (int64_t)carve_step(nullptr, g, S, T, g->P, three_d != 0, with_xent != 0).total;
+  return tc_chain_step_typed_workspace_bytes(g, S, T, three_d, with_xent, TC_DTYPE_F32);
+}
+
+int64_t tc_chain_step_typed_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T, int three_d, int with_xent,
+                                            int dtype) {
+  if (!g || S <= 0 || T <= 0 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  return (int64_t)carve_step(nullptr, g, S, T, g->P, three_d != 0, with_xent != 0, dtype).total;
 }
 
 int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, const float *xent_input, int three_d,
                   int64_t row_stride, float l2_regularize, float leaky, float xent_regularize, int kaldi_way,
                   float *grad, float *xent_grad, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
                   void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
-  if (!g || !sup || !input || !results_dev3) return TC_ERR_INVALID_ARGUMENT;
+  return tc_chain_step_typed(g, sup, input, xent_input, three_d, row_stride, l2_regularize, leaky, xent_regularize,
+                             kaldi_way, grad, xent_grad, results_dev3, loss_dev1, xent_objf_dev, TC_DTYPE_F32, workspace,
+                             workspace_bytes, device, stream_v);
+}
+
+int tc_chain_step_typed(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int three_d,
+                        int64_t row_stride, float l2_regularize, float leaky, float xent_regularize, int kaldi_way,
+                        void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
+                        int dtype, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  // (16-bit tensors travel as float pointers up to the kernels that read or write them: NumParams::elem, launch_to2d)
+  const float *input = static_cast<const float *>(input_v), *xent_input = static_cast<const float *>(xent_input_v);
+  float *grad = static_cast<float *>(grad_v), *xent_grad = static_cast<float *>(xent_grad_v);
+  const bool half = dtype != TC_DTYPE_F32;
   const bool use_xent = xent_input != nullptr && xent_regularize != 0.0f;
   // grad == NULL: an evaluation step ([K] ComputeChainObjfAndDeriv with nnet_output_deriv == NULL, as Kaldi's own
   // diagnostics call it): the two forward recursions, the results and the loss; no Backward(), so no alpha-beta
@@ -623,13 +648,18 @@ int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, cons
   if (P != g->P) return TC_ERR_INVALID_ARGUMENT;
   const int64_t rows = (int64_t)S * T;
   if (!three_d && row_stride < P) return TC_ERR_INVALID_ARGUMENT;
-  const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent);
+  if (half && three_d && (S > 65535 || (T + 239) / 240 > 65535)) return TC_ERR_UNSUPPORTED;  // (tc_from2d's limits)
+  const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype);
   if (!workspace || (int64_t)w.total > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_v;
   // frame-major views of the tensors: the caller's own for 2-D input, copies for (B, C, T) (torchain/functions.py:118-125)
-  const float *y = input, *xe = xent_input;
+  const float *y = input;
   float *gr = grad, *xg = use_xent ? xent_grad : nullptr;
   int64_t stride = row_stride, gstride = P;  // (2-D gradients are written as contiguous matrices)
+  // what the numerator reads for the cross-entropy objective (xent_in, xent_stride) and for the objective-only pass of
+  // kaldi_way == 0 (num_in, num_stride): the caller's tensors, or for 16-bit 2-D tensors their float32 copies
+  const float *num_in = input, *xent_in = xent_input;
+  int64_t num_stride = three_d ? (int64_t)P : row_stride, xent_stride = row_stride;
   int rc = TC_OK;
   // (B, C, T) with the regulariser: xent_deriv has entries only where the numerator has posteriors, so it is written
   // straight into the caller's cleared (B, C, T) gradient, and the cross-entropy objective reads xent_input where it
@@ -643,17 +673,31 @@ int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, cons
   if (three_d) {
     y = second_only ? w.x2d : w.y2d;  // (filled inside chain_objf, beside the numerator: bct_input)
     gr = eval_only ? nullptr : w.g2d;
-    xg = use_xent && !eval_only ? xent_grad : nullptr;
+    // (16-bit: the numerator writes the float32 scratch, rounded into the caller's tensor at the end)
+    xg = use_xent && !eval_only ? (half ? w.xg : xent_grad) : nullptr;
     stride = P;
-    if (use_xent && !eval_only) {
+    if (xg) {
       DeviceGuard guard(device);
       if (!guard.ok) return TC_ERR_HIP;
-      TC_HIP_CHECK(hipMemsetAsync(xent_grad, 0, (size_t)rows * P * sizeof(float), stream));
+      TC_HIP_CHECK(hipMemsetAsync(xg, 0, (size_t)rows * P * sizeof(float), stream));
     }
+  } else if (half) {
+    // 16-bit 2-D tensors: widened into contiguous float32 matrices, on which the float32 2-D step runs as it is
+    DeviceGuard guard(device);
+    if (!guard.ok) return TC_ERR_HIP;
+    rc = launch_widen_rows(dtype, input, row_stride, w.y2d, rows, P, stream);
+    if (rc == TC_OK && use_xent) rc = launch_widen_rows(dtype, xent_input, row_stride, w.x2d, rows, P, stream);
+    if (rc != TC_OK) return rc;
+    y = second_only ? w.x2d : w.y2d;
+    gr = eval_only ? nullptr : w.g2d;
+    xg = use_xent && !eval_only ? w.xg : nullptr;
+    stride = P;
+    num_in = w.y2d;
+    xent_in = w.x2d;
+    num_stride = xent_stride = P;
   } else if (second_only) {
     y = xent_input;
   }
-  (void)xe;
   // 2-D: the matrices leave as the reference's backward returns them (-deriv, -xent_regularize * xent_deriv); 3-D: the
   // MMI gradient's sign rides on the way back through tc_from2d, so the 2-D scratch holds the plain derivative
   const float dscale = three_d ? 1.0f : -1.0f, xscale = -xent_regularize;  // (the (B, C, T) xent gradient: final values too)
@@ -665,12 +709,13 @@ int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, cons
     DeviceGuard guard(device);
     if (!guard.ok) return TC_ERR_HIP;
     NumParams np;
-    rc = fill_num_params(sup, device, stream, input, rows, P, three_d ? (int64_t)P : row_stride, nullptr, 0, nullptr, 0, wi.num_lp, &np);
+    rc = fill_num_params(sup, device, stream, num_in, rows, P, num_stride, nullptr, 0, nullptr, 0, wi.num_lp, &np);
     if (rc != TC_OK) return rc;
     np.y_bct = three_d ? 1 : 0;
+    np.elem = three_d ? dtype : TC_DTYPE_F32;
     np.xent_scale = xscale;
-    np.xent_out = xent_input;
-    np.xent_out_stride = row_stride;
+    np.xent_out = xent_in;
+    np.xent_out_stride = xent_stride;
     np.xent_out_bct = three_d ? 1 : 0;
     np.seq_xent = wi.xent_lp;
     rc = launch_num(np, stream);
@@ -678,13 +723,20 @@ int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, cons
     if (rc != TC_OK) return rc;
   }
   rc = chain_objf(g, sup, y, rows, P, stride, results_dev3, gr, gstride, xg, gstride, l2_regularize, leaky, dscale, xscale,
-                  w.chain, (int64_t)w.chain_bytes, device, stream_v, use_xent && !second_only ? xent_input : nullptr, row_stride,
+                  w.chain, (int64_t)w.chain_bytes, device, stream_v, use_xent && !second_only ? xent_in : nullptr, xent_stride,
                   use_xent ? xent_objf_dev : nullptr, bct, bct, three_d ? (second_only ? xent_input : input) : nullptr,
-                  second_only && xent_objf_dev != nullptr, loss_dev1);
+                  second_only && xent_objf_dev != nullptr, loss_dev1, dtype);
   if (rc != TC_OK) return rc;
-  if (three_d && !eval_only) {
+  if (three_d && !eval_only && !half) {
     rc = tc_from2d(gr, P, S, P, T, -1.0f, grad, device, stream_v);
     if (rc != TC_OK) return rc;
+  }
+  if (half && !eval_only) {
+    // the one rounding of every gradient element, from the float32 values tc_chain_step would have returned
+    DeviceGuard guard(device);
+    if (!guard.ok) return TC_ERR_HIP;
+    rc = three_d ? launch_from2d(dtype, gr, P, grad, S, P, T, -1.0f, stream) : launch_round(dtype, gr, grad, rows * P, stream);
+    if (rc == TC_OK && xg) rc = launch_round(dtype, xg, xent_grad, rows * P, stream);
   }
   return rc;  // (the loss value -objf / weight was written with the results: finalize_kernel)
 }

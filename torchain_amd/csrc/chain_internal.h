@@ -387,6 +387,9 @@ struct NumParams {
   // only its posteriors' entries, so the 3-D call needs no frame-major copy of either (tc_chain_step)
   int xent_bct = 0, xent_out_bct = 0, y_bct = 0;  // (y is read at the supervision's (frame, pdf) pairs only)
   int lds_states, lds_arcs, lds_uniq;
+  // TC_DTYPE_* of y and xent_out when they are the caller's 16-bit (B, C, T) tensors (tc_chain_step_typed): the kernels
+  // widen what they read; the 2-D pointers of this structure are always float32
+  int elem = TC_DTYPE_F32;
 };
 
 }  // namespace tc
@@ -494,6 +497,14 @@ int launch_trace_mat_mat(const float *a, int64_t a_stride, const float *b, int64
                          double *partial, double *out, hipStream_t stream);
 int launch_layout(bool to2d, const float *in, float *out, int B, int Cn, int T, int64_t stride2d, float scale,
                   hipStream_t stream);
+// the caller's tensors of tc_chain_step_typed (dtype: TC_DTYPE_*): the layout copies with the (B, C, T) side of that type
+// (TC_DTYPE_F32: launch_layout), the widening copy of 16-bit 2-D rows into a contiguous float32 matrix and the rounding
+// copy of n contiguous floats into 16 bits (these two: TC_DTYPE_BF16 / TC_DTYPE_F16 only)
+int launch_to2d(int dtype, const void *in_bct, float *out, int B, int Cn, int T, int64_t stride2d, hipStream_t stream);
+int launch_from2d(int dtype, const float *in, int64_t stride2d, void *out_bct, int B, int Cn, int T, float scale,
+                  hipStream_t stream);
+int launch_widen_rows(int dtype, const void *in, int64_t in_stride, float *out, int64_t rows, int cols, hipStream_t stream);
+int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t stream);
 
 extern thread_local int g_last_hip_error;
 

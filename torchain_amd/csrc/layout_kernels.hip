@@ -6,7 +6,11 @@
 // xent scale in one pass.  Both are plain HBM-bound transposes through LDS: a workgroup moves a
 // [64 channels] x [<= 240 frames] tile of one sequence, reading and writing 256-byte (or longer) runs; the
 // backward one reads its 2-D rows with 16-byte loads and writes 8-byte pairs where alignment allows.
+// The same two kernels take bfloat16 / float16 (B, C, T) tensors (tc_chain_step_typed): the forward one widens as it
+// reads, the backward one rounds once as it writes; the tile in LDS and the scale stay float32.  Two plain streams serve
+// 16-bit 2-D tensors: a widening copy of strided rows into a contiguous float32 matrix and a rounding copy back.
 #include "chain_internal.h"
+#include "half_io.h"
 
 namespace tc {
 
@@ -14,23 +18,42 @@ namespace {
 
 constexpr int kTileC = 64, kTileTMax = 240, kLayoutThreads = 512;
 
+// the (B, C, T) side holds E (the caller's tensor), the 2-D side float32 (the step's scratch)
+template <bool TO2D, typename E>
+struct LayoutIo {
+  using in_t = typename std::conditional<TO2D, typename Elem<E>::bits, float>::type;
+  using out_t = typename std::conditional<TO2D, float, typename Elem<E>::bits>::type;
+};
+
 // TO2D: in (B, C, T) contiguous -> out[(t*B + b) * out_stride + c];  !TO2D: the inverse, times `scale`
-template <bool TO2D, bool VEC>
-__global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const float *__restrict__ in, float *__restrict__ out,
+// (E = float: the float32 kernels; otherwise TO2D widens each element it reads, !TO2D rounds each one it writes)
+template <bool TO2D, bool VEC, typename E = float>
+__global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const typename LayoutIo<TO2D, E>::in_t *__restrict__ in,
+                                                                typename LayoutIo<TO2D, E>::out_t *__restrict__ out,
                                                                 int B, int Cn, int T, int64_t stride2d, float scale) {
+  constexpr bool kF32 = std::is_same<E, float>::value;
   extern __shared__ float tile[];  // kTileC x (frames of the tile | 1): sized by the launch, several blocks per CU
   const int c0 = blockIdx.x * kTileC, b = blockIdx.y, t0 = blockIdx.z * kTileTMax;
   const int tc = min(kTileTMax, T - t0), nc = min(kTileC, Cn - c0);
   const int pitch = tc | 1;  // odd pitch: the transposed accesses are bank-conflict-free
   const int tid = threadIdx.x;
-  const float *bct = TO2D ? in : out;  // the (B, C, T) side
-  (void)bct;
-  if (TO2D) {
+  if constexpr (TO2D) {
     // read runs of tc floats along t (for tc == T the whole tile is one contiguous block); dword accesses on both
     // sides: 16-byte row stores and 8-byte run loads were measured here and are slower (0.30 vs 0.26 ms at C3)
-    for (int idx = tid; idx < nc * tc; idx += kLayoutThreads) {
-      const int c = idx / tc, t = idx - c * tc;
-      tile[c * pitch + t] = in[((int64_t)b * Cn + c0 + c) * T + t0 + t];
+    if (!kF32 && VEC) {
+      // 16-bit runs: one dword = two frames when T is even (every run then starts 4-byte aligned; tc is even too)
+      const int half = tc / 2;
+      for (int idx = tid; idx < nc * half; idx += kLayoutThreads) {
+        const int c = idx / half, t = 2 * (idx - c * half);
+        const uint32_t v = *reinterpret_cast<const uint32_t *>(in + ((int64_t)b * Cn + c0 + c) * T + t0 + t);
+        tile[c * pitch + t] = Elem<E>::widen((uint16_t)(v & 0xFFFFu));
+        tile[c * pitch + t + 1] = Elem<E>::widen((uint16_t)(v >> 16));
+      }
+    } else {
+      for (int idx = tid; idx < nc * tc; idx += kLayoutThreads) {
+        const int c = idx / tc, t = idx - c * tc;
+        tile[c * pitch + t] = Elem<E>::widen(in[((int64_t)b * Cn + c0 + c) * T + t0 + t]);
+      }
     }
     __syncthreads();
     const int cx = tid & (kTileC - 1);
@@ -62,20 +85,92 @@ __global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const float *__r
         if (cx < nc) tile[cx * pitch + t] = in[((int64_t)(t0 + t) * B + b) * stride2d + c0 + cx];
     }
     __syncthreads();
-    // Write side: runs of tc floats per channel; 8-byte stores when every run starts 8-byte aligned
-    if (VEC && (T & 1) == 0 && (tc & 1) == 0) {
-      const int half = tc / 2;
-      for (int idx = tid; idx < nc * half; idx += kLayoutThreads) {
-        const int c = idx / half, t = 2 * (idx - c * half);
-        *reinterpret_cast<float2 *>(out + ((int64_t)b * Cn + c0 + c) * T + t0 + t) =
-            make_float2(scale * tile[c * pitch + t], scale * tile[c * pitch + t + 1]);
+    if constexpr (!kF32) {
+      // Write side of a 16-bit tensor: scale in float32, round once; 8-byte stores (4 frames) when every run starts
+      // 8-byte aligned, 4-byte ones (2 frames) when it starts 4-byte aligned
+      if (VEC && (T & 3) == 0) {
+        const int quad = tc / 4;
+        for (int idx = tid; idx < nc * quad; idx += kLayoutThreads) {
+          const int c = idx / quad, t = 4 * (idx - c * quad);
+          const float *src = tile + c * pitch + t;
+          const uint32_t lo = Elem<E>::round(scale * src[0]) | ((uint32_t)Elem<E>::round(scale * src[1]) << 16);
+          const uint32_t hi = Elem<E>::round(scale * src[2]) | ((uint32_t)Elem<E>::round(scale * src[3]) << 16);
+          *reinterpret_cast<uint2 *>(out + ((int64_t)b * Cn + c0 + c) * T + t0 + t) = make_uint2(lo, hi);
+        }
+      } else if (VEC && (T & 1) == 0) {
+        const int half = tc / 2;
+        for (int idx = tid; idx < nc * half; idx += kLayoutThreads) {
+          const int c = idx / half, t = 2 * (idx - c * half);
+          const float *src = tile + c * pitch + t;
+          *reinterpret_cast<uint32_t *>(out + ((int64_t)b * Cn + c0 + c) * T + t0 + t) =
+              Elem<E>::round(scale * src[0]) | ((uint32_t)Elem<E>::round(scale * src[1]) << 16);
+        }
+      } else {
+        for (int idx = tid; idx < nc * tc; idx += kLayoutThreads) {
+          const int c = idx / tc, t = idx - c * tc;
+          out[((int64_t)b * Cn + c0 + c) * T + t0 + t] = Elem<E>::round(scale * tile[c * pitch + t]);
+        }
       }
     } else {
-      for (int idx = tid; idx < nc * tc; idx += kLayoutThreads) {
-        const int c = idx / tc, t = idx - c * tc;
-        out[((int64_t)b * Cn + c0 + c) * T + t0 + t] = scale * tile[c * pitch + t];
+      // Write side: runs of tc floats per channel; 8-byte stores when every run starts 8-byte aligned
+      if (VEC && (T & 1) == 0 && (tc & 1) == 0) {
+        const int half = tc / 2;
+        for (int idx = tid; idx < nc * half; idx += kLayoutThreads) {
+          const int c = idx / half, t = 2 * (idx - c * half);
+          *reinterpret_cast<float2 *>(out + ((int64_t)b * Cn + c0 + c) * T + t0 + t) =
+              make_float2(scale * tile[c * pitch + t], scale * tile[c * pitch + t + 1]);
+        }
+      } else {
+        for (int idx = tid; idx < nc * tc; idx += kLayoutThreads) {
+          const int c = idx / tc, t = idx - c * tc;
+          out[((int64_t)b * Cn + c0 + c) * T + t0 + t] = scale * tile[c * pitch + t];
+        }
       }
     }
+  }
+}
+
+// 16-bit 2-D input -> float32: (rows, cols) with `in_stride` -> contiguous (rows, cols), one wave per row at a time.
+// VEC: 16-byte loads (8 elements) and two 16-byte stores, when cols and in_stride are multiples of 8 and both bases
+// 16-byte aligned.
+constexpr int kCastThreads = 256, kCastBlocksMax = 4096;
+template <typename E, bool VEC>
+__global__ __launch_bounds__(kCastThreads) void widen_rows_kernel(const uint16_t *__restrict__ in, int64_t in_stride,
+                                                                  float *__restrict__ out, int64_t rows, int cols) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * (kCastThreads / 64) + wave; r < rows; r += (int64_t)gridDim.x * (kCastThreads / 64)) {
+    const uint16_t *src = in + r * in_stride;
+    float *dst = out + r * cols;
+    if (VEC) {
+      for (int c = lane * 8; c < cols; c += 64 * 8) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(src + c);
+        *reinterpret_cast<float4 *>(dst + c) =
+            make_float4(Elem<E>::widen((uint16_t)(v.x & 0xFFFFu)), Elem<E>::widen((uint16_t)(v.x >> 16)),
+                        Elem<E>::widen((uint16_t)(v.y & 0xFFFFu)), Elem<E>::widen((uint16_t)(v.y >> 16)));
+        *reinterpret_cast<float4 *>(dst + c + 4) =
+            make_float4(Elem<E>::widen((uint16_t)(v.z & 0xFFFFu)), Elem<E>::widen((uint16_t)(v.z >> 16)),
+                        Elem<E>::widen((uint16_t)(v.w & 0xFFFFu)), Elem<E>::widen((uint16_t)(v.w >> 16)));
+      }
+    } else {
+      for (int c = lane; c < cols; c += 64) dst[c] = Elem<E>::widen(src[c]);
+    }
+  }
+}
+
+// float32 -> 16-bit, n contiguous elements, rounded once.  VEC: two 16-byte loads and one 16-byte store per 8 elements
+// (n a multiple of 8, both bases 16-byte aligned).
+template <typename E, bool VEC>
+__global__ __launch_bounds__(kCastThreads) void round_kernel(const float *__restrict__ in, uint16_t *__restrict__ out,
+                                                             int64_t n) {
+  const int64_t step = (int64_t)gridDim.x * kCastThreads;
+  if (VEC) {
+    for (int64_t i = (int64_t)blockIdx.x * kCastThreads + threadIdx.x; i < n / 8; i += step) {
+      const float4 a = reinterpret_cast<const float4 *>(in)[2 * i], b = reinterpret_cast<const float4 *>(in)[2 * i + 1];
+      auto pack = [](float lo, float hi) { return (uint32_t)Elem<E>::round(lo) | ((uint32_t)Elem<E>::round(hi) << 16); };
+      reinterpret_cast<uint4 *>(out)[i] = make_uint4(pack(a.x, a.y), pack(a.z, a.w), pack(b.x, b.y), pack(b.z, b.w));
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * kCastThreads + threadIdx.x; i < n; i += step) out[i] = Elem<E>::round(in[i]);
   }
 }
 
@@ -121,6 +216,98 @@ int launch_trace_mat_mat(const float *a, int64_t a_stride, const float *b, int64
   hipLaunchKernelGGL(trace_final_kernel, dim3(1), dim3(64), 0, stream, partial, out);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
+}
+
+namespace {
+
+template <typename E>
+int launch_layout_16(bool to2d, const void *in, void *out, int B, int Cn, int T, int64_t stride2d, float scale,
+                     hipStream_t stream) {
+  count_launch(kCntLayout);
+  const dim3 grid((Cn + kTileC - 1) / kTileC, B, (T + kTileTMax - 1) / kTileTMax);
+  const size_t lds = sizeof(float) * kTileC * ((size_t)(T < kTileTMax ? T : kTileTMax) | 1);
+  if (to2d) {
+    const uint16_t *src = static_cast<const uint16_t *>(in);
+    float *dst = static_cast<float *>(out);
+    if ((T & 1) == 0 && ((uintptr_t)in & 3) == 0)
+      hipLaunchKernelGGL((layout_kernel<true, true, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+    else
+      hipLaunchKernelGGL((layout_kernel<true, false, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+  } else {
+    const float *src = static_cast<const float *>(in);
+    uint16_t *dst = static_cast<uint16_t *>(out);
+    if (stride2d % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 7) == 0)
+      hipLaunchKernelGGL((layout_kernel<false, true, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+    else
+      hipLaunchKernelGGL((layout_kernel<false, false, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+  }
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
+
+int cast_blocks(int64_t items) {
+  const int64_t b = (items + kCastThreads - 1) / kCastThreads;
+  return (int)(b < 1 ? 1 : b > kCastBlocksMax ? kCastBlocksMax : b);
+}
+
+template <typename E>
+int launch_widen_rows_e(const void *in, int64_t in_stride, float *out, int64_t rows, int cols, hipStream_t stream) {
+  const uint16_t *src = static_cast<const uint16_t *>(in);
+  const int blocks = cast_blocks(rows * 64);  // (a wave per row)
+  if (cols % 8 == 0 && in_stride % 8 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0)
+    hipLaunchKernelGGL((widen_rows_kernel<E, true>), dim3(blocks), dim3(kCastThreads), 0, stream, src, in_stride, out, rows, cols);
+  else
+    hipLaunchKernelGGL((widen_rows_kernel<E, false>), dim3(blocks), dim3(kCastThreads), 0, stream, src, in_stride, out, rows, cols);
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
+
+template <typename E>
+int launch_round_e(const float *in, void *out, int64_t n, hipStream_t stream) {
+  uint16_t *dst = static_cast<uint16_t *>(out);
+  if (n % 8 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0)
+    hipLaunchKernelGGL((round_kernel<E, true>), dim3(cast_blocks(n / 8)), dim3(kCastThreads), 0, stream, in, dst, n);
+  else
+    hipLaunchKernelGGL((round_kernel<E, false>), dim3(cast_blocks(n)), dim3(kCastThreads), 0, stream, in, dst, n);
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
+
+}  // namespace
+
+int launch_to2d(int dtype, const void *in_bct, float *out, int B, int Cn, int T, int64_t stride2d, hipStream_t stream) {
+  switch (dtype) {
+    case TC_DTYPE_F32: return launch_layout(true, static_cast<const float *>(in_bct), out, B, Cn, T, stride2d, 1.0f, stream);
+    case TC_DTYPE_BF16: return launch_layout_16<__hip_bfloat16>(true, in_bct, out, B, Cn, T, stride2d, 1.0f, stream);
+    case TC_DTYPE_F16: return launch_layout_16<__half>(true, in_bct, out, B, Cn, T, stride2d, 1.0f, stream);
+  }
+  return TC_ERR_INVALID_ARGUMENT;
+}
+
+int launch_from2d(int dtype, const float *in, int64_t stride2d, void *out_bct, int B, int Cn, int T, float scale,
+                  hipStream_t stream) {
+  switch (dtype) {
+    case TC_DTYPE_F32: return launch_layout(false, in, static_cast<float *>(out_bct), B, Cn, T, stride2d, scale, stream);
+    case TC_DTYPE_BF16: return launch_layout_16<__hip_bfloat16>(false, in, out_bct, B, Cn, T, stride2d, scale, stream);
+    case TC_DTYPE_F16: return launch_layout_16<__half>(false, in, out_bct, B, Cn, T, stride2d, scale, stream);
+  }
+  return TC_ERR_INVALID_ARGUMENT;
+}
+
+int launch_widen_rows(int dtype, const void *in, int64_t in_stride, float *out, int64_t rows, int cols, hipStream_t stream) {
+  switch (dtype) {
+    case TC_DTYPE_BF16: return launch_widen_rows_e<__hip_bfloat16>(in, in_stride, out, rows, cols, stream);
+    case TC_DTYPE_F16: return launch_widen_rows_e<__half>(in, in_stride, out, rows, cols, stream);
+  }
+  return TC_ERR_INVALID_ARGUMENT;
+}
+
+int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t stream) {
+  switch (dtype) {
+    case TC_DTYPE_BF16: return launch_round_e<__hip_bfloat16>(in, out, n, stream);
+    case TC_DTYPE_F16: return launch_round_e<__half>(in, out, n, stream);
+  }
+  return TC_ERR_INVALID_ARGUMENT;
 }
 
 int launch_layout(bool to2d, const float *in, float *out, int B, int Cn, int T, int64_t stride2d, float scale,

@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include "chain_internal.h"
+#include "half_io.h"
 
 namespace tc {
 
@@ -79,18 +80,24 @@ __device__ __forceinline__ SeqView seq_view(const NumParams &p, int q) {
   return v;
 }
 
+// El: element type of y / xent_out when they are the caller's (B, C, T) tensors (NumParams::elem; 2-D: float32)
+template <typename El>
 __device__ __forceinline__ float load_y(const NumParams &p, int q, int t, int pdf) {
-  return p.y_bct ? p.y[((int64_t)q * p.P + pdf) * p.T + t] : p.y[((int64_t)t * p.S + q) * p.y_stride + pdf];
+  return p.y_bct ? load_elem<El>(p.y, ((int64_t)q * p.P + pdf) * p.T + t) : p.y[((int64_t)t * p.S + q) * p.y_stride + pdf];
 }
 
 // the sequence's posterior v = weight * gamma of (frame t, pdf) into deriv / xent, and its cross-entropy objective term
+template <typename El>
 __device__ __forceinline__ double write_posterior(const NumParams &p, int q, int t, int pdf, float v) {
   const int64_t row = (int64_t)t * p.S + q;
   const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + t;  // (sequence, pdf, frame) of a (B, C, T) tensor
   if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
   if (p.xent) p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_scale * v;
   if (p.seq_xent)
-    return (double)(p.xent_scale * v) * (double)p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf];
+    return (double)(p.xent_scale * v) * (double)(std::is_same<El, float>::value
+                                                     ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
+                                                     : p.xent_out_bct ? load_elem<El>(p.xent_out, bct)
+                                                                      : p.xent_out[row * p.xent_out_stride + pdf]);
   return 0.0;
 }
 
@@ -109,6 +116,7 @@ __device__ __forceinline__ void e2e_xent_sum(double v, double *out, int tid) {
 
 }  // namespace
 
+template <typename El = float>
 __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int MS = (p.t.e2e_tab.max_states + 3) & ~3, MP = (p.t.e2e_tab.max_pdfs + 3) & ~3;
@@ -132,7 +140,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
   }
   float ynx[kE2ePdfsPerThread];
 #pragma unroll
-  for (int r = 0; r < kE2ePdfsPerThread; ++r) ynx[r] = pk[r] >= 0 ? load_y(p, q, 0, pk[r]) : 0.f;
+  for (int r = 0; r < kE2ePdfsPerThread; ++r) ynx[r] = pk[r] >= 0 ? load_y<El>(p, q, 0, pk[r]) : 0.f;
   for (int i = tid; i < v.n; i += kE2eThreads) A[i] = i == start ? 0.0 : -INFINITY;
 
   // ---- forward ----
@@ -144,7 +152,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
       const int k = tid + r * kE2eThreads;
       E[k] = ynx[r];
       if (want_beta) v.stage[(int64_t)t * v.np + k] = ynx[r];
-      if (t + 1 < T) ynx[r] = load_y(p, q, t + 1, pk[r]);  // a frame ahead
+      if (t + 1 < T) ynx[r] = load_y<El>(p, q, t + 1, pk[r]);  // a frame ahead
     }
     __syncthreads();
     const double *a_cur = A + c * MS;
@@ -260,7 +268,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
       if (p.staged)
         v.stage[(int64_t)t * v.np + k] = val;  // launch_num_e2e_scatter adds it once the denominator has written deriv
       else
-        xo += write_posterior(p, q, t, pk[r], val);
+        xo += write_posterior<El>(p, q, t, pk[r], val);
     }
     c = 1 - c;
   }
@@ -276,6 +284,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
 
 // Second half of a staged e2e numerator: deriv[row, pdf] += weight * posterior, xent_deriv[row, pdf] = it.  Each
 // (frame, pdf) of a sequence has one owner; the sequence's cross-entropy sum is added in a fixed order.
+template <typename El = float>
 __global__ __launch_bounds__(kE2eThreads) void num_e2e_scatter_kernel(const NumParams p) {
   const int q = blockIdx.x, tid = threadIdx.x;
   const E2eDev &e = p.t.e2e_tab;
@@ -286,7 +295,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_scatter_kernel(const NumP
   const int64_t n = (int64_t)p.T * np;
   for (int64_t i = tid; i < n; i += kE2eThreads) {
     const int t = (int)(i / np), k = (int)(i - (int64_t)t * np);
-    xo += write_posterior(p, q, t, pdf_of[k], stage[i]);
+    xo += write_posterior<El>(p, q, t, pdf_of[k], stage[i]);
   }
   if (p.seq_xent) e2e_xent_sum(xo, p.seq_xent + q, tid);
 }
@@ -303,15 +312,28 @@ int launch_num_e2e(const NumParams &p, hipStream_t stream) {
   if (e.max_states > TC_E2E_MAX_STATES || e.max_arcs > TC_E2E_MAX_ARCS || e.max_pdfs > TC_E2E_MAX_PDFS)
     return TC_ERR_UNSUPPORTED;
   const size_t lds = num_e2e_lds_bytes(e.max_states, e.max_arcs, e.max_pdfs);
-  TC_HIP_CHECK(allow_dynamic_lds((const void *)num_e2e_kernel, lds));
-  hipLaunchKernelGGL(num_e2e_kernel, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
+  const void *kernel = p.elem == TC_DTYPE_BF16 ? (const void *)num_e2e_kernel<__hip_bfloat16>
+                       : p.elem == TC_DTYPE_F16 ? (const void *)num_e2e_kernel<__half>
+                                                : (const void *)num_e2e_kernel<float>;
+  TC_HIP_CHECK(allow_dynamic_lds(kernel, lds));
+  if (p.elem == TC_DTYPE_BF16)
+    hipLaunchKernelGGL(num_e2e_kernel<__hip_bfloat16>, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
+  else if (p.elem == TC_DTYPE_F16)
+    hipLaunchKernelGGL(num_e2e_kernel<__half>, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
+  else
+    hipLaunchKernelGGL(num_e2e_kernel<float>, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }
 
 int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream) {
   if (!p.deriv && !p.xent && !p.seq_xent) return TC_OK;
-  hipLaunchKernelGGL(num_e2e_scatter_kernel, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
+  if (p.elem == TC_DTYPE_BF16)
+    hipLaunchKernelGGL(num_e2e_scatter_kernel<__hip_bfloat16>, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
+  else if (p.elem == TC_DTYPE_F16)
+    hipLaunchKernelGGL(num_e2e_scatter_kernel<__half>, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
+  else
+    hipLaunchKernelGGL(num_e2e_scatter_kernel<float>, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }

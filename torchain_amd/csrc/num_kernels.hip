@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "chain_internal.h"
+#include "half_io.h"
 
 namespace tc {
 
@@ -48,7 +49,8 @@ __device__ __forceinline__ void seq_xent_sum(double v, double *out, int tid) {
   }
 }
 
-template <bool STAGE>
+// E: element type of y / xent_out when they are the caller's (B, C, T) tensors (NumParams::elem; 2-D: float32)
+template <bool STAGE, typename E = float>
 __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   double *log_alpha = reinterpret_cast<double *>(lds_raw);
@@ -105,8 +107,12 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
 
   // gather: [K] nnet_output_.Lookup(nnet_output_indexes_, ...); row = t*S + q
   for (int u = tid; u < nu; u += 128)
-    ylp[u] = p.y_bct ? p.y[((int64_t)q * p.P + p.t.uniq_pdf[ub + u]) * T + p.t.uniq_t[ub + u]]
-                     : p.y[((int64_t)p.t.uniq_t[ub + u] * S + q) * p.y_stride + p.t.uniq_pdf[ub + u]];
+    if constexpr (std::is_same<E, float>::value)
+      ylp[u] = p.y_bct ? p.y[((int64_t)q * p.P + p.t.uniq_pdf[ub + u]) * T + p.t.uniq_t[ub + u]]
+                       : p.y[((int64_t)p.t.uniq_t[ub + u] * S + q) * p.y_stride + p.t.uniq_pdf[ub + u]];
+    else
+      ylp[u] = p.y_bct ? load_elem<E>(p.y, ((int64_t)q * p.P + p.t.uniq_pdf[ub + u]) * T + p.t.uniq_t[ub + u])
+                       : p.y[((int64_t)p.t.uniq_t[ub + u] * S + q) * p.y_stride + p.t.uniq_pdf[ub + u]];
   for (int i = tid; i < nst; i += 128) {
     log_alpha[i] = i == 0 ? 0.0 : -INFINITY;
     log_beta[i] = -INFINITY;
@@ -181,13 +187,19 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
     if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
     const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + p.t.uniq_t[ub + u];  // (sequence, pdf, frame) of a (B, C, T) tensor
     if (p.xent) p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_scale * v;
-    if (p.seq_xent) xo += (double)(p.xent_scale * v) * (double)p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf];
+    // (the cross-entropy output: the caller's (B, C, T) tensor of element type E, or a float32 matrix)
+    if (p.seq_xent)
+      xo += (double)(p.xent_scale * v) * (double)(std::is_same<E, float>::value
+                                                      ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
+                                                  : p.xent_out_bct ? load_elem<E>(p.xent_out, bct)
+                                                                   : p.xent_out[row * p.xent_out_stride + pdf]);
   }
   if (p.seq_xent && !p.staged) seq_xent_sum(xo, p.seq_xent + q, tid);
 }
 
 // Second half of a staged numerator: deriv[row, pdf] += weight * posterior, xent_deriv[row, pdf] = it, one owner
 // per (row, pdf) as above.
+template <typename E = float>
 __global__ __launch_bounds__(128) void num_scatter_kernel(const NumParams p) {
   const int q = blockIdx.x, S = p.S;
   const int ub = p.t.seq_uniq_off[q], nu = p.t.seq_uniq_off[q + 1] - ub;
@@ -199,7 +211,12 @@ __global__ __launch_bounds__(128) void num_scatter_kernel(const NumParams p) {
     if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
     const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + p.t.uniq_t[ub + u];  // (sequence, pdf, frame) of a (B, C, T) tensor
     if (p.xent) p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_scale * v;
-    if (p.seq_xent) xo += (double)(p.xent_scale * v) * (double)p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf];
+    // (the cross-entropy output: the caller's (B, C, T) tensor of element type E, or a float32 matrix)
+    if (p.seq_xent)
+      xo += (double)(p.xent_scale * v) * (double)(std::is_same<E, float>::value
+                                                      ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
+                                                  : p.xent_out_bct ? load_elem<E>(p.xent_out, bct)
+                                                                   : p.xent_out[row * p.xent_out_stride + pdf]);
   }
   if (p.seq_xent) seq_xent_sum(xo, p.seq_xent + q, threadIdx.x);
 }
@@ -207,10 +224,32 @@ __global__ __launch_bounds__(128) void num_scatter_kernel(const NumParams p) {
 int launch_num_scatter(const NumParams &p, hipStream_t stream) {
   if (p.t.e2e) return launch_num_e2e_scatter(p, stream);  // end-to-end supervision: num_e2e_kernels.hip
   if (!p.deriv && !p.xent && !p.seq_xent) return TC_OK;
-  hipLaunchKernelGGL(num_scatter_kernel, dim3(p.S), dim3(128), 0, stream, p);
+  if (p.elem == TC_DTYPE_BF16)
+    hipLaunchKernelGGL(num_scatter_kernel<__hip_bfloat16>, dim3(p.S), dim3(128), 0, stream, p);
+  else if (p.elem == TC_DTYPE_F16)
+    hipLaunchKernelGGL(num_scatter_kernel<__half>, dim3(p.S), dim3(128), 0, stream, p);
+  else
+    hipLaunchKernelGGL(num_scatter_kernel<float>, dim3(p.S), dim3(128), 0, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }
+
+namespace {
+template <bool STAGE, typename E>
+int launch_num_fwd_bwd(const NumParams &p, size_t lds, hipStream_t stream) {
+  TC_HIP_CHECK(allow_dynamic_lds((const void *)num_fwd_bwd_kernel<STAGE, E>, lds));
+  hipLaunchKernelGGL((num_fwd_bwd_kernel<STAGE, E>), dim3(p.S), dim3(128), lds, stream, p);
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
+
+template <bool STAGE>
+int launch_num_fwd_bwd(const NumParams &p, size_t lds, hipStream_t stream) {
+  if (p.elem == TC_DTYPE_BF16) return launch_num_fwd_bwd<STAGE, __hip_bfloat16>(p, lds, stream);
+  if (p.elem == TC_DTYPE_F16) return launch_num_fwd_bwd<STAGE, __half>(p, lds, stream);
+  return launch_num_fwd_bwd<STAGE, float>(p, lds, stream);
+}
+}  // namespace
 
 int launch_num(const NumParams &p, hipStream_t stream) {
   if (p.t.e2e) return launch_num_e2e(p, stream);  // end-to-end supervision: num_e2e_kernels.hip
@@ -220,16 +259,8 @@ int launch_num(const NumParams &p, hipStream_t stream) {
   if (lds > (size_t)kLdsLimitBytes) return TC_ERR_UNSUPPORTED;
   // with the sequence's tables staged in LDS when that keeps a workgroup within a quarter of a CU's LDS
   const size_t staged = lds + ((size_t)2 * (p.lds_states + 2) + (size_t)5 * p.lds_arcs + (size_t)(p.T + 2)) * 4;
-  if (staged <= (size_t)kLdsLimitBytes / 4) {
-    TC_HIP_CHECK(allow_dynamic_lds((const void *)num_fwd_bwd_kernel<true>, staged));
-    hipLaunchKernelGGL(num_fwd_bwd_kernel<true>, dim3(p.S), dim3(128), staged, stream, p);
-    TC_HIP_CHECK(hipGetLastError());
-    return TC_OK;
-  }
-  TC_HIP_CHECK(allow_dynamic_lds((const void *)num_fwd_bwd_kernel<false>, lds));
-  hipLaunchKernelGGL(num_fwd_bwd_kernel<false>, dim3(p.S), dim3(128), lds, stream, p);
-  TC_HIP_CHECK(hipGetLastError());
-  return TC_OK;
+  if (staged <= (size_t)kLdsLimitBytes / 4) return launch_num_fwd_bwd<true>(p, staged, stream);
+  return launch_num_fwd_bwd<false>(p, lds, stream);
 }
 
 // ---- scalar epilogue: [K] ComputeChainObjfAndDeriv after the two computations --------------------

@@ -14,6 +14,10 @@ Same names, argument meaning, defaults and quirks as the reference:
   (``functions.py:106-115``).
 * ``kaldi_way=False`` re-runs the whole objective on ``xent_input`` and overwrites ``results`` and
   the MMI gradient with that second call's outputs, as the reference does (``functions.py:96-103``).
+* bfloat16 / float16 inputs (a mixed-precision model's output) take the same one call (``tc_chain_step_typed``): the
+  library widens them as it reads them and rounds the gradients once as it writes them, so ``results`` are those of
+  ``input.float()``, the loss is that loss in the input's dtype and the gradients are the float32 ones ``.to(dtype)``.
+  ``input`` and ``xent_input`` of different dtypes are up-cast to float32 first (correct, not the fast path).
 """
 import ctypes as C
 
@@ -21,7 +25,11 @@ import torch
 from torch.autograd import Function
 
 from . import io
-from ._lib import check, lib
+from ._lib import TC_DTYPE_BF16, TC_DTYPE_F16, TC_DTYPE_F32, check, lib
+
+# element types tc_chain_step(_typed) takes as they are
+_STEP_DTYPES = {torch.float32: TC_DTYPE_F32, torch.bfloat16: TC_DTYPE_BF16, torch.float16: TC_DTYPE_F16}
+_HALF = (torch.bfloat16, torch.float16)
 
 
 class ChainResults:
@@ -311,7 +319,7 @@ class _ChainStep(Function):
         ctx.grads = (grad, xgrad)
         if results._defer_host_copy:
             return input.new_zeros(1)
-        return out[3:4]
+        return out[3:4].to(input.dtype)
 
     @staticmethod
     def backward(ctx, grad_output):
@@ -339,15 +347,21 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         raise ValueError("nnet output of shape %s does not match the supervision (%s expected)" % (tuple(input.shape), want))
     x = input.detach()
     xe = xent_input.detach() if use_xent else None
+    dtype = _STEP_DTYPES[x.dtype]
+    if xe is not None and xe.dtype != x.dtype:
+        raise ValueError("input and xent_input must have the same dtype (%s, %s)" % (x.dtype, xe.dtype))
     grad = torch.empty_like(x, memory_format=torch.contiguous_format) if want_grad else None
     xgrad = torch.empty_like(xe, memory_format=torch.contiguous_format) if use_xent and want_grad else None
     with torch.cuda.device(device):
         cur = torch.cuda.current_stream(device)
-        key = (S, T, three_d, use_xent)
+        key = (S, T, three_d, use_xent, dtype)
         sizes = den_graph.__dict__.setdefault("_step_bytes", {}) if isinstance(den_graph, io.DenominatorGraph) else {}
         nbytes = sizes.get(key)
         if nbytes is None:
-            nbytes = lib.tc_chain_step_workspace_bytes(den_ptr, S, T, int(three_d), int(use_xent))
+            if dtype == TC_DTYPE_F32:
+                nbytes = lib.tc_chain_step_workspace_bytes(den_ptr, S, T, int(three_d), int(use_xent))
+            else:
+                nbytes = lib.tc_chain_step_typed_workspace_bytes(den_ptr, S, T, int(three_d), int(use_xent), dtype)
             if nbytes < 0:
                 check(int(nbytes), "tc_chain_step_workspace_bytes")
             sizes[key] = nbytes
@@ -355,12 +369,15 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         # (inside a graph capture the workspace comes from the graph's own pool and lives as long as the graph does)
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device) if capturing else _workspace(device, cur.cuda_stream, nbytes)
         out = torch.empty(6, dtype=torch.float32, device=device)  # objf, l2_term, weight | loss | xent objective (f64)
-        rc = lib.tc_chain_step(den_ptr, sup_ptr, _ptr(x), _ptr(xe), int(three_d), 0 if three_d else x.stride(0),
-                               float(l2_regularize), float(leaky_hmm_coefficient), float(xent_regularize),
-                               int(bool(kaldi_way)), _ptr(grad), _ptr(xgrad), C.c_void_p(out.data_ptr()),
-                               C.c_void_p(out.data_ptr() + 12), C.c_void_p(out.data_ptr() + 16) if use_xent else None,
-                               _ptr(ws), ws.numel(), device.index, C.c_void_p(cur.cuda_stream))
-        check(rc, "tc_chain_step")
+        args = (den_ptr, sup_ptr, _ptr(x), _ptr(xe), int(three_d), 0 if three_d else x.stride(0), float(l2_regularize),
+                float(leaky_hmm_coefficient), float(xent_regularize), int(bool(kaldi_way)), _ptr(grad), _ptr(xgrad),
+                C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 12),
+                C.c_void_p(out.data_ptr() + 16) if use_xent else None)
+        tail = (_ptr(ws), ws.numel(), device.index, C.c_void_p(cur.cuda_stream))
+        if dtype == TC_DTYPE_F32:
+            check(lib.tc_chain_step(*args, *tail), "tc_chain_step")
+        else:  # bfloat16 / float16: widened on the way in, gradients rounded once on the way out
+            check(lib.tc_chain_step_typed(*args, dtype, *tail), "tc_chain_step_typed")
         results._dev = out[:3]
         results._stale = True
         results._ready = None
@@ -378,10 +395,11 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
 
 
 def _one_call(x):
-    """Tensors ``tc_chain_step`` takes as they are: CUDA float32, (B, C, T) contiguous or 2-D with unit column stride."""
+    """Tensors ``tc_chain_step`` takes as they are: CUDA float32 (or bfloat16 / float16: ``tc_chain_step_typed``),
+    (B, C, T) contiguous or 2-D with unit column stride."""
     if x is None:
         return True
-    if not (x.is_cuda and x.dtype == torch.float32):
+    if not (x.is_cuda and x.dtype in _STEP_DTYPES):
         return False
     return (x.dim() == 3 and x.is_contiguous()) or (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1])
 
@@ -396,9 +414,31 @@ def _as_step_input(x):
     """A tensor ``tc_chain_step`` takes as it is (evaluation steps only: nothing flows back, so a copy is harmless)."""
     assert x.is_cuda, "Only CUDA implementation is available"
     x = x.detach()
-    if x.dtype != torch.float32:
+    if x.dtype not in _STEP_DTYPES:
         x = x.float()
     return x if _one_call(x) else x.contiguous()
+
+
+def _same_dtype(input, xent_input):
+    """``input`` and ``xent_input`` of different dtypes: the 16-bit one(s) up-cast to float32 (tracked by autograd), which
+    takes the float32 path -- correct, but with the two extra passes the 16-bit one call saves."""
+    if xent_input is None or xent_input.dtype == input.dtype:
+        return input, xent_input
+    return (input.float() if input.dtype in _HALF else input), (xent_input.float() if xent_input.dtype in _HALF else xent_input)
+
+
+def _half_one_call(input, xent_input):
+    """16-bit CUDA inputs in a layout ``tc_chain_step_typed`` does not take as it is: made contiguous (tracked by autograd)
+    so that the step is still one call; up-cast to float32 when even that does not fit (a 3-D input with a 2-D
+    ``xent_input``)."""
+    input = input if _one_call(input) else input.contiguous()
+    if xent_input is not None:
+        xent_input = xent_input if _one_call(xent_input) else xent_input.contiguous()
+        if xent_input.dim() != input.dim():
+            return input.float(), xent_input.float()
+        if input.dim() == 2 and xent_input.stride(0) != input.stride(0):
+            input, xent_input = input.contiguous(), xent_input.contiguous()
+    return input, xent_input
 
 
 def to2d(x):
@@ -424,6 +464,7 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
                      xent_input, kaldi_way):
     """``chain_loss`` with the ``ChainResults`` given (parallel.chain_loss_data_parallel passes one that defers the
     host copy of the three floats until after its all-reduce)."""
+    input, xent_input = _same_dtype(input, xent_input)
     if not _needs_grad(input, xent_input):
         # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the
         # forward recursions only.  The reference has no such check (functions.py:74,82) and pays for a training step.
@@ -431,6 +472,8 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
         out, _, _ = _run_step(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
                               xent_regularize, kaldi_way, want_grad=False)
         return (input.new_zeros(1) if results._defer_host_copy else out[3:4].to(input.dtype)), results
+    if input.is_cuda and input.dtype in _HALF:
+        input, xent_input = _half_one_call(input, xent_input)
     if (_one_call(input) and _one_call(xent_input) and (xent_input is None or xent_input.dim() == input.dim())
             and (xent_input is None or xent_input.dim() == 3 or xent_input.stride(0) == input.stride(0))):
         loss = _ChainStep.apply(input, xent_input, results, den_graph, supervision,

@@ -60,9 +60,13 @@ chain_step.register_autograd(_backward, setup_context=_setup)
 def chain_loss_op(input, den_graph, supervision, l2_regularize=0.0, leaky_hmm_coefficient=1e-5, xent_regularize=0.0, xent_input=None,
                   kaldi_way=False):
     """``functions.chain_loss`` through the registered operator: ``(loss, results)`` with the same values and gradients.  Inputs
-    must be what ``tc_chain_step`` takes as they are (CUDA float32, (B, C, T) contiguous or 2-D with unit column stride)."""
+    must be what ``tc_chain_step`` takes as they are (CUDA float32, bfloat16 or float16, one dtype for both; (B, C, T)
+    contiguous or 2-D with unit column stride).  The loss has the input's dtype, ``results`` stay float32."""
     if not (functions._one_call(input) and functions._one_call(xent_input)):
-        raise ValueError("chain_loss_op needs CUDA float32 tensors, (B, C, T) contiguous or 2-D with unit column stride")
+        raise ValueError("chain_loss_op needs CUDA float32 / bfloat16 / float16 tensors, (B, C, T) contiguous or 2-D with unit "
+                         "column stride")
+    if xent_input is not None and xent_input.dtype != input.dtype:
+        raise ValueError("chain_loss_op needs input and xent_input of one dtype (%s, %s)" % (input.dtype, xent_input.dtype))
     if isinstance(den_graph, io.DenominatorGraph):
         den_graph.prepare(input.device)
     want_grad = functions._needs_grad(input, xent_input)
@@ -80,4 +84,4 @@ def chain_loss_op(input, den_graph, supervision, l2_regularize=0.0, leaky_hmm_co
         results._xent_dev = out.detach()[4:6].view(torch.float64)
         results._xent_ready = results._ready
         results._xent_scale = 1.0 / -float(xent_regularize)
-    return out[3:4], results
+    return out[3:4].to(input.dtype), results
