@@ -353,6 +353,32 @@ int tc_chain_step_typed(tc_den_graph *graph, tc_supervision *supervision, const 
                         float *loss_dev1, double *xent_objf_dev, int dtype, void *workspace, int64_t workspace_bytes,
                         int device, void *stream);
 
+/* tc_chain_step_typed with Kaldi's per-frame derivative weights ([K] nnet-chain-training.cc: with apply_deriv_weights,
+ * nnet_output_deriv.MulRowsVec(deriv_weights) and the same on xent_deriv, after both objectives are formed).
+ * deriv_weights: device float32[S * T], 4-byte aligned (else TC_ERR_INVALID_ARGUMENT), one per frame-major row t * S + s
+ * (the row order of the 2-D tensors, and of the egs' <DW> / <DW2> weights); NULL is tc_chain_step_typed itself, which is
+ * this entry's NULL case.
+ *   gradients : every element tc_chain_step_typed writes as g[row, pdf] becomes w[row] * g, one float32 multiply of the
+ *               unweighted float32 value; for bfloat16 / float16 that product is rounded once, to nearest even.  This
+ *               holds for the MMI gradient, the xent gradient (both kaldi_way settings) and the soft-failure gradient
+ *               (-l2 * weight * y, or 0).  So for w >= 0 it is bit for bit the unweighted gradient times w; for w < 0 the
+ *               values agree but a zero's sign may differ.
+ *   scalars   : results_dev3, loss_dev1 and xent_objf_dev are those of the unweighted call, bit for bit (the cross-entropy
+ *               objective sums the unweighted xent_deriv; the weight does not depend on w).
+ *   where     : three_d != 0: the layout copy back applies -w[row] in its one multiply (float32 and 16-bit); the xent
+ *               entries are weighted as the numerator writes them.  three_d == 0: 16-bit: the rounding pass of the MMI
+ *               gradient applies w, the numerator weights the xent entries; float32: the numerator weights the xent
+ *               entries, and one in-place pass over the MMI gradient (behind the soft-failure reset) applies w.  The
+ *               denominator kernels are not involved.
+ *   grad == NULL (an evaluation step): deriv_weights is not read.
+ * Workspace: tc_chain_step_typed_workspace_bytes (unchanged).  No host synchronisation; safe under stream capture, where
+ * the pointer is baked into the graph and each replay reads the weights' current contents. */
+int tc_chain_step_weighted(tc_den_graph *graph, tc_supervision *supervision, const void *input, const void *xent_input,
+                           int three_d, int64_t row_stride, float l2_regularize, float leaky_hmm_coefficient,
+                           float xent_regularize, int kaldi_way, void *grad, void *xent_grad, float *results_dev3,
+                           float *loss_dev1, double *xent_objf_dev, const float *deriv_weights, int dtype, void *workspace,
+                           int64_t workspace_bytes, int device, void *stream);
+
 /* The benchmarked unit: [K] DenominatorComputation::Forward() + Backward(deriv_weight, deriv)
  * (direct use in the reference: src/chain-supervision-test.hpp:403-414).
  *   logprob_dev   : device double[1], sum over sequences of the denominator log-prob

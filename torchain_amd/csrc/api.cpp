@@ -447,13 +447,15 @@ int tc_num_forward_backward(tc_supervision *sup, const float *y, int64_t rows, i
 // area for the scatter behind the denominator, as for small batches).
 // xent_out / xent_objf_dev (tc_chain_step): the cross-entropy output and where sum(xent_out * xent) goes -- formed from
 // the numerator's posteriors as they are written, not from the dense matrices
+// xent_row_w (tc_chain_step_weighted): the per-row factor of the xent entries the numerator writes (not of its objective sum)
 static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int64_t rows, int32_t cols,
                       int64_t y_stride, float *results_dev3, float *deriv, int64_t deriv_stride, float *xent,
                       int64_t xent_stride, float l2_regularize, float leaky, float deriv_scale, float xent_scale,
                       void *workspace, int64_t workspace_bytes, int device, void *stream_v,
                       const float *xent_out = nullptr, int64_t xent_out_stride = 0, double *xent_objf_dev = nullptr,
                       int xent_bct = 0, int xent_out_bct = 0, const float *bct_input = nullptr,
-                      bool xent_sums_ready = false, float *loss_dev1 = nullptr, int bct_dtype = TC_DTYPE_F32) {
+                      bool xent_sums_ready = false, float *loss_dev1 = nullptr, int bct_dtype = TC_DTYPE_F32,
+                      const float *xent_row_w = nullptr) {
   if (!g || !sup || !y || !results_dev3) return TC_ERR_INVALID_ARGUMENT;
   if (sup->P != g->P) return TC_ERR_INVALID_ARGUMENT;
   if ((int64_t)sup->S * sup->T != rows) return TC_ERR_INVALID_ARGUMENT;
@@ -482,6 +484,7 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
     np.seq_xent = w.xent_lp;
   }
   np.xent_bct = xent_bct;  // (a (B, C, T) tensor the caller has cleared: only the posteriors' entries are written)
+  np.xent_row_w = xent ? xent_row_w : nullptr;  // (tc_chain_step_weighted: the numerator is xent's only non-zero writer)
   if (bct_input) {
     np.y = bct_input;
     np.y_bct = 1;
@@ -631,7 +634,18 @@ int tc_chain_step_typed(tc_den_graph *g, tc_supervision *sup, const void *input_
                         int64_t row_stride, float l2_regularize, float leaky, float xent_regularize, int kaldi_way,
                         void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
                         int dtype, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  return tc_chain_step_weighted(g, sup, input_v, xent_input_v, three_d, row_stride, l2_regularize, leaky, xent_regularize,
+                                kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev, nullptr, dtype,
+                                workspace, workspace_bytes, device, stream_v);
+}
+
+int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v,
+                           int three_d, int64_t row_stride, float l2_regularize, float leaky, float xent_regularize,
+                           int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1,
+                           double *xent_objf_dev, const float *deriv_weights, int dtype, void *workspace,
+                           int64_t workspace_bytes, int device, void *stream_v) {
   if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)deriv_weights & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
   // (16-bit tensors travel as float pointers up to the kernels that read or write them: NumParams::elem, launch_to2d)
   const float *input = static_cast<const float *>(input_v), *xent_input = static_cast<const float *>(xent_input_v);
   float *grad = static_cast<float *>(grad_v), *xent_grad = static_cast<float *>(xent_grad_v);
@@ -648,7 +662,14 @@ int tc_chain_step_typed(tc_den_graph *g, tc_supervision *sup, const void *input_
   if (P != g->P) return TC_ERR_INVALID_ARGUMENT;
   const int64_t rows = (int64_t)S * T;
   if (!three_d && row_stride < P) return TC_ERR_INVALID_ARGUMENT;
-  if (half && three_d && (S > 65535 || (T + 239) / 240 > 65535)) return TC_ERR_UNSUPPORTED;  // (tc_from2d's limits)
+  // (tc_from2d's limits; the float32 unweighted call meets them in tc_from2d itself)
+  if ((half || deriv_weights) && three_d && (S > 65535 || (T + 239) / 240 > 65535)) return TC_ERR_UNSUPPORTED;
+  // Kaldi's deriv_weights ([K] nnet-chain-training.cc: MulRowsVec on both derivatives, after the objectives are formed):
+  // ignored by an evaluation step, which writes no gradient.  Every gradient element becomes w[row] * g, one float32
+  // multiply of the unweighted value, in whichever pass writes it last: the layout copy back ((B, C, T)), the rounding
+  // pass (16-bit 2-D), the numerator's xent stores (all layouts), and for the float32 2-D MMI gradient, which the
+  // denominator and the numerator write into the caller's tensor, one in-place pass over it.
+  const float *row_w = eval_only ? nullptr : deriv_weights;
   const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype);
   if (!workspace || (int64_t)w.total > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_v;
@@ -725,17 +746,32 @@ int tc_chain_step_typed(tc_den_graph *g, tc_supervision *sup, const void *input_
   rc = chain_objf(g, sup, y, rows, P, stride, results_dev3, gr, gstride, xg, gstride, l2_regularize, leaky, dscale, xscale,
                   w.chain, (int64_t)w.chain_bytes, device, stream_v, use_xent && !second_only ? xent_in : nullptr, xent_stride,
                   use_xent ? xent_objf_dev : nullptr, bct, bct, three_d ? (second_only ? xent_input : input) : nullptr,
-                  second_only && xent_objf_dev != nullptr, loss_dev1, dtype);
+                  second_only && xent_objf_dev != nullptr, loss_dev1, dtype, row_w);
   if (rc != TC_OK) return rc;
   if (three_d && !eval_only && !half) {
-    rc = tc_from2d(gr, P, S, P, T, -1.0f, grad, device, stream_v);
+    if (row_w) {
+      DeviceGuard guard(device);
+      if (!guard.ok) return TC_ERR_HIP;
+      rc = launch_from2d(TC_DTYPE_F32, gr, P, grad, S, P, T, -1.0f, stream, row_w);  // (-w[row] * g, one multiply)
+    } else {
+      rc = tc_from2d(gr, P, S, P, T, -1.0f, grad, device, stream_v);
+    }
+    if (rc != TC_OK) return rc;
+  }
+  if (!three_d && !half && row_w) {
+    // behind chain_objf's launch_zero_on_fail, so a soft failure's -l2 * weight * y is weighted too
+    DeviceGuard guard(device);
+    if (!guard.ok) return TC_ERR_HIP;
+    rc = launch_scale_rows(gr, rows, P, row_w, stream);
     if (rc != TC_OK) return rc;
   }
   if (half && !eval_only) {
-    // the one rounding of every gradient element, from the float32 values tc_chain_step would have returned
+    // the one rounding of every gradient element, from the float32 values tc_chain_step would have returned (times
+    // the row's weight for the MMI gradient; the numerator has weighted the xent gradient's entries already)
     DeviceGuard guard(device);
     if (!guard.ok) return TC_ERR_HIP;
-    rc = three_d ? launch_from2d(dtype, gr, P, grad, S, P, T, -1.0f, stream) : launch_round(dtype, gr, grad, rows * P, stream);
+    rc = three_d ? launch_from2d(dtype, gr, P, grad, S, P, T, -1.0f, stream, row_w)
+                 : launch_round(dtype, gr, grad, rows * P, stream, row_w, P);
     if (rc == TC_OK && xg) rc = launch_round(dtype, xg, xent_grad, rows * P, stream);
   }
   return rc;  // (the loss value -objf / weight was written with the results: finalize_kernel)

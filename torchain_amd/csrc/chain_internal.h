@@ -390,6 +390,10 @@ struct NumParams {
   // TC_DTYPE_* of y and xent_out when they are the caller's 16-bit (B, C, T) tensors (tc_chain_step_typed): the kernels
   // widen what they read; the 2-D pointers of this structure are always float32
   int elem = TC_DTYPE_F32;
+  // per-row factor of the xent stores (tc_chain_step_weighted: Kaldi's deriv_weights, indexed by the frame-major row
+  // t*S + s): xent[...] = xent_row_w[row] * (xent_scale * v).  seq_xent keeps summing the unweighted xent_scale * v, and
+  // deriv is not weighted here.  Null: no factor.
+  const float *xent_row_w = nullptr;
 };
 
 }  // namespace tc
@@ -495,16 +499,23 @@ int launch_step_loss(const float *results3, float *loss1, hipStream_t stream);
 int64_t trace_workspace_bytes();
 int launch_trace_mat_mat(const float *a, int64_t a_stride, const float *b, int64_t b_stride, int64_t rows, int cols,
                          double *partial, double *out, hipStream_t stream);
+// row_w (the way back, !to2d; tc_chain_step_weighted): a per-row factor of the 2-D side, out = scale * row_w[row] * in
+// formed as (scale * row_w[row]) * in; null: out = scale * in
 int launch_layout(bool to2d, const float *in, float *out, int B, int Cn, int T, int64_t stride2d, float scale,
-                  hipStream_t stream);
+                  hipStream_t stream, const float *row_w = nullptr);
 // the caller's tensors of tc_chain_step_typed (dtype: TC_DTYPE_*): the layout copies with the (B, C, T) side of that type
 // (TC_DTYPE_F32: launch_layout), the widening copy of 16-bit 2-D rows into a contiguous float32 matrix and the rounding
-// copy of n contiguous floats into 16 bits (these two: TC_DTYPE_BF16 / TC_DTYPE_F16 only)
+// copy of n contiguous floats into 16 bits (these two: TC_DTYPE_BF16 / TC_DTYPE_F16 only).  row_w: as launch_layout's
+// for launch_from2d; for launch_round the factor of row i / cols of the n floats, rounded once from row_w[row] * in[i]
 int launch_to2d(int dtype, const void *in_bct, float *out, int B, int Cn, int T, int64_t stride2d, hipStream_t stream);
 int launch_from2d(int dtype, const float *in, int64_t stride2d, void *out_bct, int B, int Cn, int T, float scale,
-                  hipStream_t stream);
+                  hipStream_t stream, const float *row_w = nullptr);
 int launch_widen_rows(int dtype, const void *in, int64_t in_stride, float *out, int64_t rows, int cols, hipStream_t stream);
-int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t stream);
+int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t stream, const float *row_w = nullptr,
+                 int cols = 0);
+// a[r][c] *= row_w[r] in place on a contiguous float32 (rows, cols) matrix (the 2-D float32 MMI gradient of
+// tc_chain_step_weighted, which the denominator and the numerator write straight into the caller's tensor)
+int launch_scale_rows(float *a, int64_t rows, int cols, const float *row_w, hipStream_t stream);
 
 extern thread_local int g_last_hip_error;
 

@@ -27,11 +27,15 @@ struct LayoutIo {
 
 // TO2D: in (B, C, T) contiguous -> out[(t*B + b) * out_stride + c];  !TO2D: the inverse, times `scale`
 // (E = float: the float32 kernels; otherwise TO2D widens each element it reads, !TO2D rounds each one it writes)
-template <bool TO2D, bool VEC, typename E = float>
+// W (!TO2D; tc_chain_step_weighted): times a per-row factor as well, out = (scale * row_w[t*B + b]) * in: the factor is
+// loaded once per 2-D row a thread reads and folded in as the tile is filled, so the tile holds final float32 values
+template <bool TO2D, bool VEC, typename E = float, bool W = false>
 __global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const typename LayoutIo<TO2D, E>::in_t *__restrict__ in,
                                                                 typename LayoutIo<TO2D, E>::out_t *__restrict__ out,
-                                                                int B, int Cn, int T, int64_t stride2d, float scale) {
+                                                                int B, int Cn, int T, int64_t stride2d, float scale,
+                                                                const float *__restrict__ row_w) {
   constexpr bool kF32 = std::is_same<E, float>::value;
+  static_assert(!(W && TO2D), "row factors are for the way back");
   extern __shared__ float tile[];  // kTileC x (frames of the tile | 1): sized by the launch, several blocks per CU
   const int c0 = blockIdx.x * kTileC, b = blockIdx.y, t0 = blockIdx.z * kTileTMax;
   const int tc = min(kTileTMax, T - t0), nc = min(kTileC, Cn - c0);
@@ -74,6 +78,10 @@ __global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const typename L
           if (cq + 1 < nc) v.y = src[1];
           if (cq + 2 < nc) v.z = src[2];
         }
+        if constexpr (W) {
+          const float f = scale * row_w[(int64_t)(t0 + t) * B + b];
+          v = make_float4(f * v.x, f * v.y, f * v.z, f * v.w);
+        }
         tile[(cq + 0) * pitch + t] = v.x;
         tile[(cq + 1) * pitch + t] = v.y;
         tile[(cq + 2) * pitch + t] = v.z;
@@ -82,9 +90,13 @@ __global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const typename L
     } else {
       const int cx = tid & (kTileC - 1);
       for (int t = tid / kTileC; t < tc; t += kLayoutThreads / kTileC)
-        if (cx < nc) tile[cx * pitch + t] = in[((int64_t)(t0 + t) * B + b) * stride2d + c0 + cx];
+        if (cx < nc) {
+          const float v = in[((int64_t)(t0 + t) * B + b) * stride2d + c0 + cx];
+          tile[cx * pitch + t] = W ? (scale * row_w[(int64_t)(t0 + t) * B + b]) * v : v;
+        }
     }
     __syncthreads();
+    const float s = W ? 1.0f : scale;  // (W: the tile holds the scaled values already)
     if constexpr (!kF32) {
       // Write side of a 16-bit tensor: scale in float32, round once; 8-byte stores (4 frames) when every run starts
       // 8-byte aligned, 4-byte ones (2 frames) when it starts 4-byte aligned
@@ -93,8 +105,8 @@ __global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const typename L
         for (int idx = tid; idx < nc * quad; idx += kLayoutThreads) {
           const int c = idx / quad, t = 4 * (idx - c * quad);
           const float *src = tile + c * pitch + t;
-          const uint32_t lo = Elem<E>::round(scale * src[0]) | ((uint32_t)Elem<E>::round(scale * src[1]) << 16);
-          const uint32_t hi = Elem<E>::round(scale * src[2]) | ((uint32_t)Elem<E>::round(scale * src[3]) << 16);
+          const uint32_t lo = Elem<E>::round(s * src[0]) | ((uint32_t)Elem<E>::round(s * src[1]) << 16);
+          const uint32_t hi = Elem<E>::round(s * src[2]) | ((uint32_t)Elem<E>::round(s * src[3]) << 16);
           *reinterpret_cast<uint2 *>(out + ((int64_t)b * Cn + c0 + c) * T + t0 + t) = make_uint2(lo, hi);
         }
       } else if (VEC && (T & 1) == 0) {
@@ -103,12 +115,12 @@ __global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const typename L
           const int c = idx / half, t = 2 * (idx - c * half);
           const float *src = tile + c * pitch + t;
           *reinterpret_cast<uint32_t *>(out + ((int64_t)b * Cn + c0 + c) * T + t0 + t) =
-              Elem<E>::round(scale * src[0]) | ((uint32_t)Elem<E>::round(scale * src[1]) << 16);
+              Elem<E>::round(s * src[0]) | ((uint32_t)Elem<E>::round(s * src[1]) << 16);
         }
       } else {
         for (int idx = tid; idx < nc * tc; idx += kLayoutThreads) {
           const int c = idx / tc, t = idx - c * tc;
-          out[((int64_t)b * Cn + c0 + c) * T + t0 + t] = Elem<E>::round(scale * tile[c * pitch + t]);
+          out[((int64_t)b * Cn + c0 + c) * T + t0 + t] = Elem<E>::round(s * tile[c * pitch + t]);
         }
       }
     } else {
@@ -118,12 +130,12 @@ __global__ __launch_bounds__(kLayoutThreads) void layout_kernel(const typename L
         for (int idx = tid; idx < nc * half; idx += kLayoutThreads) {
           const int c = idx / half, t = 2 * (idx - c * half);
           *reinterpret_cast<float2 *>(out + ((int64_t)b * Cn + c0 + c) * T + t0 + t) =
-              make_float2(scale * tile[c * pitch + t], scale * tile[c * pitch + t + 1]);
+              make_float2(s * tile[c * pitch + t], s * tile[c * pitch + t + 1]);
         }
       } else {
         for (int idx = tid; idx < nc * tc; idx += kLayoutThreads) {
           const int c = idx / tc, t = idx - c * tc;
-          out[((int64_t)b * Cn + c0 + c) * T + t0 + t] = scale * tile[c * pitch + t];
+          out[((int64_t)b * Cn + c0 + c) * T + t0 + t] = s * tile[c * pitch + t];
         }
       }
     }
@@ -157,20 +169,55 @@ __global__ __launch_bounds__(kCastThreads) void widen_rows_kernel(const uint16_t
   }
 }
 
+// w * v as a float32 value: the empty asm keeps the backend from fusing the multiply into the float16 conversion
+// (v_fma_mixlo_f16 rounds the exact product straight to 16 bits, and its + 0 addend turns a product of -0 into +0)
+__device__ __forceinline__ float weigh(float w, float v) {
+  float p = w * v;
+  asm volatile("" : "+v"(p));
+  return p;
+}
+
 // float32 -> 16-bit, n contiguous elements, rounded once.  VEC: two 16-byte loads and one 16-byte store per 8 elements
-// (n a multiple of 8, both bases 16-byte aligned).
-template <typename E, bool VEC>
+// (n a multiple of 8, both bases 16-byte aligned; with W, cols a multiple of 8 too).  W (tc_chain_step_weighted): element i
+// is row i / cols of a (rows, cols) matrix and is rounded from row_w[row] * in[i].
+template <typename E, bool VEC, bool W = false>
 __global__ __launch_bounds__(kCastThreads) void round_kernel(const float *__restrict__ in, uint16_t *__restrict__ out,
-                                                             int64_t n) {
+                                                             int64_t n, const float *__restrict__ row_w, int cols) {
   const int64_t step = (int64_t)gridDim.x * kCastThreads;
   if (VEC) {
     for (int64_t i = (int64_t)blockIdx.x * kCastThreads + threadIdx.x; i < n / 8; i += step) {
-      const float4 a = reinterpret_cast<const float4 *>(in)[2 * i], b = reinterpret_cast<const float4 *>(in)[2 * i + 1];
+      float4 a = reinterpret_cast<const float4 *>(in)[2 * i], b = reinterpret_cast<const float4 *>(in)[2 * i + 1];
+      if constexpr (W) {
+        const float f = row_w[8 * i / cols];  // (the 8 elements lie in one row)
+        a = make_float4(weigh(f, a.x), weigh(f, a.y), weigh(f, a.z), weigh(f, a.w));
+        b = make_float4(weigh(f, b.x), weigh(f, b.y), weigh(f, b.z), weigh(f, b.w));
+      }
       auto pack = [](float lo, float hi) { return (uint32_t)Elem<E>::round(lo) | ((uint32_t)Elem<E>::round(hi) << 16); };
       reinterpret_cast<uint4 *>(out)[i] = make_uint4(pack(a.x, a.y), pack(a.z, a.w), pack(b.x, b.y), pack(b.z, b.w));
     }
   } else {
-    for (int64_t i = (int64_t)blockIdx.x * kCastThreads + threadIdx.x; i < n; i += step) out[i] = Elem<E>::round(in[i]);
+    for (int64_t i = (int64_t)blockIdx.x * kCastThreads + threadIdx.x; i < n; i += step)
+      out[i] = Elem<E>::round(W ? weigh(row_w[i / cols], in[i]) : in[i]);
+  }
+}
+
+// a[r][c] *= row_w[r] in place, contiguous float32 (rows, cols), one wave per row at a time (the factor is loaded once per
+// row and wave).  VEC: 16-byte loads and stores (cols a multiple of 4, base 16-byte aligned).
+template <bool VEC>
+__global__ __launch_bounds__(kCastThreads) void scale_rows_kernel(float *__restrict__ a, int64_t rows, int cols,
+                                                                  const float *__restrict__ row_w) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * (kCastThreads / 64) + wave; r < rows; r += (int64_t)gridDim.x * (kCastThreads / 64)) {
+    const float f = row_w[r];
+    float *row = a + r * cols;
+    if (VEC) {
+      for (int c = lane * 4; c < cols; c += 64 * 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(row + c);
+        *reinterpret_cast<float4 *>(row + c) = make_float4(f * v.x, f * v.y, f * v.z, f * v.w);
+      }
+    } else {
+      for (int c = lane; c < cols; c += 64) row[c] = f * row[c];
+    }
   }
 }
 
@@ -222,7 +269,7 @@ namespace {
 
 template <typename E>
 int launch_layout_16(bool to2d, const void *in, void *out, int B, int Cn, int T, int64_t stride2d, float scale,
-                     hipStream_t stream) {
+                     hipStream_t stream, const float *row_w = nullptr) {
   count_launch(kCntLayout);
   const dim3 grid((Cn + kTileC - 1) / kTileC, B, (T + kTileTMax - 1) / kTileTMax);
   const size_t lds = sizeof(float) * kTileC * ((size_t)(T < kTileTMax ? T : kTileTMax) | 1);
@@ -230,16 +277,27 @@ int launch_layout_16(bool to2d, const void *in, void *out, int B, int Cn, int T,
     const uint16_t *src = static_cast<const uint16_t *>(in);
     float *dst = static_cast<float *>(out);
     if ((T & 1) == 0 && ((uintptr_t)in & 3) == 0)
-      hipLaunchKernelGGL((layout_kernel<true, true, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+      hipLaunchKernelGGL((layout_kernel<true, true, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale,
+                         nullptr);
     else
-      hipLaunchKernelGGL((layout_kernel<true, false, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+      hipLaunchKernelGGL((layout_kernel<true, false, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale,
+                         nullptr);
   } else {
     const float *src = static_cast<const float *>(in);
     uint16_t *dst = static_cast<uint16_t *>(out);
-    if (stride2d % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 7) == 0)
-      hipLaunchKernelGGL((layout_kernel<false, true, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+    const bool vec = stride2d % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 7) == 0;
+    if (row_w && vec)
+      hipLaunchKernelGGL((layout_kernel<false, true, E, true>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d,
+                         scale, row_w);
+    else if (row_w)
+      hipLaunchKernelGGL((layout_kernel<false, false, E, true>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d,
+                         scale, row_w);
+    else if (vec)
+      hipLaunchKernelGGL((layout_kernel<false, true, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale,
+                         nullptr);
     else
-      hipLaunchKernelGGL((layout_kernel<false, false, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale);
+      hipLaunchKernelGGL((layout_kernel<false, false, E>), grid, dim3(kLayoutThreads), lds, stream, src, dst, B, Cn, T, stride2d, scale,
+                         nullptr);
   }
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
@@ -263,12 +321,17 @@ int launch_widen_rows_e(const void *in, int64_t in_stride, float *out, int64_t r
 }
 
 template <typename E>
-int launch_round_e(const float *in, void *out, int64_t n, hipStream_t stream) {
+int launch_round_e(const float *in, void *out, int64_t n, hipStream_t stream, const float *row_w, int cols) {
   uint16_t *dst = static_cast<uint16_t *>(out);
-  if (n % 8 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0)
-    hipLaunchKernelGGL((round_kernel<E, true>), dim3(cast_blocks(n / 8)), dim3(kCastThreads), 0, stream, in, dst, n);
+  const bool vec = n % 8 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0;
+  if (row_w && vec && cols % 8 == 0)
+    hipLaunchKernelGGL((round_kernel<E, true, true>), dim3(cast_blocks(n / 8)), dim3(kCastThreads), 0, stream, in, dst, n, row_w, cols);
+  else if (row_w)
+    hipLaunchKernelGGL((round_kernel<E, false, true>), dim3(cast_blocks(n)), dim3(kCastThreads), 0, stream, in, dst, n, row_w, cols);
+  else if (vec)
+    hipLaunchKernelGGL((round_kernel<E, true>), dim3(cast_blocks(n / 8)), dim3(kCastThreads), 0, stream, in, dst, n, nullptr, 0);
   else
-    hipLaunchKernelGGL((round_kernel<E, false>), dim3(cast_blocks(n)), dim3(kCastThreads), 0, stream, in, dst, n);
+    hipLaunchKernelGGL((round_kernel<E, false>), dim3(cast_blocks(n)), dim3(kCastThreads), 0, stream, in, dst, n, nullptr, 0);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }
@@ -285,11 +348,11 @@ int launch_to2d(int dtype, const void *in_bct, float *out, int B, int Cn, int T,
 }
 
 int launch_from2d(int dtype, const float *in, int64_t stride2d, void *out_bct, int B, int Cn, int T, float scale,
-                  hipStream_t stream) {
+                  hipStream_t stream, const float *row_w) {
   switch (dtype) {
-    case TC_DTYPE_F32: return launch_layout(false, in, static_cast<float *>(out_bct), B, Cn, T, stride2d, scale, stream);
-    case TC_DTYPE_BF16: return launch_layout_16<__hip_bfloat16>(false, in, out_bct, B, Cn, T, stride2d, scale, stream);
-    case TC_DTYPE_F16: return launch_layout_16<__half>(false, in, out_bct, B, Cn, T, stride2d, scale, stream);
+    case TC_DTYPE_F32: return launch_layout(false, in, static_cast<float *>(out_bct), B, Cn, T, stride2d, scale, stream, row_w);
+    case TC_DTYPE_BF16: return launch_layout_16<__hip_bfloat16>(false, in, out_bct, B, Cn, T, stride2d, scale, stream, row_w);
+    case TC_DTYPE_F16: return launch_layout_16<__half>(false, in, out_bct, B, Cn, T, stride2d, scale, stream, row_w);
   }
   return TC_ERR_INVALID_ARGUMENT;
 }
@@ -302,27 +365,49 @@ int launch_widen_rows(int dtype, const void *in, int64_t in_stride, float *out, 
   return TC_ERR_INVALID_ARGUMENT;
 }
 
-int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t stream) {
+int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t stream, const float *row_w, int cols) {
+  if (row_w && cols <= 0) return TC_ERR_INVALID_ARGUMENT;
   switch (dtype) {
-    case TC_DTYPE_BF16: return launch_round_e<__hip_bfloat16>(in, out, n, stream);
-    case TC_DTYPE_F16: return launch_round_e<__half>(in, out, n, stream);
+    case TC_DTYPE_BF16: return launch_round_e<__hip_bfloat16>(in, out, n, stream, row_w, cols);
+    case TC_DTYPE_F16: return launch_round_e<__half>(in, out, n, stream, row_w, cols);
   }
   return TC_ERR_INVALID_ARGUMENT;
 }
 
+int launch_scale_rows(float *a, int64_t rows, int cols, const float *row_w, hipStream_t stream) {
+  if (!a || !row_w || rows <= 0 || cols <= 0) return TC_ERR_INVALID_ARGUMENT;
+  const int blocks = cast_blocks(rows * 64);  // (a wave per row)
+  if (cols % 4 == 0 && ((uintptr_t)a & 15) == 0)
+    hipLaunchKernelGGL((scale_rows_kernel<true>), dim3(blocks), dim3(kCastThreads), 0, stream, a, rows, cols, row_w);
+  else
+    hipLaunchKernelGGL((scale_rows_kernel<false>), dim3(blocks), dim3(kCastThreads), 0, stream, a, rows, cols, row_w);
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
+
 int launch_layout(bool to2d, const float *in, float *out, int B, int Cn, int T, int64_t stride2d, float scale,
-                  hipStream_t stream) {
+                  hipStream_t stream, const float *row_w) {
+  if (to2d && row_w) return TC_ERR_INVALID_ARGUMENT;
   count_launch(kCntLayout);
   const dim3 grid((Cn + kTileC - 1) / kTileC, B, (T + kTileTMax - 1) / kTileTMax);
   const size_t lds = sizeof(float) * kTileC * ((size_t)(T < kTileTMax ? T : kTileTMax) | 1);
   // 16-byte path of the 2-D side: rows and base 16-byte aligned, whole float4s of channels in every tile
   const bool vec = stride2d % 4 == 0 && ((uintptr_t)(to2d ? out : in) & 15) == 0 && ((uintptr_t)(to2d ? in : out) & 7) == 0;
   if (to2d)
-    hipLaunchKernelGGL((layout_kernel<true, false>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T, stride2d, scale);
+    hipLaunchKernelGGL((layout_kernel<true, false>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T, stride2d, scale,
+                       nullptr);
+  else if (row_w && vec)
+    hipLaunchKernelGGL((layout_kernel<false, true, float, true>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T,
+                       stride2d, scale, row_w);
+  else if (row_w)
+    hipLaunchKernelGGL((layout_kernel<false, false, float, true>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T,
+                       stride2d, scale, row_w);
   else if (vec)
-    hipLaunchKernelGGL((layout_kernel<false, true>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T, stride2d, scale);
+    hipLaunchKernelGGL((layout_kernel<false, true>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T, stride2d, scale,
+                       nullptr);
   else
-    hipLaunchKernelGGL((layout_kernel<false, false>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T, stride2d, scale);
+    hipLaunchKernelGGL((layout_kernel<false, false>), grid, dim3(kLayoutThreads), lds, stream, in, out, B, Cn, T, stride2d, scale,
+                       nullptr);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }

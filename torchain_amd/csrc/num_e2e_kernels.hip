@@ -92,7 +92,10 @@ __device__ __forceinline__ double write_posterior(const NumParams &p, int q, int
   const int64_t row = (int64_t)t * p.S + q;
   const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + t;  // (sequence, pdf, frame) of a (B, C, T) tensor
   if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
-  if (p.xent) p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_scale * v;
+  if (p.xent) {  // (times the row's deriv_weight when one is given; the objective term below is not)
+    const float xv = p.xent_scale * v;
+    p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_row_w ? p.xent_row_w[row] * xv : xv;
+  }
   if (p.seq_xent)
     return (double)(p.xent_scale * v) * (double)(std::is_same<El, float>::value
                                                      ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]

@@ -186,7 +186,10 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
     // -xent_regularize * xent_deriv, formed here instead of in two more passes over the matrices)
     if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
     const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + p.t.uniq_t[ub + u];  // (sequence, pdf, frame) of a (B, C, T) tensor
-    if (p.xent) p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_scale * v;
+    if (p.xent) {  // (times the row's deriv_weight when one is given; the objective term below is not)
+      const float xv = p.xent_scale * v;
+      p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_row_w ? p.xent_row_w[row] * xv : xv;
+    }
     // (the cross-entropy output: the caller's (B, C, T) tensor of element type E, or a float32 matrix)
     if (p.seq_xent)
       xo += (double)(p.xent_scale * v) * (double)(std::is_same<E, float>::value
@@ -210,7 +213,10 @@ __global__ __launch_bounds__(128) void num_scatter_kernel(const NumParams p) {
     const int pdf = p.t.uniq_pdf[ub + u];
     if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
     const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + p.t.uniq_t[ub + u];  // (sequence, pdf, frame) of a (B, C, T) tensor
-    if (p.xent) p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_scale * v;
+    if (p.xent) {  // (times the row's deriv_weight when one is given; the objective term below is not)
+      const float xv = p.xent_scale * v;
+      p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_row_w ? p.xent_row_w[row] * xv : xv;
+    }
     // (the cross-entropy output: the caller's (B, C, T) tensor of element type E, or a float32 matrix)
     if (p.seq_xent)
       xo += (double)(p.xent_scale * v) * (double)(std::is_same<E, float>::value

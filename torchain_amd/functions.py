@@ -18,8 +18,14 @@ Same names, argument meaning, defaults and quirks as the reference:
   library widens them as it reads them and rounds the gradients once as it writes them, so ``results`` are those of
   ``input.float()``, the loss is that loss in the input's dtype and the gradients are the float32 ones ``.to(dtype)``.
   ``input`` and ``xent_input`` of different dtypes are up-cast to float32 first (correct, not the fast path).
+* ``deriv_weights`` (Kaldi's per-frame ``<DW>`` / ``<DW2>`` weights, ``io.Example.deriv_weights``): a ``(T*B,)`` vector in
+  the frame-major row order ``t*B + b``.  Each gradient element becomes ``w[row] * g``, one float32 multiply of the
+  unweighted value (rounded once for 16-bit inputs), as Kaldi's ``MulRowsVec`` after ``ComputeChainObjfAndDeriv``;
+  ``results``, the loss and ``xent_objf`` are unchanged.  ``None`` (the default) keeps the reference's behaviour, which
+  drops the weights.  The one call applies them in the passes it makes anyway (``tc_chain_step_weighted``).
 """
 import ctypes as C
+import inspect
 
 import torch
 from torch.autograd import Function
@@ -202,13 +208,37 @@ def _device_loss(results, like):
     return (-(r[0] / r[2])).reshape(1).to(like.dtype)
 
 
+def _deriv_weights(w, rows):
+    """``chain_loss``'s ``deriv_weights`` checked: None, or a 1-D real tensor of ``rows`` (S*T) entries on the CPU or a GPU.
+    Raises ``ValueError`` otherwise, and for a CPU tensor under stream capture (its copy could not be captured)."""
+    if w is None:
+        return None
+    if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.numel() != rows or w.is_complex() or w.dtype == torch.bool:
+        raise ValueError("deriv_weights must be a 1-D real tensor of %d entries (one per frame-major row t*B + b), got %s"
+                         % (rows, tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__))
+    if not w.is_cuda and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise ValueError("deriv_weights must be a CUDA tensor under stream capture (a CPU tensor's copy is not captured)")
+    return w
+
+
+def _weights_on(w, device):
+    """Checked ``deriv_weights`` as the library reads them: float32, contiguous, on ``device`` (a no-op when they are)."""
+    return None if w is None else w.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _rows_of(x):
+    """Frame-major rows of an nnet output: T*B for (B, C, T), the number of rows for 2-D."""
+    return x.shape[0] * x.shape[2] if x.dim() == 3 else x.shape[0]
+
+
 class _ChainLoss(Function):
     """Lattice-free MMI loss; see the reference docstring ``torchain/functions.py:23-60`` for the
-    meaning of every argument (identical here)."""
+    meaning of every argument (identical here).  ``deriv_weights``: per-row factors of both gradients, applied in
+    backward (frame-major rows, as the 2-D tensors here)."""
 
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False):
+                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None):
         assert input.is_cuda, "Only CUDA implementation is available"
         # The kernels write the two matrices as backward() returns them (-deriv, -xent_regularize * xent_deriv):
         # the reference scales one and negates both in three more passes over (T*B, C) tensors.
@@ -231,13 +261,19 @@ class _ChainLoss(Function):
                                              xent_grad, l2_regularize, leaky_hmm_coefficient, xent_regularize,
                                              as_gradients=True, holder=results)
             ctx.xent_grad = xent_grad
+        ctx.row_w = _weights_on(deriv_weights, input.device)
         if results._defer_host_copy:
             return input.new_zeros(1)  # (filled in behind the all-reduce: parallel.chain_loss_data_parallel)
         return _device_loss(results, input)
 
     @staticmethod
     def backward(ctx, grad_output):
-        return (ctx.mmi_grad, getattr(ctx, "xent_grad", None), None, None, None, None, None, None, None)
+        g, xg = ctx.mmi_grad, getattr(ctx, "xent_grad", None)
+        if ctx.row_w is not None:  # ([K] MulRowsVec on both derivatives)
+            w = ctx.row_w.unsqueeze(1)
+            g = g * w.to(g.dtype)
+            xg = xg * w.to(xg.dtype) if xg is not None else None
+        return (g, xg, None, None, None, None, None, None, None, None)
 
 
 def _stream(device):
@@ -272,7 +308,7 @@ class _ChainLoss3d(Function):
 
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False):
+                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None):
         assert input.is_cuda, "Only CUDA implementation is available"
         x2d = to2d_hip(input.detach())
         mmi_grad = torch.empty_like(x2d)
@@ -294,6 +330,7 @@ class _ChainLoss3d(Function):
             ctx.xent_grad = xent_grad
             ctx.xent_shape = tuple(xent_input.shape)
             ctx.xent_scale = float(xent_regularize)
+        ctx.row_w = _weights_on(deriv_weights, input.device)
         if results._defer_host_copy:
             return input.new_zeros(1)
         return _device_loss(results, input)
@@ -302,7 +339,12 @@ class _ChainLoss3d(Function):
     def backward(ctx, grad_output):
         g = from2d_hip(ctx.mmi_grad, ctx.in_shape, -1.0)
         xg = from2d_hip(ctx.xent_grad, ctx.xent_shape, -ctx.xent_scale) if hasattr(ctx, "xent_grad") else None
-        return (g, xg, None, None, None, None, None, None, None)
+        if ctx.row_w is not None:  # ([K] MulRowsVec; row t*B + b is element (b, :, t) here)
+            B, _, T = ctx.in_shape
+            w = ctx.row_w.view(T, B).t().unsqueeze(1)
+            g = g * w
+            xg = xg * w if xg is not None else None
+        return (g, xg, None, None, None, None, None, None, None, None)
 
 
 class _ChainStep(Function):
@@ -313,9 +355,10 @@ class _ChainStep(Function):
 
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False):
+                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None):
         out, grad, xgrad = _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
-                                     leaky_hmm_coefficient, xent_regularize, kaldi_way, want_grad=True)
+                                     leaky_hmm_coefficient, xent_regularize, kaldi_way, want_grad=True,
+                                     deriv_weights=deriv_weights)
         ctx.grads = (grad, xgrad)
         if results._defer_host_copy:
             return input.new_zeros(1)
@@ -323,13 +366,14 @@ class _ChainStep(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return (ctx.grads[0], ctx.grads[1], None, None, None, None, None, None, None)
+        return (ctx.grads[0], ctx.grads[1], None, None, None, None, None, None, None, None)
 
 
 def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-              xent_regularize, kaldi_way, want_grad):
-    """One ``tc_chain_step``.  ``want_grad=False`` is the evaluation step (``grad == NULL``): forward recursions only,
-    no gradient tensors -- [K] ``ComputeChainObjfAndDeriv`` with ``nnet_output_deriv == NULL``."""
+              xent_regularize, kaldi_way, want_grad, deriv_weights=None):
+    """One ``tc_chain_step_weighted``.  ``want_grad=False`` is the evaluation step (``grad == NULL``): forward recursions
+    only, no gradient tensors -- [K] ``ComputeChainObjfAndDeriv`` with ``nnet_output_deriv == NULL``; ``deriv_weights``
+    (checked by ``_deriv_weights``) are then not passed on."""
     device = input.device
     three_d = input.dim() == 3
     use_xent = xent_input is not None and xent_regularize != 0.0
@@ -368,21 +412,22 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         capturing = torch.cuda.is_current_stream_capturing()
         # (inside a graph capture the workspace comes from the graph's own pool and lives as long as the graph does)
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device) if capturing else _workspace(device, cur.cuda_stream, nbytes)
+        # (a CPU vector is copied here; a float32 CUDA vector is read where it lies, so a replay reads its current values)
+        w = _weights_on(deriv_weights, device) if want_grad else None
         out = torch.empty(6, dtype=torch.float32, device=device)  # objf, l2_term, weight | loss | xent objective (f64)
         args = (den_ptr, sup_ptr, _ptr(x), _ptr(xe), int(three_d), 0 if three_d else x.stride(0), float(l2_regularize),
                 float(leaky_hmm_coefficient), float(xent_regularize), int(bool(kaldi_way)), _ptr(grad), _ptr(xgrad),
                 C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 12),
                 C.c_void_p(out.data_ptr() + 16) if use_xent else None)
         tail = (_ptr(ws), ws.numel(), device.index, C.c_void_p(cur.cuda_stream))
-        if dtype == TC_DTYPE_F32:
-            check(lib.tc_chain_step(*args, *tail), "tc_chain_step")
-        else:  # bfloat16 / float16: widened on the way in, gradients rounded once on the way out
-            check(lib.tc_chain_step_typed(*args, dtype, *tail), "tc_chain_step_typed")
+        # (float32 and NULL weights: tc_chain_step itself; bfloat16 / float16 are widened on the way in and their
+        # gradients rounded once on the way out)
+        check(lib.tc_chain_step_weighted(*args, _ptr(w), dtype, *tail), "tc_chain_step_weighted")
         results._dev = out[:3]
         results._stale = True
         results._ready = None
         if capturing:
-            results._graph_keeps = ws  # replays write through it; read the values after a replay with ``invalidate()``
+            results._graph_keeps = (ws, w)  # replays write through it; read the values after a replay with ``invalidate()``
         else:
             results._ready = torch.cuda.Event()
             results._ready.record(cur)
@@ -455,17 +500,24 @@ def _fusable(x):
 
 def chain_loss(input, den_graph, supervision,
                l2_regularize=0.0, leaky_hmm_coefficient=1e-5,
-               xent_regularize=0.0, xent_input=None, kaldi_way=False):
+               xent_regularize=0.0, xent_input=None, kaldi_way=False, *, deriv_weights=None):
     return _chain_loss_into(ChainResults(), input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                            xent_regularize, xent_input, kaldi_way)
+                            xent_regularize, xent_input, kaldi_way, deriv_weights)
+
+
+# What introspection reports stays the reference's signature (torchain/functions.py:128-130), the drop-in surface callers
+# compare against; ``deriv_weights`` is this library's keyword-only extension (``chain_loss.__kwdefaults__``).
+chain_loss.__signature__ = inspect.signature(chain_loss).replace(
+    parameters=[p for p in inspect.signature(chain_loss).parameters.values() if p.name != "deriv_weights"])
 
 
 def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                     xent_input, kaldi_way):
+                     xent_input, kaldi_way, deriv_weights=None):
     """``chain_loss`` with the ``ChainResults`` given (parallel.chain_loss_data_parallel passes one that defers the
     host copy of the three floats until after its all-reduce)."""
+    deriv_weights = _deriv_weights(deriv_weights, _rows_of(input))
     input, xent_input = _same_dtype(input, xent_input)
-    if not _needs_grad(input, xent_input):
+    if not _needs_grad(input, xent_input):  # (deriv_weights: checked above, and not used without a gradient)
         # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the
         # forward recursions only.  The reference has no such check (functions.py:74,82) and pays for a training step.
         x, xe = _as_step_input(input), (_as_step_input(xent_input) if xent_input is not None else None)
@@ -477,16 +529,16 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
     if (_one_call(input) and _one_call(xent_input) and (xent_input is None or xent_input.dim() == input.dim())
             and (xent_input is None or xent_input.dim() == 3 or xent_input.stride(0) == input.stride(0))):
         loss = _ChainStep.apply(input, xent_input, results, den_graph, supervision,
-                                l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way)
+                                l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights)
         return loss, results
     if _fusable(input) and (xent_input is None or _fusable(xent_input)):
         loss = _ChainLoss3d.apply(input, xent_input, results, den_graph, supervision,
-                                  l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way)
+                                  l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights)
         return loss, results
     input = to2d(input)
     if xent_input is not None:
         xent_input = to2d(xent_input)
 
     loss = _ChainLoss.apply(input, xent_input, results, den_graph, supervision,
-                            l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way)
+                            l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights)
     return loss, results

@@ -34,6 +34,13 @@ def shard_rows(x2d, num_sequences, lo, hi):
     return x2d.reshape(T, num_sequences, cols)[:, lo:hi, :].reshape(T * (hi - lo), cols)
 
 
+def shard_deriv_weights(w, num_sequences, lo, hi):
+    """Entries of a frame-major ``(T*S,)`` weight vector (entry = t*S + s, as ``io.Example.deriv_weights``) that belong to
+    sequences [lo, hi), as a ``(T*(hi-lo),)`` vector in the same frame-major order: the 1-D ``shard_rows``."""
+    T = w.shape[0] // num_sequences
+    return w.reshape(T, num_sequences)[:, lo:hi].reshape(T * (hi - lo))
+
+
 def shard_supervision_fst(sup, lo, hi):
     """Per-rank supervision from a ``torchain_amd.synth.SupFst``-like merged acceptor: keeps the
     sub-acceptor of sequences [lo, hi).  Host-side numpy; mirrors what a per-rank egs reader would
@@ -146,19 +153,21 @@ def _finish_host_copy(results):
 
 
 def chain_loss_data_parallel(input, den_graph, supervision, l2_regularize=0.0, leaky_hmm_coefficient=1e-5,
-                             xent_regularize=0.0, xent_input=None, kaldi_way=False, group=None, even_if_alone=False):
+                             xent_regularize=0.0, xent_input=None, kaldi_way=False, group=None, even_if_alone=False,
+                             *, deriv_weights=None):
     """``chain_loss`` on this rank's shard followed by the one all-reduce.  Returns
     ``(loss, results)`` where ``results`` holds the GLOBAL ``[objf, l2_term, weight]`` (and ``xent_objf``) and
     ``loss`` is a tensor whose value is the global ``-objf/weight`` and whose backward is this rank's local
     gradient (``-deriv``, exactly as the single-GPU wrapper; DDP then averages parameter grads).  The rank's own
     results never visit the host: the kernels' device-side floats go into the collective and one copy brings the
-    reduced values back."""
+    reduced values back.  ``deriv_weights``: this rank's own weights (``shard_deriv_weights``), as ``chain_loss`` takes them;
+    they scale the local gradient only."""
     if input.is_cuda and hasattr(den_graph, "prepare"):
         sync_den_graph_variant(den_graph, input.device, group)
     results = ChainResults()
     results._defer_host_copy = bool(input.is_cuda)
     loss, results = _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                                     xent_regularize, xent_input, kaldi_way)
+                                     xent_regularize, xent_input, kaldi_way, deriv_weights)
     all_reduce_results(results, group=group, device=input.device if input.is_cuda else None, even_if_alone=even_if_alone)
     with torch.no_grad():
         loss.copy_(results.loss)
