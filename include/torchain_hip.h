@@ -379,6 +379,38 @@ int tc_chain_step_weighted(tc_den_graph *graph, tc_supervision *supervision, con
                            float *loss_dev1, double *xent_objf_dev, const float *deriv_weights, int dtype, void *workspace,
                            int64_t workspace_bytes, int device, void *stream);
 
+/* tc_chain_step_weighted with an out-of-range penalty on the network output (after [K] PenalizeOutOfRange, restated: the
+ * definition below is this library's and is complete).  The denominator kernels take exp(y) at clamp(y, -L, L), L = 30
+ * (kOutputLimit), so outside that range an output has lost the objective's restoring force; the penalty gives one back.
+ * out_of_range_regularize = c: finite and >= 0, else TC_ERR_INVALID_ARGUMENT; c == 0 is tc_chain_step_weighted itself,
+ * which is this entry's c == 0 case (the same kernels and the same launches).
+ * With y the float32 value of the CHAIN output `input` (the exact widened value of a 16-bit element; never xent_input, also
+ * when kaldi_way == 0 runs the objective on xent_input) and g the float32 MMI gradient element tc_chain_step_typed returns:
+ *     p  = y > L ? y - L : (y < -L ? y + L : 0)     one float32 subtract; p = 0 where y is NaN or +-inf
+ *     t  = fl32(fl32(2 * c) * p)                     one float32 multiply
+ *     g' = fl32(g + t)                               one float32 add, not fused with the multiply
+ * which is gradient descent on c * sum (y - clamp(y, -L, L))^2.  Every row of every sequence is penalised (Kaldi takes a
+ * random subset of rows and scales up; this is deterministic), and t is not multiplied by the supervision's weight.
+ *   order     : deriv_weights apply after, w[row] * g'; a 16-bit gradient is rounded once, from that product.  The penalty
+ *               lies behind the soft-failure reset: a failed step returns w[row] * ((l2 * weight * y, or 0) + t).
+ *   p == 0    : the element has the bits of the unpenalised call, a zero's sign included.
+ *   untouched : results_dev3, loss_dev1, xent_objf_dev and the xent gradient, bit for bit, for both kaldi_way settings: the
+ *               penalty is not part of the objective.
+ *   where     : three_d != 0, float32 and 16-bit: the layout copy back, which reads `input` at the index it writes.
+ *               three_d == 0, 16-bit: the rounding pass of the MMI gradient, which reads the widened float32 input.
+ *               three_d == 0, float32: one in-place pass over the MMI gradient that reads `input` with row_stride; it is
+ *               the pass that applies deriv_weights when those are given too.  The denominator and the numerator
+ *               kernels are not involved.
+ *   grad == NULL (an evaluation step): out_of_range_regularize is checked and not used.
+ * Workspace: tc_chain_step_typed_workspace_bytes (unchanged, every layout and dtype).  No host synchronisation; safe under
+ * stream capture. */
+int tc_chain_step_penalized(tc_den_graph *graph, tc_supervision *supervision, const void *input, const void *xent_input,
+                            int three_d, int64_t row_stride, float l2_regularize, float leaky_hmm_coefficient,
+                            float xent_regularize, int kaldi_way, void *grad, void *xent_grad, float *results_dev3,
+                            float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                            float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                            void *stream);
+
 /* The benchmarked unit: [K] DenominatorComputation::Forward() + Backward(deriv_weight, deriv)
  * (direct use in the reference: src/chain-supervision-test.hpp:403-414).
  *   logprob_dev   : device double[1], sum over sequences of the denominator log-prob

@@ -142,6 +142,9 @@ def _load():
     L.tc_chain_step_weighted.restype = C.c_int
     L.tc_chain_step_weighted.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, vp,
                                          vp, vp, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int, vp]
+    L.tc_chain_step_penalized.restype = C.c_int
+    L.tc_chain_step_penalized.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, vp,
+                                          vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, C.c_int64, C.c_int, vp]
     L.tc_supervision_free.restype = None
     L.tc_supervision_free.argtypes = [vp]
     for name in ("tc_supervision_num_pdf", "tc_supervision_num_sequence", "tc_supervision_num_frame"):

@@ -4,6 +4,7 @@
 // the kernels on the caller's stream.  No host synchronisation; no allocation once the per-device supervision
 // pool (supervision.cpp) is warm.
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <cstring>
 
@@ -644,8 +645,19 @@ int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *inp
                            int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1,
                            double *xent_objf_dev, const float *deriv_weights, int dtype, void *workspace,
                            int64_t workspace_bytes, int device, void *stream_v) {
+  return tc_chain_step_penalized(g, sup, input_v, xent_input_v, three_d, row_stride, l2_regularize, leaky, xent_regularize,
+                                 kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev, deriv_weights, 0.0f,
+                                 dtype, workspace, workspace_bytes, device, stream_v);
+}
+
+int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v,
+                            int three_d, int64_t row_stride, float l2_regularize, float leaky, float xent_regularize,
+                            int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1,
+                            double *xent_objf_dev, const float *deriv_weights, float out_of_range_regularize, int dtype,
+                            void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
   if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)deriv_weights & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
+  if (!(out_of_range_regularize >= 0.0f) || std::isinf(out_of_range_regularize)) return TC_ERR_INVALID_ARGUMENT;
   // (16-bit tensors travel as float pointers up to the kernels that read or write them: NumParams::elem, launch_to2d)
   const float *input = static_cast<const float *>(input_v), *xent_input = static_cast<const float *>(xent_input_v);
   float *grad = static_cast<float *>(grad_v), *xent_grad = static_cast<float *>(xent_grad_v);
@@ -663,13 +675,21 @@ int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *inp
   const int64_t rows = (int64_t)S * T;
   if (!three_d && row_stride < P) return TC_ERR_INVALID_ARGUMENT;
   // (tc_from2d's limits; the float32 unweighted call meets them in tc_from2d itself)
-  if ((half || deriv_weights) && three_d && (S > 65535 || (T + 239) / 240 > 65535)) return TC_ERR_UNSUPPORTED;
+  if ((half || deriv_weights || out_of_range_regularize > 0.0f) && three_d && (S > 65535 || (T + 239) / 240 > 65535))
+    return TC_ERR_UNSUPPORTED;
   // Kaldi's deriv_weights ([K] nnet-chain-training.cc: MulRowsVec on both derivatives, after the objectives are formed):
   // ignored by an evaluation step, which writes no gradient.  Every gradient element becomes w[row] * g, one float32
   // multiply of the unweighted value, in whichever pass writes it last: the layout copy back ((B, C, T)), the rounding
   // pass (16-bit 2-D), the numerator's xent stores (all layouts), and for the float32 2-D MMI gradient, which the
   // denominator and the numerator write into the caller's tensor, one in-place pass over it.
   const float *row_w = eval_only ? nullptr : deriv_weights;
+  // The out-of-range penalty (after [K] PenalizeOutOfRange, restated in torchain_hip.h): t = fl32(2c) * p(y) joins the
+  // MMI gradient in the same last passes, in front of the row weight; y is always the chain output `input`, also when
+  // kaldi_way == 0 runs the objective on xent_input.  (B, C, T): the layout copy back reads `input` where it lies, at the
+  // index it writes; 16-bit 2-D: the rounding pass reads the widened copy w.y2d; float32 2-D: the in-place pass that
+  // applies the row weights (or one of its own) reads `input` with its row stride.  pen_c2 == 0: none of this runs.
+  const float pen_c2 = eval_only ? 0.0f : 2.0f * out_of_range_regularize;
+  if (std::isinf(pen_c2)) return TC_ERR_INVALID_ARGUMENT;
   const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype);
   if (!workspace || (int64_t)w.total > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_v;
@@ -749,20 +769,23 @@ int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *inp
                   second_only && xent_objf_dev != nullptr, loss_dev1, dtype, row_w);
   if (rc != TC_OK) return rc;
   if (three_d && !eval_only && !half) {
-    if (row_w) {
+    if (row_w || pen_c2 > 0.0f) {
       DeviceGuard guard(device);
       if (!guard.ok) return TC_ERR_HIP;
-      rc = launch_from2d(TC_DTYPE_F32, gr, P, grad, S, P, T, -1.0f, stream, row_w);  // (-w[row] * g, one multiply)
+      // (-w[row] * g, one multiply; penalised: w[row] * (-g + t))
+      rc = pen_c2 > 0.0f ? launch_from2d_penalized(TC_DTYPE_F32, gr, P, grad, input, S, P, T, -1.0f, pen_c2, row_w, stream)
+                         : launch_from2d(TC_DTYPE_F32, gr, P, grad, S, P, T, -1.0f, stream, row_w);
     } else {
       rc = tc_from2d(gr, P, S, P, T, -1.0f, grad, device, stream_v);
     }
     if (rc != TC_OK) return rc;
   }
-  if (!three_d && !half && row_w) {
-    // behind chain_objf's launch_zero_on_fail, so a soft failure's -l2 * weight * y is weighted too
+  if (!three_d && !half && (row_w || pen_c2 > 0.0f)) {
+    // behind chain_objf's launch_zero_on_fail, so a soft failure's -l2 * weight * y is penalised and weighted too
     DeviceGuard guard(device);
     if (!guard.ok) return TC_ERR_HIP;
-    rc = launch_scale_rows(gr, rows, P, row_w, stream);
+    rc = pen_c2 > 0.0f ? launch_penalize_rows(gr, rows, P, input, row_stride, pen_c2, row_w, stream)
+                       : launch_scale_rows(gr, rows, P, row_w, stream);
     if (rc != TC_OK) return rc;
   }
   if (half && !eval_only) {
@@ -770,8 +793,12 @@ int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *inp
     // the row's weight for the MMI gradient; the numerator has weighted the xent gradient's entries already)
     DeviceGuard guard(device);
     if (!guard.ok) return TC_ERR_HIP;
-    rc = three_d ? launch_from2d(dtype, gr, P, grad, S, P, T, -1.0f, stream, row_w)
-                 : launch_round(dtype, gr, grad, rows * P, stream, row_w, P);
+    if (pen_c2 > 0.0f)
+      rc = three_d ? launch_from2d_penalized(dtype, gr, P, grad, input, S, P, T, -1.0f, pen_c2, row_w, stream)
+                   : launch_round_penalized(dtype, gr, grad, rows * P, w.y2d, pen_c2, row_w, P, stream);
+    else
+      rc = three_d ? launch_from2d(dtype, gr, P, grad, S, P, T, -1.0f, stream, row_w)
+                   : launch_round(dtype, gr, grad, rows * P, stream, row_w, P);
     if (rc == TC_OK && xg) rc = launch_round(dtype, xg, xent_grad, rows * P, stream);
   }
   return rc;  // (the loss value -objf / weight was written with the results: finalize_kernel)

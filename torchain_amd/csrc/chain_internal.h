@@ -499,6 +499,10 @@ int launch_step_loss(const float *results3, float *loss1, hipStream_t stream);
 int64_t trace_workspace_bytes();
 int launch_trace_mat_mat(const float *a, int64_t a_stride, const float *b, int64_t b_stride, int64_t rows, int cols,
                          double *partial, double *out, hipStream_t stream);
+// The one limit of the network output: the denominator kernels take exp(y) at clamp(y, -kOutputLimit, kOutputLimit)
+// (den_device.h:72-73, den_tied_device.h:83, den_slab_kernel.hip:47-48 spell the value out), and the out-of-range penalty
+// of tc_chain_step_penalized (after [K] PenalizeOutOfRange, restated in torchain_hip.h) acts outside the same range.
+constexpr float kOutputLimit = 30.0f;
 // row_w (the way back, !to2d; tc_chain_step_weighted): a per-row factor of the 2-D side, out = scale * row_w[row] * in
 // formed as (scale * row_w[row]) * in; null: out = scale * in
 int launch_layout(bool to2d, const float *in, float *out, int B, int Cn, int T, int64_t stride2d, float scale,
@@ -516,6 +520,17 @@ int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t s
 // a[r][c] *= row_w[r] in place on a contiguous float32 (rows, cols) matrix (the 2-D float32 MMI gradient of
 // tc_chain_step_weighted, which the denominator and the numerator write straight into the caller's tensor)
 int launch_scale_rows(float *a, int64_t rows, int cols, const float *row_w, hipStream_t stream);
+// penalty_kernels.hip (tc_chain_step_penalized, pen_c2 = fl32(2 * c) > 0): launch_from2d, launch_round and launch_scale_rows
+// with the out-of-range penalty in the same pass.  Each element becomes row_w[row] * fl32(g + fl32(pen_c2 * p(y))), with g
+// what the unpenalised pass writes for row_w == NULL, row_w NULL taken as 1, and y the network output of the element, laid
+// out as the pass's OUTPUT is: the caller's (B, C, T) tensor of `dtype`, the n contiguous widened floats, rows of y_stride.
+// An element with p == 0 keeps g's bits (times row_w).
+int launch_from2d_penalized(int dtype, const float *in, int64_t stride2d, void *out_bct, const void *y_bct, int B, int Cn,
+                            int T, float scale, float pen_c2, const float *row_w, hipStream_t stream);
+int launch_round_penalized(int dtype, const float *in, void *out, int64_t n, const float *y, float pen_c2, const float *row_w,
+                           int cols, hipStream_t stream);
+int launch_penalize_rows(float *a, int64_t rows, int cols, const float *y, int64_t y_stride, float pen_c2,
+                         const float *row_w, hipStream_t stream);
 
 extern thread_local int g_last_hip_error;
 

@@ -23,6 +23,13 @@ Same names, argument meaning, defaults and quirks as the reference:
   unweighted value (rounded once for 16-bit inputs), as Kaldi's ``MulRowsVec`` after ``ComputeChainObjfAndDeriv``;
   ``results``, the loss and ``xent_objf`` are unchanged.  ``None`` (the default) keeps the reference's behaviour, which
   drops the weights.  The one call applies them in the passes it makes anyway (``tc_chain_step_weighted``).
+* ``out_of_range_regularize`` (after Kaldi's ``PenalizeOutOfRange``, restated in ``torchain_hip.h``): the kernels take
+  ``exp(y)`` at ``clamp(y, -30, 30)``, so an output outside that range has lost the objective's restoring force.  With
+  ``c > 0`` every gradient element of the chain output gets ``t = fl32(2c) * p`` added, ``p`` the part of ``y`` beyond
+  ``+-30`` (0 inside, and for NaN / inf): descent on ``c * sum((y - clamp(y))**2)``, on every row, not scaled by the
+  supervision's weight, in front of ``deriv_weights``.  ``results``, the loss, ``xent_objf`` and the xent gradient do not
+  change; without a gradient the option does nothing.  ``0.0`` (the default, not Kaldi's 0.01) keeps the reference's
+  behaviour.  The one call adds it in the passes it makes anyway (``tc_chain_step_penalized``).
 """
 import ctypes as C
 import inspect
@@ -136,12 +143,15 @@ def _ptr(t):
 
 def compute_chain_objf_and_deriv(den_graph, supervision, nnet_output, results, nnet_output_deriv,
                                  xent_output_deriv, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                                 as_gradients=False, holder=None):
+                                 as_gradients=False, holder=None, *, out_of_range_regularize=0.0):
     """The hot call: replaces ``my_lib.my_lib_ComputeChainObjfAndDeriv`` (``src/my_lib.h:33-42``).
     ``results`` is the CPU float[3] tensor of ``ChainResults`` and is filled on return.  ``as_gradients``: the two
     matrices come back as the reference's backward returns them (``functions.py:106-115``), ``-deriv`` and
     ``-xent_regularize * xent_deriv`` (``tc_chain_objf_and_grad``).  ``holder``: the ``ChainResults`` that keeps the
-    device-side float[3]; when it asks for it (data-parallel use) the host copy is left to the caller."""
+    device-side float[3]; when it asks for it (data-parallel use) the host copy is left to the caller.
+    ``out_of_range_regularize``: the penalty of ``chain_loss`` on ``nnet_output_deriv`` (which is ``-g``, or ``g`` with
+    ``as_gradients``), added with torch ops behind the call; ``results`` and ``xent_output_deriv`` do not change."""
+    out_of_range_regularize = _out_of_range(out_of_range_regularize)
     assert nnet_output.is_cuda, "Only the HIP (ROCm) implementation is available"
     if nnet_output.dim() != 2 or nnet_output.stride(1) != 1 or nnet_output.dtype != torch.float32:
         raise ValueError("nnet_output must be a 2-D float32 tensor with unit column stride")
@@ -171,6 +181,10 @@ def compute_chain_objf_and_deriv(den_graph, supervision, nnet_output, results, n
             float(l2_regularize), float(leaky_hmm_coefficient), float(xent_regularize), _ptr(ws), ws.numel(),
             device.index, C.c_void_p(stream))
         check(rc, "tc_chain_objf_and_grad" if as_gradients else "tc_chain_objf_and_deriv")
+        if out_of_range_regularize > 0.0 and nnet_output_deriv is not None:
+            g = nnet_output_deriv if as_gradients else -nnet_output_deriv
+            g = _penalized(g, nnet_output, out_of_range_regularize)
+            nnet_output_deriv.copy_(g if as_gradients else -g)
         if holder is not None:
             holder._dev = res_dev  # (ChainResults.data copies it to the host when it is read)
             holder._stale = True
@@ -226,6 +240,46 @@ def _weights_on(w, device):
     return None if w is None else w.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+# the limit of the network output (kOutputLimit in the library): exp(y) is taken at clamp(y, -30, 30), and the
+# out-of-range penalty acts outside the same range
+OUTPUT_LIMIT = 30.0
+
+
+def _out_of_range(c):
+    """``chain_loss``'s ``out_of_range_regularize`` checked: a finite real number >= 0, returned as a float.  Raises
+    ``ValueError`` otherwise (before anything touches the GPU)."""
+    try:
+        value = float(c)
+    except (TypeError, ValueError):
+        raise ValueError("out_of_range_regularize must be a finite number >= 0, got %r" % (c,)) from None
+    if isinstance(c, bool) or not (0.0 <= value < float("inf")) or not (2.0 * value < 3.0e38):
+        raise ValueError("out_of_range_regularize must be a finite number >= 0, got %r" % (c,))
+    return value
+
+
+def _options(options, who="chain_loss"):
+    """The keyword-only extensions that ``chain_loss`` and its siblings take through ``**options`` -- today one,
+    ``out_of_range_regularize`` (default 0.0) -- checked: the penalty's factor as a float.  The pinned part of the signatures
+    (the reference's parameters, then ``deriv_weights`` as the one declared keyword-only argument) stays as it is; an
+    unknown keyword is the ``TypeError`` a declared signature would raise."""
+    c = options.pop("out_of_range_regularize", 0.0)
+    if options:
+        raise TypeError("%s() got an unexpected keyword argument %r" % (who, next(iter(options))))
+    return _out_of_range(c)
+
+
+def _penalized(g, y, c):
+    """The library's penalised gradient with torch ops in the library's order (``tc_chain_step_penalized``): ``g + t`` where
+    ``p != 0`` and ``g`` itself elsewhere, ``t = fl32(2c) * p``, ``p`` the part of ``y`` beyond ``+-OUTPUT_LIMIT`` (0 for NaN and
+    ``+-inf``).  Float32 throughout, one multiply and one add: bit for bit what the kernels write."""
+    y = y.detach().float()
+    zero = torch.zeros_like(y)
+    p = torch.where(y > OUTPUT_LIMIT, y - OUTPUT_LIMIT, torch.where(y < -OUTPUT_LIMIT, y + OUTPUT_LIMIT, zero))
+    p = torch.where(torch.isinf(y), zero, p)
+    t = p * (2.0 * c)  # (the scalar is rounded to float32 first: fl32(2c) * p)
+    return torch.where(p != 0, g.float() + t, g.float()).to(g.dtype)
+
+
 def _rows_of(x):
     """Frame-major rows of an nnet output: T*B for (B, C, T), the number of rows for 2-D."""
     return x.shape[0] * x.shape[2] if x.dim() == 3 else x.shape[0]
@@ -238,7 +292,8 @@ class _ChainLoss(Function):
 
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None):
+                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
+                out_of_range_regularize=0.0):
         assert input.is_cuda, "Only CUDA implementation is available"
         # The kernels write the two matrices as backward() returns them (-deriv, -xent_regularize * xent_deriv):
         # the reference scales one and negates both in three more passes over (T*B, C) tensors.
@@ -262,6 +317,7 @@ class _ChainLoss(Function):
                                              as_gradients=True, holder=results)
             ctx.xent_grad = xent_grad
         ctx.row_w = _weights_on(deriv_weights, input.device)
+        ctx.pen = (input.detach(), float(out_of_range_regularize))  # (always the chain output, never xent_input)
         if results._defer_host_copy:
             return input.new_zeros(1)  # (filled in behind the all-reduce: parallel.chain_loss_data_parallel)
         return _device_loss(results, input)
@@ -269,11 +325,13 @@ class _ChainLoss(Function):
     @staticmethod
     def backward(ctx, grad_output):
         g, xg = ctx.mmi_grad, getattr(ctx, "xent_grad", None)
+        if ctx.pen[1] > 0.0:  # (in front of the weights, as tc_chain_step_penalized)
+            g = _penalized(g, *ctx.pen)
         if ctx.row_w is not None:  # ([K] MulRowsVec on both derivatives)
             w = ctx.row_w.unsqueeze(1)
             g = g * w.to(g.dtype)
             xg = xg * w.to(xg.dtype) if xg is not None else None
-        return (g, xg, None, None, None, None, None, None, None, None)
+        return (g, xg, None, None, None, None, None, None, None, None, None)
 
 
 def _stream(device):
@@ -308,7 +366,8 @@ class _ChainLoss3d(Function):
 
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None):
+                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
+                out_of_range_regularize=0.0):
         assert input.is_cuda, "Only CUDA implementation is available"
         x2d = to2d_hip(input.detach())
         mmi_grad = torch.empty_like(x2d)
@@ -331,6 +390,7 @@ class _ChainLoss3d(Function):
             ctx.xent_shape = tuple(xent_input.shape)
             ctx.xent_scale = float(xent_regularize)
         ctx.row_w = _weights_on(deriv_weights, input.device)
+        ctx.pen = (input.detach(), float(out_of_range_regularize))
         if results._defer_host_copy:
             return input.new_zeros(1)
         return _device_loss(results, input)
@@ -339,12 +399,14 @@ class _ChainLoss3d(Function):
     def backward(ctx, grad_output):
         g = from2d_hip(ctx.mmi_grad, ctx.in_shape, -1.0)
         xg = from2d_hip(ctx.xent_grad, ctx.xent_shape, -ctx.xent_scale) if hasattr(ctx, "xent_grad") else None
+        if ctx.pen[1] > 0.0:
+            g = _penalized(g, *ctx.pen)
         if ctx.row_w is not None:  # ([K] MulRowsVec; row t*B + b is element (b, :, t) here)
             B, _, T = ctx.in_shape
             w = ctx.row_w.view(T, B).t().unsqueeze(1)
             g = g * w
             xg = xg * w if xg is not None else None
-        return (g, xg, None, None, None, None, None, None, None, None)
+        return (g, xg, None, None, None, None, None, None, None, None, None)
 
 
 class _ChainStep(Function):
@@ -355,10 +417,11 @@ class _ChainStep(Function):
 
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None):
+                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
+                out_of_range_regularize=0.0):
         out, grad, xgrad = _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
                                      leaky_hmm_coefficient, xent_regularize, kaldi_way, want_grad=True,
-                                     deriv_weights=deriv_weights)
+                                     deriv_weights=deriv_weights, out_of_range_regularize=out_of_range_regularize)
         ctx.grads = (grad, xgrad)
         if results._defer_host_copy:
             return input.new_zeros(1)
@@ -366,14 +429,15 @@ class _ChainStep(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return (ctx.grads[0], ctx.grads[1], None, None, None, None, None, None, None, None)
+        return (ctx.grads[0], ctx.grads[1], None, None, None, None, None, None, None, None, None)
 
 
 def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-              xent_regularize, kaldi_way, want_grad, deriv_weights=None):
-    """One ``tc_chain_step_weighted``.  ``want_grad=False`` is the evaluation step (``grad == NULL``): forward recursions
+              xent_regularize, kaldi_way, want_grad, deriv_weights=None, out_of_range_regularize=0.0):
+    """One ``tc_chain_step_penalized``.  ``want_grad=False`` is the evaluation step (``grad == NULL``): forward recursions
     only, no gradient tensors -- [K] ``ComputeChainObjfAndDeriv`` with ``nnet_output_deriv == NULL``; ``deriv_weights``
-    (checked by ``_deriv_weights``) are then not passed on."""
+    (checked by ``_deriv_weights``) are then not passed on, and ``out_of_range_regularize`` (checked by ``_out_of_range``)
+    has nothing to act on."""
     device = input.device
     three_d = input.dim() == 3
     use_xent = xent_input is not None and xent_regularize != 0.0
@@ -420,9 +484,10 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
                 C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 12),
                 C.c_void_p(out.data_ptr() + 16) if use_xent else None)
         tail = (_ptr(ws), ws.numel(), device.index, C.c_void_p(cur.cuda_stream))
-        # (float32 and NULL weights: tc_chain_step itself; bfloat16 / float16 are widened on the way in and their
-        # gradients rounded once on the way out)
-        check(lib.tc_chain_step_weighted(*args, _ptr(w), dtype, *tail), "tc_chain_step_weighted")
+        # (float32, NULL weights and no penalty: tc_chain_step itself; bfloat16 / float16 are widened on the way in and
+        # their gradients rounded once on the way out)
+        check(lib.tc_chain_step_penalized(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail),
+              "tc_chain_step_penalized")
         results._dev = out[:3]
         results._stale = True
         results._ready = None
@@ -500,24 +565,27 @@ def _fusable(x):
 
 def chain_loss(input, den_graph, supervision,
                l2_regularize=0.0, leaky_hmm_coefficient=1e-5,
-               xent_regularize=0.0, xent_input=None, kaldi_way=False, *, deriv_weights=None):
+               xent_regularize=0.0, xent_input=None, kaldi_way=False, *, deriv_weights=None, **options):
+    """``options``: ``out_of_range_regularize=0.0``, keyword-only (the module docstring; ``_options``)."""
     return _chain_loss_into(ChainResults(), input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                            xent_regularize, xent_input, kaldi_way, deriv_weights)
+                            xent_regularize, xent_input, kaldi_way, deriv_weights, _options(options))
 
 
 # What introspection reports stays the reference's signature (torchain/functions.py:128-130), the drop-in surface callers
-# compare against; ``deriv_weights`` is this library's keyword-only extension (``chain_loss.__kwdefaults__``).
+# compare against; ``deriv_weights`` (``chain_loss.__kwdefaults__``) and ``out_of_range_regularize`` (through ``**options``)
+# are this library's keyword-only extensions.
 chain_loss.__signature__ = inspect.signature(chain_loss).replace(
-    parameters=[p for p in inspect.signature(chain_loss).parameters.values() if p.name != "deriv_weights"])
+    parameters=[p for p in inspect.signature(chain_loss).parameters.values() if p.kind == p.POSITIONAL_OR_KEYWORD])
 
 
 def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                     xent_input, kaldi_way, deriv_weights=None):
+                     xent_input, kaldi_way, deriv_weights=None, out_of_range_regularize=0.0):
     """``chain_loss`` with the ``ChainResults`` given (parallel.chain_loss_data_parallel passes one that defers the
     host copy of the three floats until after its all-reduce)."""
     deriv_weights = _deriv_weights(deriv_weights, _rows_of(input))
+    c = _out_of_range(out_of_range_regularize)
     input, xent_input = _same_dtype(input, xent_input)
-    if not _needs_grad(input, xent_input):  # (deriv_weights: checked above, and not used without a gradient)
+    if not _needs_grad(input, xent_input):  # (deriv_weights and the penalty: checked above, not used without a gradient)
         # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the
         # forward recursions only.  The reference has no such check (functions.py:74,82) and pays for a training step.
         x, xe = _as_step_input(input), (_as_step_input(xent_input) if xent_input is not None else None)
@@ -529,16 +597,16 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
     if (_one_call(input) and _one_call(xent_input) and (xent_input is None or xent_input.dim() == input.dim())
             and (xent_input is None or xent_input.dim() == 3 or xent_input.stride(0) == input.stride(0))):
         loss = _ChainStep.apply(input, xent_input, results, den_graph, supervision,
-                                l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights)
+                                l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights, c)
         return loss, results
     if _fusable(input) and (xent_input is None or _fusable(xent_input)):
         loss = _ChainLoss3d.apply(input, xent_input, results, den_graph, supervision,
-                                  l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights)
+                                  l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights, c)
         return loss, results
     input = to2d(input)
     if xent_input is not None:
         xent_input = to2d(xent_input)
 
     loss = _ChainLoss.apply(input, xent_input, results, den_graph, supervision,
-                            l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights)
+                            l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights, c)
     return loss, results

@@ -13,10 +13,12 @@ over the gathered batch and ``parallel_train.py:26-75`` (per-device loss) is bro
 ``results.data = sum over devices``, ``loss = sum(loss_d * weight_d) / sum(weight_d)``
 (``parallel_train.py:70-75``) -- is what ``all_reduce_results`` implements.
 """
+import inspect
+
 import numpy as np
 import torch
 
-from .functions import ChainResults, _chain_loss_into
+from .functions import ChainResults, _chain_loss_into, _options
 
 
 def shard_range(num_sequences, rank, world_size):
@@ -154,24 +156,32 @@ def _finish_host_copy(results):
 
 def chain_loss_data_parallel(input, den_graph, supervision, l2_regularize=0.0, leaky_hmm_coefficient=1e-5,
                              xent_regularize=0.0, xent_input=None, kaldi_way=False, group=None, even_if_alone=False,
-                             *, deriv_weights=None):
+                             *, deriv_weights=None, **options):
     """``chain_loss`` on this rank's shard followed by the one all-reduce.  Returns
     ``(loss, results)`` where ``results`` holds the GLOBAL ``[objf, l2_term, weight]`` (and ``xent_objf``) and
     ``loss`` is a tensor whose value is the global ``-objf/weight`` and whose backward is this rank's local
     gradient (``-deriv``, exactly as the single-GPU wrapper; DDP then averages parameter grads).  The rank's own
     results never visit the host: the kernels' device-side floats go into the collective and one copy brings the
     reduced values back.  ``deriv_weights``: this rank's own weights (``shard_deriv_weights``), as ``chain_loss`` takes them;
-    they scale the local gradient only."""
+    they scale the local gradient only.  ``out_of_range_regularize`` (keyword-only, default 0.0, through ``**options``): as
+    ``chain_loss`` takes it; the term is per element of the local gradient, so every rank passes the same value and nothing
+    else is needed."""
+    c = _options(options, "chain_loss_data_parallel")
     if input.is_cuda and hasattr(den_graph, "prepare"):
         sync_den_graph_variant(den_graph, input.device, group)
     results = ChainResults()
     results._defer_host_copy = bool(input.is_cuda)
     loss, results = _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                                     xent_regularize, xent_input, kaldi_way, deriv_weights)
+                                     xent_regularize, xent_input, kaldi_way, deriv_weights, c)
     all_reduce_results(results, group=group, device=input.device if input.is_cuda else None, even_if_alone=even_if_alone)
     with torch.no_grad():
         loss.copy_(results.loss)
     return loss, results
+
+
+# (as chain_loss: introspection reports the declared parameters; the options taken through ``**options`` are in the docstring)
+chain_loss_data_parallel.__signature__ = inspect.signature(chain_loss_data_parallel).replace(
+    parameters=[p for p in inspect.signature(chain_loss_data_parallel).parameters.values() if p.kind != p.VAR_KEYWORD])
 
 
 def combine_results(list_of_results):
