@@ -85,7 +85,12 @@ int tc_den_graph_prepare(tc_den_graph *graph, int device);
  * frames_per_sequence, label_dim, fst).  The FST is the merged, epsilon-free, time-sorted acceptor
  * in CSR form: state i owns arcs [arc_begin[i], arc_begin[i+1]); start state 0; ilabel = pdf_id + 1;
  * final_weight[i] = +inf when state i is not final.  The handle splits the FST into its
- * num_sequences independent per-sequence acceptors (TC_ERR_NOT_SEPARABLE if it does not factor). */
+ * num_sequences independent per-sequence acceptors (TC_ERR_NOT_SEPARABLE if it does not factor).
+ * Size: a sequence may have any number of states.  The numerator keeps a sequence in LDS when it fits (16 * states +
+ * 4 * arcs + 4 * unique (frame, pdf) <= 160 KB, about 6000 states) and otherwise a window of two time levels, with a
+ * log-alpha history of 8 bytes per state in the supervision's device slot; the functions that run the numerator return
+ * TC_ERR_UNSUPPORTED only when a single time level does not fit (32 * states + 4 * arcs + 4 * unique of the level, about
+ * 4000 states) or the history exceeds 4 GiB.  tc_supervision_stats tells which, on the host. */
 int tc_supervision_create(tc_supervision **out, float weight, int32_t num_sequences,
                           int32_t frames_per_sequence, int32_t label_dim, int32_t num_states,
                           const int32_t *arc_begin, const int32_t *arc_ilabel, const float *arc_weight,
@@ -227,6 +232,17 @@ int32_t tc_supervision_num_pdf(const tc_supervision *supervision);
 int32_t tc_supervision_num_sequence(const tc_supervision *supervision);
 int32_t tc_supervision_num_frame(const tc_supervision *supervision);
 float tc_supervision_weight(const tc_supervision *supervision);
+/* What the numerator will do with a regular supervision, host only (nothing touches a GPU): out[0] = sequences,
+ * out[1] = frames per sequence, and the maxima over the sequences of out[2] = states, out[3] = arcs, out[4] = unique
+ * (frame, pdf) entries, out[5] = states of one time level, out[6] = arcs leaving one level, out[7] = unique entries of one
+ * frame; out[8] = LDS bytes of the resident kernel (a whole sequence on chip: 16 * states + 4 * arcs + 4 * unique),
+ * out[9] = LDS bytes of the level-windowed kernel (two adjacent levels: 32 * level states + 4 * level arcs + 4 * frame
+ * unique), out[10] = bytes of that kernel's log-alpha history (8 per state of the minibatch, in the supervision's device
+ * slot), out[11] = the kernel the numerator launches: 0 resident (out[8] <= 160 KB), 1 windowed (otherwise, or with
+ * tc_debug_set("force_num_windowed", 1) as it stands at this call), or the negative TC_ERR_* it returns --
+ * TC_ERR_UNSUPPORTED when one level does not fit LDS (out[9] + 2 KB > 160 KB) or the history exceeds 4 GiB.
+ * End-to-end supervisions have no levels: TC_ERR_INVALID_ARGUMENT, as for a null pointer. */
+int tc_supervision_stats(const tc_supervision *supervision, int64_t *out12);
 
 /* Copies the supervision's arc tables to `device` on `stream` (asynchronously: pinned staging; idempotent -- a
  * later call on another stream makes that stream wait for the copy).  The tables live in a slot of a per-device
@@ -524,6 +540,9 @@ int tc_from2d(const float *in2d, int64_t in_stride, int32_t B, int32_t C, int32_
  *                     T / 2 is the balanced choice, profiles/r06_planes_ab.txt)
  *   "exp_per_frame"  (1: the streamed path transposes exp(y) one frame at a time, as it does when all frames would take
  *                     more than 1 GB of workspace)
+ *   "force_num_windowed" (1: regular supervisions that fit the resident numerator kernel take the level-windowed one,
+ *                     which otherwise serves those that do not fit; same bits.  Read at every numerator launch and by
+ *                     tc_supervision_stats)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -538,7 +557,8 @@ int tc_debug_set(const char *key, int value);
  * (tc_den_graph_prepare's one-off timing launches of a graph's two kernels are counted like any other);
  * "den_long_utterance_launches" = on-chip denominator launches whose frame sums did not fit LDS and went through the
  * workspace (utterances of many hundred frames on the largest on-chip graphs); "num_e2e_staged_launches" = end-to-end
- * numerator launches that ran beside the denominator and left their posteriors for the scatter kernel.
+ * numerator launches that ran beside the denominator and left their posteriors for the scatter kernel;
+ * "num_windowed_launches" = regular numerator launches that took the level-windowed kernel (counted in "num_launches" too).
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -152,6 +152,8 @@ def _load():
         getattr(L, name).argtypes = [vp]
     L.tc_supervision_weight.restype = f32
     L.tc_supervision_weight.argtypes = [vp]
+    L.tc_supervision_stats.restype = C.c_int
+    L.tc_supervision_stats.argtypes = [vp, vp]
     L.tc_supervision_prepare.restype = C.c_int
     L.tc_supervision_prepare.argtypes = [vp, C.c_int, vp]
     L.tc_chain_workspace_bytes.restype = i64

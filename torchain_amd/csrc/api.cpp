@@ -226,6 +226,9 @@ int fill_num_params(tc_supervision *sup, int device, hipStream_t stream, const f
   p->lds_states = (sup->tab.max_states + 1) & ~1;
   p->lds_arcs = (sup->tab.max_arcs + 3) & ~3;
   p->lds_uniq = (sup->tab.max_uniq + 3) & ~3;
+  p->win_states = (sup->tab.max_level_states + 1) & ~1;
+  p->win_arcs = (sup->tab.max_level_arcs + 3) & ~3;
+  p->win_uniq = (sup->tab.max_frame_uniq + 3) & ~3;
   return TC_OK;
 }
 

@@ -310,7 +310,23 @@ struct NumTables {
   std::vector<int32_t> uniq_begin;    // per uniq (+1 per sequence): range into uniq_arc
   std::vector<int32_t> uniq_arc;      // local arc ids in increasing order
   int32_t max_states = 0, max_arcs = 0, max_uniq = 0;
+  // what the level-windowed kernel (num_windowed_kernels.hip) needs besides: where each frame's unique entries begin,
+  // and the widest level / the most arcs leaving one level / the most unique entries of one frame over all sequences
+  std::vector<int32_t> frame_uniq;    // [S][T + 1] sequence-local unique id where each frame's entries begin
+  int32_t max_level_states = 0, max_level_arcs = 0, max_frame_uniq = 0;
 };
+
+// LDS of the two regular numerator kernels (launch_num, tc_supervision_stats).  Resident (num_kernels.hip): log-alpha and
+// log-beta per state, y per unique (frame, pdf), the occupation per arc, of a whole sequence.  Windowed
+// (num_windowed_kernels.hip): log-alpha and log-beta of two adjacent levels, y and the occupations of one frame.
+inline size_t num_resident_lds_bytes(int32_t max_states, int32_t max_arcs, int32_t max_uniq) {
+  return (size_t)((max_states + 1) & ~1) * 16 + (size_t)((max_uniq + 3) & ~3) * 4 + (size_t)((max_arcs + 3) & ~3) * 4;
+}
+inline size_t num_windowed_lds_bytes(int32_t level_states, int32_t level_arcs, int32_t frame_uniq) {
+  return (size_t)((level_states + 1) & ~1) * 32 + (size_t)((frame_uniq + 3) & ~3) * 4 + (size_t)((level_arcs + 3) & ~3) * 4;
+}
+// (beside its dynamic arrays the windowed kernel has a total and the 128 shares of the cross-entropy sum in static LDS)
+inline bool num_windowed_fits(size_t dynamic_bytes) { return dynamic_bytes + 2048 <= (size_t)kLdsLimitBytes; }
 
 // End-to-end supervision ([K] Supervision::e2e_fsts, supervision_e2e.cpp): per-sequence acceptors with cycles, walked
 // frame by frame by num_e2e_kernels.hip.  Per sequence: states [state_off[s], state_off[s+1]), arcs [arc_off[s], ...),
@@ -354,6 +370,10 @@ struct NumDev {
   const int32_t *seq_state_off, *seq_arc_off, *seq_uniq_off, *level_begin, *out_begin, *in_begin, *in_arc,
       *arc_src, *arc_dst, *arc_uniq, *uniq_t, *uniq_pdf, *uniq_begin, *uniq_arc;
   const float *arc_logw, *final_logw;
+  // the level-windowed kernel's: frame_uniq as NumTables'; alpha_hist = its log-alpha history, one double per state of
+  // every sequence, in the pool slot behind the tables (not uploaded)
+  const int32_t *frame_uniq = nullptr;
+  double *alpha_hist = nullptr;
   float *stage = nullptr;  // [unique (frame, pdf) entries of all sequences]: posteriors in transit (launch_num_scatter)
   PoolSlot *slot = nullptr;
   size_t upload_bytes = 0;  // of the slot's pinned staging, to be copied to the device
@@ -387,6 +407,7 @@ struct NumParams {
   // only its posteriors' entries, so the 3-D call needs no frame-major copy of either (tc_chain_step)
   int xent_bct = 0, xent_out_bct = 0, y_bct = 0;  // (y is read at the supervision's (frame, pdf) pairs only)
   int lds_states, lds_arcs, lds_uniq;
+  int win_states, win_arcs, win_uniq;  // the same for one level / one frame (the level-windowed kernel's LDS arrays)
   // TC_DTYPE_* of y and xent_out when they are the caller's 16-bit (B, C, T) tensors (tc_chain_step_typed): the kernels
   // widen what they read; the 2-D pointers of this structure are always float32
   int elem = TC_DTYPE_F32;
@@ -468,6 +489,7 @@ inline size_t pair_stamp_bytes(int T) { return ((size_t)2 * kWaves * (T + 2) * 8
 int64_t big_small_floats(int hb, int P, int T, int Sp);
 int launch_num(const NumParams &p, hipStream_t stream);
 int launch_num_scatter(const NumParams &p, hipStream_t stream);
+int launch_num_windowed(const NumParams &p, hipStream_t stream);     // num_windowed_kernels.hip (via launch_num)
 int launch_num_e2e(const NumParams &p, hipStream_t stream);          // num_e2e_kernels.hip (via launch_num)
 int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via launch_num_scatter)
 size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs);
@@ -538,7 +560,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -547,7 +569,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -12,21 +12,9 @@
 
 #include "chain_internal.h"
 #include "half_io.h"
+#include "num_device.h"
 
 namespace tc {
-
-__device__ __forceinline__ double log_add(double x, double y) {
-  // [K] LogAdd(double, double), kMinLogDiffDouble = log(DBL_EPSILON)
-  double diff;
-  if (x < y) {
-    diff = x - y;
-    x = y;
-  } else {
-    diff = y - x;
-  }
-  if (diff >= -36.04365338911715) return x + log1p(exp(diff));
-  return x;
-}
 
 // Two wavefronts per sequence: the alpha and the beta recursions do not depend on each other, so wave 0
 // walks the levels forward while wave 1 walks them backward (T steps each, one shared barrier per step);
@@ -37,18 +25,7 @@ __device__ __forceinline__ double log_add(double x, double y) {
 // weight: a few KB) are copied into LDS first.  The T steps are one chain of dependent loads per step -- offsets ->
 // arc ids -> arc fields -> alpha -- and from global memory every link was an L2 round trip: 0.73 us per step, 0.11 ms
 // for 150 frames whatever the batch; from LDS the chain is a fraction of that.
-// the 128 threads' shares of a sequence's cross-entropy objective, added in a fixed order
-__device__ __forceinline__ void seq_xent_sum(double v, double *out, int tid) {
-  __shared__ double xo_sh[128];
-  xo_sh[tid] = v;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 128; ++i) t += xo_sh[i];
-    *out = t;
-  }
-}
-
+// (the arithmetic itself is in num_device.h, shared with the level-windowed kernel)
 // E: element type of y / xent_out when they are the caller's (B, C, T) tensors (NumParams::elem; 2-D: float32)
 template <bool STAGE, typename E = float>
 __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
@@ -69,7 +46,7 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
 
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int T = p.T, S = p.S;
+  const int T = p.T;
   const int sb = p.t.seq_state_off[q], nst = p.t.seq_state_off[q + 1] - sb;
   const int ab = p.t.seq_arc_off[q], narc = p.t.seq_arc_off[q + 1] - ab;
   const int ub = p.t.seq_uniq_off[q], nu = p.t.seq_uniq_off[q + 1] - ub;
@@ -102,17 +79,12 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
   auto arc_dst = [&](int a) __attribute__((always_inline)) { return STAGE ? s_dst[a] : g_arc_dst[a]; };
   auto arc_uniq = [&](int a) __attribute__((always_inline)) { return STAGE ? s_uq[a] : g_arc_uniq[a]; };
   auto arc_logw = [&](int a) __attribute__((always_inline)) { return STAGE ? s_lw[a] : g_arc_logw[a]; };
+  auto score = [&](int a) __attribute__((always_inline)) { return ylp[arc_uniq(a)] + arc_logw(a); };
   const float *final_logw = p.t.final_logw + sb;
   const bool want_beta = p.deriv != nullptr || p.xent != nullptr || p.seq_xent != nullptr;
 
   // gather: [K] nnet_output_.Lookup(nnet_output_indexes_, ...); row = t*S + q
-  for (int u = tid; u < nu; u += 128)
-    if constexpr (std::is_same<E, float>::value)
-      ylp[u] = p.y_bct ? p.y[((int64_t)q * p.P + p.t.uniq_pdf[ub + u]) * T + p.t.uniq_t[ub + u]]
-                       : p.y[((int64_t)p.t.uniq_t[ub + u] * S + q) * p.y_stride + p.t.uniq_pdf[ub + u]];
-    else
-      ylp[u] = p.y_bct ? load_elem<E>(p.y, ((int64_t)q * p.P + p.t.uniq_pdf[ub + u]) * T + p.t.uniq_t[ub + u])
-                       : p.y[((int64_t)p.t.uniq_t[ub + u] * S + q) * p.y_stride + p.t.uniq_pdf[ub + u]];
+  for (int u = tid; u < nu; u += 128) ylp[u] = num_load_y<E>(p, q, ub + u);
   for (int i = tid; i < nst; i += 128) {
     log_alpha[i] = i == 0 ? 0.0 : -INFINITY;
     log_beta[i] = -INFINITY;
@@ -127,34 +99,24 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
       // forward: level step+1 states take the log-sum over their in-arcs, in arc order
       const int l0 = level(step + 1), l1 = level(step + 2);
       for (int st = l0 + lane; st < l1; st += 64) {
-        double acc = -INFINITY;
-        for (int i = in_begin(st); i < in_begin(st + 1); ++i) {
-          const int a = in_arc(i);
-          const float sc = ylp[arc_uniq(a)] + arc_logw(a);  // float sum, as Kaldi
-          acc = log_add(acc, (double)sc + log_alpha[arc_src(a)]);
-        }
-        log_alpha[st] = acc;
+        log_alpha[st] = num_state_log_sum(in_begin(st), in_begin(st + 1), in_arc, score,
+                                          [&](int a) __attribute__((always_inline)) { return log_alpha[arc_src(a)]; });
       }
     } else if (want_beta) {
       // backward: level T-1-step states take the log-sum over their out-arcs
       const int t = T - 1 - step;
       const int l0 = level(t), l1 = level(t + 1);
       for (int st = l0 + lane; st < l1; st += 64) {
-        double this_log_beta = -INFINITY;  // interior states are not final
-        for (int a = out_begin(st); a < out_begin(st + 1); ++a) {
-          const float sc = ylp[arc_uniq(a)] + arc_logw(a);
-          this_log_beta = log_add(this_log_beta, (double)sc + log_beta[arc_dst(a)]);
-        }
-        log_beta[st] = this_log_beta;
+        log_beta[st] = num_state_log_sum(out_begin(st), out_begin(st + 1), [](int a) __attribute__((always_inline)) { return a; },
+                                         score, [&](int a) __attribute__((always_inline)) { return log_beta[arc_dst(a)]; });
       }
     }
     __syncthreads();
   }
   // total: log-add over final states in state order (one lane; a handful of states)
   if (tid == 0) {
-    double tot = -INFINITY;
-    for (int st = level(T); st < level(T + 1); ++st)
-      if (final_logw[st] != -INFINITY) tot = log_add(tot, log_alpha[st] + (double)final_logw[st]);
+    const double tot = num_total(level(T), level(T + 1), final_logw,
+                                 [&](int st) __attribute__((always_inline)) { return log_alpha[st]; });
     tot_sh = tot;
     p.seq_logprob[q] = tot;
   }
@@ -162,40 +124,20 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
   if (!want_beta) return;
   const double tot = tot_sh;
   // occupation of every arc: exp(alpha(src) + score + beta(dst) - tot)
-  for (int a = tid; a < narc; a += 128) {
-    const float sc = ylp[arc_uniq(a)] + arc_logw(a);
-    const float occupation_logprob = (float)(log_alpha[arc_src(a)] + (double)sc + log_beta[arc_dst(a)] - tot);
-    occ[a] = __expf(occupation_logprob);
-  }
+  for (int a = tid; a < narc; a += 128) occ[a] = num_occupation(log_alpha[arc_src(a)], score(a), log_beta[arc_dst(a)], tot);
   __syncthreads();
   // scatter: [K] AddElements(weight, indexes, derivs)
   const int *uniq_begin = p.t.uniq_begin + ub + q;
   const int *uniq_arc = p.t.uniq_arc + ab;
   double xo = 0.0;
   for (int u = tid; u < nu; u += 128) {
-    float sum = 0.f;
-    for (int i = uniq_begin[u]; i < uniq_begin[u + 1]; ++i) sum += occ[uniq_arc[i]];
-    const float v = p.weight * sum;
-    const int64_t row = (int64_t)p.t.uniq_t[ub + u] * S + q;
-    const int pdf = p.t.uniq_pdf[ub + u];
+    const float v = num_posterior(p, uniq_arc, uniq_begin[u], uniq_begin[u + 1],
+                                  [&](int a) __attribute__((always_inline)) { return occ[a]; });
     if (p.staged) {
       p.t.stage[ub + u] = v;  // beside the denominator: launch_num_scatter adds it once deriv is written
       continue;
     }
-    // (scales other than 1 only through tc_chain_objf_and_grad: the reference's backward, -deriv and
-    // -xent_regularize * xent_deriv, formed here instead of in two more passes over the matrices)
-    if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
-    const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + p.t.uniq_t[ub + u];  // (sequence, pdf, frame) of a (B, C, T) tensor
-    if (p.xent) {  // (times the row's deriv_weight when one is given; the objective term below is not)
-      const float xv = p.xent_scale * v;
-      p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_row_w ? p.xent_row_w[row] * xv : xv;
-    }
-    // (the cross-entropy output: the caller's (B, C, T) tensor of element type E, or a float32 matrix)
-    if (p.seq_xent)
-      xo += (double)(p.xent_scale * v) * (double)(std::is_same<E, float>::value
-                                                      ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
-                                                  : p.xent_out_bct ? load_elem<E>(p.xent_out, bct)
-                                                                   : p.xent_out[row * p.xent_out_stride + pdf]);
+    num_scatter_one<E>(p, q, ub + u, v, xo);
   }
   if (p.seq_xent && !p.staged) seq_xent_sum(xo, p.seq_xent + q, tid);
 }
@@ -204,25 +146,11 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
 // per (row, pdf) as above.
 template <typename E = float>
 __global__ __launch_bounds__(128) void num_scatter_kernel(const NumParams p) {
-  const int q = blockIdx.x, S = p.S;
+  const int q = blockIdx.x;
   const int ub = p.t.seq_uniq_off[q], nu = p.t.seq_uniq_off[q + 1] - ub;
   double xo = 0.0;
   for (int u = threadIdx.x; u < nu; u += 128) {
-    const float v = p.t.stage[ub + u];
-    const int64_t row = (int64_t)p.t.uniq_t[ub + u] * S + q;
-    const int pdf = p.t.uniq_pdf[ub + u];
-    if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
-    const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + p.t.uniq_t[ub + u];  // (sequence, pdf, frame) of a (B, C, T) tensor
-    if (p.xent) {  // (times the row's deriv_weight when one is given; the objective term below is not)
-      const float xv = p.xent_scale * v;
-      p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_row_w ? p.xent_row_w[row] * xv : xv;
-    }
-    // (the cross-entropy output: the caller's (B, C, T) tensor of element type E, or a float32 matrix)
-    if (p.seq_xent)
-      xo += (double)(p.xent_scale * v) * (double)(std::is_same<E, float>::value
-                                                      ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
-                                                  : p.xent_out_bct ? load_elem<E>(p.xent_out, bct)
-                                                                   : p.xent_out[row * p.xent_out_stride + pdf]);
+    num_scatter_one<E>(p, q, ub + u, p.t.stage[ub + u], xo);
   }
   if (p.seq_xent) seq_xent_sum(xo, p.seq_xent + q, threadIdx.x);
 }
@@ -262,7 +190,8 @@ int launch_num(const NumParams &p, hipStream_t stream) {
   count_launch(kCntNum);
   if (p.deriv || p.xent || p.seq_xent) count_launch(kCntNumBackward);
   const size_t lds = (size_t)p.lds_states * 16 + (size_t)p.lds_uniq * 4 + (size_t)p.lds_arcs * 4;
-  if (lds > (size_t)kLdsLimitBytes) return TC_ERR_UNSUPPORTED;
+  // a sequence that does not fit one workgroup's LDS: a window of levels instead (num_windowed_kernels.hip)
+  if (lds > (size_t)kLdsLimitBytes || debug_flag(kDbgForceNumWindowed)) return launch_num_windowed(p, stream);
   // with the sequence's tables staged in LDS when that keeps a workgroup within a quarter of a CU's LDS
   const size_t staged = lds + ((size_t)2 * (p.lds_states + 2) + (size_t)5 * p.lds_arcs + (size_t)(p.T + 2)) * 4;
   if (staged <= (size_t)kLdsLimitBytes / 4) return launch_num_fwd_bwd<true>(p, staged, stream);

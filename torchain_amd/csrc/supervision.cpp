@@ -304,6 +304,22 @@ int tc_supervision_create(tc_supervision **out, float weight, int32_t S, int32_t
       tb.uniq_begin.push_back(run);
       tb.seq_uniq_off.push_back((int32_t)tb.uniq_t.size());
       tb.max_uniq = std::max(tb.max_uniq, (int32_t)tb.uniq_t.size() - ubase);
+      // where each frame's entries begin (the frame only moves forward, so they are one range per frame)
+      const int32_t nu = (int32_t)tb.uniq_t.size() - ubase;
+      const size_t fb = tb.frame_uniq.size();
+      tb.frame_uniq.resize(fb + T + 1, nu);
+      for (int32_t u = nu - 1; u >= 0; --u) tb.frame_uniq[fb + tb.uniq_t[ubase + u]] = u;
+      for (int32_t f = T - 1; f >= 0; --f)
+        if (tb.frame_uniq[fb + f] > tb.frame_uniq[fb + f + 1]) tb.frame_uniq[fb + f] = tb.frame_uniq[fb + f + 1];
+      for (int32_t f = 0; f < T; ++f)
+        tb.max_frame_uniq = std::max(tb.max_frame_uniq, tb.frame_uniq[fb + f + 1] - tb.frame_uniq[fb + f]);
+    }
+    // the widest level and the most arcs leaving one level (the level-windowed kernel's LDS: num_windowed_kernels.hip)
+    const int32_t *lv = &tb.level_begin[(size_t)q * (T + 2)];
+    const int32_t *ob = &tb.out_begin[tb.out_begin.size() - (size_t)(nloc + 1)];  // this sequence's nloc + 1 entries
+    for (int32_t t = 0; t <= T; ++t) {
+      tb.max_level_states = std::max(tb.max_level_states, lv[t + 1] - lv[t]);
+      tb.max_level_arcs = std::max(tb.max_level_arcs, ob[lv[t + 1]] - ob[lv[t]]);
     }
     tb.seq_state_off.push_back((int32_t)tb.final_logw.size());
     tb.seq_arc_off.push_back((int32_t)tb.arc_src.size());
@@ -326,6 +342,34 @@ int32_t tc_supervision_num_sequence(const tc_supervision *s) { return s ? s->S :
 int32_t tc_supervision_num_frame(const tc_supervision *s) { return s ? s->T : 0; }
 float tc_supervision_weight(const tc_supervision *s) { return s ? s->weight : 0.f; }
 
+int tc_supervision_stats(const tc_supervision *s, int64_t *out) {
+  if (!s || !out) return TC_ERR_INVALID_ARGUMENT;
+  if (s->e2e) return TC_ERR_INVALID_ARGUMENT;  // (an end-to-end supervision has no levels: num_e2e_kernels.hip)
+  const NumTables &tb = s->tab;
+  const int64_t resident = (int64_t)num_resident_lds_bytes(tb.max_states, tb.max_arcs, tb.max_uniq);
+  const int64_t windowed = (int64_t)num_windowed_lds_bytes(tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq);
+  const int64_t hist = (int64_t)tb.final_logw.size() * 8;
+  out[0] = s->S;
+  out[1] = s->T;
+  out[2] = tb.max_states;
+  out[3] = tb.max_arcs;
+  out[4] = tb.max_uniq;
+  out[5] = tb.max_level_states;
+  out[6] = tb.max_level_arcs;
+  out[7] = tb.max_frame_uniq;
+  out[8] = resident;
+  out[9] = windowed;
+  out[10] = hist;
+  // launch_num's decision (num_kernels.hip), and stage_locked's bound on the history
+  if (hist > kE2eMaxScratchBytes)
+    out[11] = TC_ERR_UNSUPPORTED;
+  else if (resident <= kLdsLimitBytes && !debug_flag(kDbgForceNumWindowed))
+    out[11] = 0;
+  else
+    out[11] = num_windowed_fits((size_t)windowed) ? 1 : TC_ERR_UNSUPPORTED;
+  return TC_OK;
+}
+
 // The host half of an upload: the supervision's tables into the pinned staging of a pool slot (2-3 MB of memcpy for 64
 // x 150 frames).  No stream is involved, so a reader's look-ahead thread can do it (tc_supervision_stage) and the
 // training thread's first use of the supervision only enqueues the copy.  Caller holds sup->mu.
@@ -343,6 +387,7 @@ static int stage_locked(tc_supervision *sup, int device) {
       {tb.uniq_t.data(), tb.uniq_t.size() * 4},               {tb.uniq_pdf.data(), tb.uniq_pdf.size() * 4},
       {tb.uniq_begin.data(), tb.uniq_begin.size() * 4},       {tb.uniq_arc.data(), tb.uniq_arc.size() * 4},
       {tb.arc_logw.data(), tb.arc_logw.size() * 4},           {tb.final_logw.data(), tb.final_logw.size() * 4},
+      {tb.frame_uniq.data(), tb.frame_uniq.size() * 4},
   };
   const int nparts = (int)(sizeof(parts) / sizeof(parts[0]));
   size_t total = 0;
@@ -356,6 +401,12 @@ static int stage_locked(tc_supervision *sup, int device) {
   // runs beside the denominator (api.cpp); not part of the upload
   const size_t upload = total, stage_off = total;
   total += (tb.uniq_t.size() * 4 + 255) & ~(size_t)255;
+  // and the level-windowed kernel's log-alpha history, one double per state (num_windowed_kernels.hip); sized with the
+  // slot like the end-to-end numerator's (supervision_e2e.cpp), so that no workspace depends on the kernel taken
+  const size_t hist_bytes = tb.final_logw.size() * 8;
+  if (hist_bytes > (size_t)kE2eMaxScratchBytes) return TC_ERR_UNSUPPORTED;
+  const size_t hist_off = total;
+  total += (hist_bytes + 255) & ~(size_t)255;
   // A new supervision arrives with every minibatch: its tables live in a slot of a per-device pool (device
   // blob + PINNED host staging + two events), so that after warm-up a step neither allocates nor frees
   // device memory and the upload is a true asynchronous copy.
@@ -375,7 +426,9 @@ static int stage_locked(tc_supervision *sup, int device) {
   d.arc_uniq = P(9); d.uniq_t = P(10); d.uniq_pdf = P(11); d.uniq_begin = P(12); d.uniq_arc = P(13);
   d.arc_logw = (const float *)P(14);
   d.final_logw = (const float *)P(15);
+  d.frame_uniq = P(16);
   d.stage = (float *)(blob + stage_off);
+  d.alpha_hist = (double *)(blob + hist_off);
   sup->dev[device] = d;
   return TC_OK;
 }

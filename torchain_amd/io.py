@@ -212,6 +212,20 @@ class Supervision:
     def weight(self):
         return lib.tc_supervision_weight(self.ptr)
 
+    def stats(self):
+        """What the numerator will do with this (regular) supervision, known on the host before anything runs
+        (``tc_supervision_stats``): sizes of the largest sequence, of its widest time level, the LDS either numerator
+        kernel would need, and ``kernel``: ``"resident"`` (a whole sequence on chip), ``"windowed"`` (two time levels
+        on chip; sequences of any size) or ``"unsupported"`` (a single level beyond LDS: ``chain_loss`` will raise).
+        ``route`` is the same as a number (0, 1, negative error code).  End-to-end supervisions raise."""
+        out = np.zeros(12, np.int64)
+        check(lib.tc_supervision_stats(self.ptr, _p(out)), "tc_supervision_stats")
+        keys = ("sequences", "frames", "max_states", "max_arcs", "max_uniq", "max_level_states", "max_level_arcs",
+                "max_frame_uniq", "resident_lds_bytes", "windowed_lds_bytes", "history_bytes", "route")
+        d = dict(zip(keys, (int(x) for x in out)))
+        d["kernel"] = {0: "resident", 1: "windowed"}.get(d["route"], "unsupported")
+        return d
+
     def __del__(self, _free=lib.tc_supervision_free):
         ptr = getattr(self, "ptr", None)
         if ptr:
