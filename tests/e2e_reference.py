@@ -90,6 +90,35 @@ def random_fst(num_states, num_arcs, num_pdfs, rng, pdf_pool=None):
     return _csr(num_states, arcs, final, start=start)
 
 
+def with_unreachable_states(fst, pdfs, rng, extra=4):
+    """``fst`` plus ``extra`` states that no arc enters (so the start cannot reach them), each with arcs into the old states
+    that carry ``pdfs`` -- pdfs no other arc carries, so they are among the FST's distinct pdfs and their posteriors are
+    exactly 0 -- and one of them final."""
+    start, ab, il, aw, nx, final = fst
+    n = len(final)
+    assert not np.isin(np.asarray(pdfs) + 1, il).any()
+    new_il, new_aw, new_nx, new_ab = [], [], [], [int(ab[-1])]
+    for _ in range(extra):
+        for p in pdfs:
+            new_il.append(int(p) + 1)
+            new_aw.append(float(rng.uniform(0, 1)))
+            new_nx.append(int(rng.integers(0, n)))
+        new_ab.append(new_ab[-1] + len(pdfs))
+    more_final = np.full(extra, np.inf, np.float32)
+    more_final[-1] = 0.5
+    return (start, np.concatenate([ab, new_ab[1:]]).astype(np.int32), np.concatenate([il, new_il]).astype(np.int32),
+            np.concatenate([aw, new_aw]).astype(np.float32), np.concatenate([nx, new_nx]).astype(np.int32),
+            np.concatenate([final, more_final]).astype(np.float32))
+
+
+def distinct_pdfs_fst(num_states, num_arcs, num_pdfs, distinct, rng):
+    """``random_fst`` whose arcs carry exactly the pdfs 0 .. ``distinct`` - 1, every one of them present."""
+    fst = random_fst(num_states, num_arcs, num_pdfs, rng, pdf_pool=np.arange(distinct))
+    fst[2][:distinct] = rng.permutation(distinct) + 1
+    assert len(set(fst[2].tolist())) == distinct
+    return fst
+
+
 def batch(kind, S, num_pdfs, seed, **kw):
     rng = np.random.default_rng(seed)
     if kind == "chain":
@@ -179,3 +208,50 @@ def e2e_objective(den_graph, fsts, T, y, weight=1.0, l2=0.0, leaky=1e-5):
         deriv = -weight * l2 * y64
         xent = np.zeros_like(y64)
     return dict(objf=objf, l2_term=l2_term, weight=tot_weight, deriv=deriv, xent_deriv=xent, logz=logz, ok=ok)
+
+
+# ---- the end-to-end kernel's arithmetic, restated -----------------------------------------------------------------------------
+def kernel_arithmetic(fst, y, weight=1.0):
+    """What ``csrc/num_e2e_kernels.hip`` computes for one sequence, in numpy with the kernel's number formats: log alpha and
+    log beta in double, an arc's score ``y - cost`` a float32 sum, every log-sum a maximum and a float32 sum (in arc order) of
+    float32 ``exp`` of the float32 difference, occupations float32 ``exp`` of the float32 log-occupation summed per pdf in
+    float32, and every frame divided by its own total.  ``y``: the sequence's rows, (T, P) float32.  Returns (log Z,
+    weight * posteriors (T, P) float32).  ``exp`` is rounded correctly, so only the device's own is missing: what this differs from float64 by is what the
+    kernel's formats cost, and the tolerance of the GPU test is set from it."""
+    start, ab, il, aw, nx, final = fst
+    f32, n, T = np.float32, len(final), y.shape[0]
+    src, dst, pdf = np.repeat(np.arange(n), np.diff(ab)), np.asarray(nx), np.asarray(il) - 1
+    lw, flw = -np.asarray(aw, f32), -np.asarray(final, f32).astype(np.float64)
+
+    def exp32(x):
+        """exp of a float32, rounded to float32 once (numpy's own float32 exp is a few ulp off)"""
+        return np.exp(x.astype(f32).astype(np.float64)).astype(f32)
+
+    def log_sum(x, index):
+        """per index: max + log(float32 sum of float32 exp(x - max)); -inf for an empty or all -inf group"""
+        mx = np.full(n, -np.inf)
+        np.maximum.at(mx, index, x)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            e = np.where(np.isfinite(mx[index]), exp32(x - mx[index]), f32(0))
+            sm = np.zeros(n, f32)
+            np.add.at(sm, index, e.astype(f32))
+            return np.where(np.isfinite(mx), mx + np.log(sm.astype(np.float64)), -np.inf)
+
+    alpha = np.full((T + 1, n), -np.inf)
+    alpha[0, start] = 0.0
+    score = [(lw + y[t, pdf]).astype(f32).astype(np.float64) for t in range(T)]
+    for t in range(T):
+        alpha[t + 1] = log_sum(alpha[t, src] + score[t], dst)
+    x = alpha[T] + flw
+    logz = x.max() + np.log(np.float64(exp32(x - x.max()).sum(dtype=f32)))
+    beta = flw
+    post = np.zeros(y.shape, f32)
+    for t in range(T - 1, -1, -1):
+        x = score[t] + beta[dst]
+        with np.errstate(invalid="ignore"):
+            occ = exp32((alpha[t, src] - logz) + x)
+        g = np.zeros(y.shape[1], f32)
+        np.add.at(g, pdf, np.where(np.isnan(occ), f32(0), occ).astype(f32))
+        post[t] = g * (f32(weight) / g.sum(dtype=f32))
+        beta = log_sum(x, src)
+    return float(logz), post

@@ -68,12 +68,13 @@ def hip_den(fst, y, S, leaky=1e-5, deriv_weight=1.0, l2_scale=0.0, accumulate=Fa
                 graph=graph)
 
 
-def hip_num(sup, y, want_deriv=True, device="cuda:0"):
-    """Runs tc_num_forward_backward; returns dict(logprob_weighted, deriv)."""
-    hsup = io.Supervision.from_synth(sup)
+def hip_num(sup, y, want_deriv=True, device="cuda:0", init=0.0):
+    """Runs tc_num_forward_backward; returns dict(logprob_weighted, deriv).  ``sup``: a ``synth.SupFst`` or a handle
+    (``io.Supervision``, end-to-end ones included); ``init``: what the derivative matrix holds before the call adds to it."""
+    hsup = sup if isinstance(sup, io.Supervision) else io.Supervision.from_synth(sup)
     rows, cols = y.shape
     yt = torch.from_numpy(np.ascontiguousarray(y)).to(device)
-    deriv = torch.zeros(rows, cols, device=device) if want_deriv else None
+    deriv = torch.full((rows, cols), float(init), device=device) if want_deriv else None
     nbytes = 256 * ((hsup.n_batch * 8 + 255) // 256) + 256
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     lp = torch.zeros(1, dtype=torch.float64, device=device)
@@ -161,6 +162,38 @@ def elementwise(got, ref, what, bounds=((1e-3, 1e-4), (1e-4, 1e-3))):
         assert m.any(), (what, floor)
         worst = float((np.abs(got[m] - ref[m]) / np.abs(ref[m])).max())
         assert worst <= tol, (what, "entries above %g: worst relative error %.3g > %g" % (floor, worst, tol))
+
+
+POSTERIOR_CLASSES = (1e-2, 1e-4, 1e-6, 1e-8)
+
+
+def posteriors_elementwise(got, ref, weight, what, rel, small_abs=1e-9):
+    """A numerator's ``weight * posterior`` matrix against its float64 statement ``ref``, entry by entry and with no entry
+    left out: every entry with ref > 1e-8 * weight within ``rel`` relative, every other one within ``small_abs * weight``
+    absolute, exactly 0.0 where ref is exactly 0 (no arc of that frame carries that pdf), every row of got / weight summing
+    to 1 within 1e-5.  The classes ref / weight > 1e-2, > 1e-4, > 1e-6 and > 1e-8 must each be non-empty (as ``elementwise``
+    insists on its own); returns and prints the worst relative error of each."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape and np.isfinite(got).all() and np.isfinite(ref).all(), what
+    assert weight > 0 and (ref >= 0).all(), what
+    relerr = np.abs(got - ref) / np.where(ref > 0, ref, 1.0)
+    worst = {}
+    for floor in POSTERIOR_CLASSES:
+        m = ref > floor * weight
+        assert m.any(), (what, "no entry above %g" % floor)
+        worst[floor] = float(relerr[m].max())
+    small = ~(ref > POSTERIOR_CLASSES[-1] * weight)
+    worst_small = float(np.abs(got - ref)[small].max()) / weight if small.any() else 0.0
+    stray = int(np.count_nonzero(got[ref == 0]))
+    rows = float(np.abs(got.sum(axis=1) / weight - 1.0).max())
+    print("%s: worst relative error %s; others %.2e absolute; %d non-zero where float64 is 0; |row sum - 1| %.2e" % (
+        what, ", ".join(">%g: %.2e" % kv for kv in worst.items()), worst_small, stray, rows))
+    for floor, w in worst.items():
+        assert w <= rel, (what, "entries above %g: worst relative error %.3g > %g" % (floor, w, rel))
+    assert worst_small <= small_abs, (what, "entries up to 1e-8: worst absolute error %.3g > %g" % (worst_small, small_abs))
+    assert stray == 0, (what, "%d entries are non-zero where no arc of the frame carries the pdf" % stray)
+    assert rows <= 1e-5, (what, "a row of posteriors sums to 1 +- %.3g" % rows)
+    return worst
 
 
 def occupy_half_the_cus(stream, millis):

@@ -93,6 +93,8 @@ def lattice_supervision(S, T, num_pdfs, width, fan, seed, weight=1.0, final_weig
                         np.array(aw, np.float32), np.array(nx, np.int32), final)
 
 
+EDGE_WIDTHS = (63, 64, 65, 127, 128, 129, 1)
+
 # name -> (sequences, frames, width(q, t, rng), fan, final weights, supervision weight, expected kernel)
 LATTICE = {
     "lattice_fits": (3, 60, lambda q, t, r: r.integers(20, 41), 3, True, 1.0, RESIDENT),
@@ -103,6 +105,8 @@ LATTICE = {
     "lattice_pinch": (2, 150, lambda q, t, r: 1 if t == 70 else r.integers(60, 101), 3, False, 1.0, WINDOWED),
     # sequences of very different size in one minibatch: one wide, the rest of three states per level
     "lattice_mixed": (4, 150, lambda q, t, r: r.integers(40, 121) if q == 1 else 3, 2, True, 1.0, WINDOWED),
+    # level widths either side of the kernels' lane strides (64 states a pass; 128 arcs and 128 (frame, pdf) entries a pass)
+    "lattice_edge": (2, 21, lambda q, t, r: EDGE_WIDTHS[(t - 1) % len(EDGE_WIDTHS)], 3, True, 0.75, RESIDENT),
 }
 
 CASES = tuple(TRIE) + tuple(LATTICE)
@@ -124,9 +128,9 @@ def supervision(name):
     return lattice_supervision(S, T, P, width, fan, seed=5, weight=weight, final_weights=fw)
 
 
-def nnet_output(name, seed=5):
+def nnet_output(name, seed=5, scale=1.0):
     sup = supervision(name)
-    return synth.random_nnet_output(sup.num_sequences, sup.frames_per_sequence, P, seed=seed)
+    return synth.random_nnet_output(sup.num_sequences, sup.frames_per_sequence, P, seed=seed, scale=scale)
 
 
 def state_times(sup):
