@@ -427,6 +427,52 @@ int tc_chain_step_penalized(tc_den_graph *graph, tc_supervision *supervision, co
                             float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
                             void *stream);
 
+/* Layouts of the tensors of tc_chain_step_strided. */
+#define TC_LAYOUT_ROWS 0         /* 2-D frame-major (T*B, C) with row_stride: three_d == 0 of the entries above */
+#define TC_LAYOUT_BCT 1          /* contiguous (B, C, T), the reference's 3-D input: three_d != 0 */
+#define TC_LAYOUT_CHANNEL_LAST 2 /* a (B, C, T) view with channel stride 1: element (b, c, t) at b*batch_stride + t*frame_stride + c */
+
+/* tc_chain_step_penalized with a layout code in place of three_d, for network outputs that come with their channels last.
+ * The reference's contract is "3-D input is (B, C, T)" (torchain/functions.py:118-125 permutes it to frame-major rows
+ * t*B + b); a batch-first LSTM or Transformer produces (B, T, C) and its user passes out.transpose(1, 2), each half of a
+ * joint chain / xent head is a strided slice out[..., :P] / out[..., P:] of such a tensor.  Those views are
+ * TC_LAYOUT_CHANNEL_LAST: no copy is made contiguous first.
+ *   layout 0, 1 : tc_chain_step_penalized with three_d = layout, argument for argument; batch_stride and frame_stride are
+ *                 not read.
+ *   layout 2    : batch_stride / frame_stride are ELEMENT strides shared by input and xent_input; row_stride is not read.
+ *                 The stride of a dimension of size 1 is ignored.  Otherwise each must be >= num_pdfs and the B * T rows must
+ *                 not overlap: batch_stride >= (T-1)*frame_stride + C (batch-major) or frame_stride >= (B-1)*batch_stride + C
+ *                 (time-major); anything else -- negative, zero, interleaved -- is TC_ERR_INVALID_ARGUMENT, as is a pointer
+ *                 that is not a multiple of the element size, and nothing is written.
+ *                 grad and xent_grad are DENSE (B, T, C) tensors of `dtype`: element (b, c, t) at (b*T + t)*C + c.
+ *   values      : those of tc_chain_step_penalized with three_d != 0 on the contiguous (B, C, T) copy of the same values, bit
+ *                 for bit, for every dtype and option: results_dev3, loss_dev1, xent_objf_dev and every gradient element.
+ *                 One exception, TC_DTYPE_F16 without weights and penalty: where the float32 MMI gradient is exactly +-0 the
+ *                 two may differ in the zero's sign.  Here the float16 element is the rounded float32 value -1 * g on every
+ *                 path; the (B, C, T) copy back fuses the product into the conversion on some of its paths (v_fma_mixlo_f16,
+ *                 whose + 0 addend turns -0 into +0).  Equal values everywhere.
+ *   how         : one gather per input (rows b*batch_stride + t*frame_stride -> contiguous float32 frame-major rows, widened
+ *                 exactly), the float32 2-D computation on those, one scatter per gradient.  The MMI gradient's scatter applies
+ *                 what the (B, C, T) copy back applies, in its order: scale -1; with deriv_weights (-1 * w[row]) * g in one
+ *                 multiply; with the penalty w[row] * (-g + t), reading `input` at the row it writes; one rounding for 16-bit
+ *                 tensors.  It runs behind the soft-failure reset.  The xent gradient's entries are scaled and weighted by
+ *                 the numerator in float32 and only moved (and, for 16 bits, rounded once) by their scatter; the cross-entropy
+ *                 objective sums the unweighted entries.
+ *   scratch     : a float32 step keeps the frame-major xent gradient in the caller's `grad` until the MMI gradient's scatter
+ *                 overwrites it: `grad` and `xent_grad` must be distinct, and neither holds anything else meanwhile.
+ *   grad == NULL: the evaluation step, as in the other entries; the gathers only.
+ * Workspace: tc_chain_step_strided_workspace_bytes(graph, B, T, layout, xent branch, dtype); for layout 2 it equals that of
+ * layout 1.  No host synchronisation, nothing allocated; safe under stream capture.  tc_debug_counter("channel_last_steps")
+ * counts the steps taken in layout 2; their gathers and scatters count as "layout_launches". */
+int64_t tc_chain_step_strided_workspace_bytes(const tc_den_graph *graph, int32_t num_sequences,
+                                              int32_t frames_per_sequence, int layout, int with_xent, int dtype);
+int tc_chain_step_strided(tc_den_graph *graph, tc_supervision *supervision, const void *input, const void *xent_input,
+                          int layout, int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize,
+                          float leaky_hmm_coefficient, float xent_regularize, int kaldi_way, void *grad, void *xent_grad,
+                          float *results_dev3, float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                          float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                          void *stream);
+
 /* The benchmarked unit: [K] DenominatorComputation::Forward() + Backward(deriv_weight, deriv)
  * (direct use in the reference: src/chain-supervision-test.hpp:403-414).
  *   logprob_dev   : device double[1], sum over sequences of the denominator log-prob
@@ -511,6 +557,26 @@ int tc_to2d(const float *in_bct, int32_t B, int32_t C, int32_t T, float *out2d, 
 int tc_from2d(const float *in2d, int64_t in_stride, int32_t B, int32_t C, int32_t T, float scale, float *out_bct,
               int device, void *stream);
 
+/* The counterparts of tc_to2d / tc_from2d for a channel-last view (TC_LAYOUT_CHANNEL_LAST of tc_chain_step_strided; the
+ * permutation of torchain/functions.py:118-125 with the channels already last), on tensors of `dtype` (TC_DTYPE_*):
+ *   out2d[(t*B + b) * out_stride + c] = (float) in[b*batch_stride + t*frame_stride + c]        (an exact widening)
+ * Strides in elements, checked as tc_chain_step_strided checks them.  One wave per row; 16-byte accesses when C, both
+ * strides (4 elements for float32, 8 for 16-bit tensors), out_stride and both base addresses allow them, else element-wise. */
+int tc_rows_gather(const void *in, int dtype, int32_t B, int32_t C, int32_t T, int64_t batch_stride, int64_t frame_stride,
+                   float *out2d, int64_t out_stride, int device, void *stream);
+
+/* The way back into a DENSE (B, T, C) tensor of `dtype`, with what tc_chain_step_strided applies to the MMI gradient:
+ *   out_btc[(b*T + t)*C + c] = round(f(in2d[(t*B + b) * in_stride + c]))
+ *   f(v) = scale * v                                  row_weights == NULL, out_of_range_regularize == 0
+ *        = (scale * w[t*B + b]) * v                   row_weights given: one float32 multiply of v
+ *        = w[t*B + b] * (scale * v + fl32(2c) * p(y)) out_of_range_regularize = c > 0 (w = 1 without row_weights): the penalty
+ *          of tc_chain_step_penalized with y = input[b*batch_stride + t*frame_stride + c]; an element with p(y) == 0 keeps
+ *          the bits of scale * v (times w)
+ * rounded once to nearest even for 16-bit tensors.  input, batch_stride and frame_stride are read only with c > 0. */
+int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, int32_t C, int32_t T, float scale,
+                    const float *row_weights, float out_of_range_regularize, const void *input, int64_t batch_stride,
+                    int64_t frame_stride, void *out_btc, int device, void *stream);
+
 /* Diagnostic, host only: replays one arc walk from the graph's built schedules exactly as the kernels
  * consume them and returns, per state, direction 0: sum over in-arcs (h->g) of w*gather[h]*pdf_factor[pdf],
  * direction 1: sum over out-arcs (h->g) of w*gather[g]*pdf_factor[pdf]  (gather: num_states floats,
@@ -558,7 +624,9 @@ int tc_debug_set(const char *key, int value);
  * "den_long_utterance_launches" = on-chip denominator launches whose frame sums did not fit LDS and went through the
  * workspace (utterances of many hundred frames on the largest on-chip graphs); "num_e2e_staged_launches" = end-to-end
  * numerator launches that ran beside the denominator and left their posteriors for the scatter kernel;
- * "num_windowed_launches" = regular numerator launches that took the level-windowed kernel (counted in "num_launches" too).
+ * "num_windowed_launches" = regular numerator launches that took the level-windowed kernel (counted in "num_launches" too);
+ * "channel_last_steps" = tc_chain_step_strided calls taken in TC_LAYOUT_CHANNEL_LAST (their row gathers and scatters, and
+ * tc_rows_gather / tc_rows_scatter, count as "layout_launches").
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libtorchain_hip.so")
 
 TC_OK = 0
 TC_DTYPE_F32, TC_DTYPE_BF16, TC_DTYPE_F16 = 0, 1, 2  # element types of tc_chain_step_typed
+TC_LAYOUT_ROWS, TC_LAYOUT_BCT, TC_LAYOUT_CHANNEL_LAST = 0, 1, 2  # layouts of tc_chain_step_strided
 ERRORS = {
     -1: "TC_ERR_INVALID_ARGUMENT", -2: "TC_ERR_BAD_FST", -3: "TC_ERR_UNSUPPORTED", -4: "TC_ERR_WORKSPACE",
     -5: "TC_ERR_HIP", -6: "TC_ERR_IO", -7: "TC_ERR_NOT_SEPARABLE",
@@ -145,6 +146,15 @@ def _load():
     L.tc_chain_step_penalized.restype = C.c_int
     L.tc_chain_step_penalized.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, vp,
                                           vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, C.c_int64, C.c_int, vp]
+    L.tc_chain_step_strided_workspace_bytes.restype = C.c_int64
+    L.tc_chain_step_strided_workspace_bytes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_int]
+    L.tc_chain_step_strided.restype = C.c_int
+    L.tc_chain_step_strided.argtypes = [vp, vp, vp, vp, C.c_int, i64, i64, i64, C.c_float, C.c_float, C.c_float, C.c_int, vp,
+                                        vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, C.c_int64, C.c_int, vp]
+    L.tc_rows_gather.restype = C.c_int
+    L.tc_rows_gather.argtypes = [vp, C.c_int, i32, i32, i32, i64, i64, vp, i64, C.c_int, vp]
+    L.tc_rows_scatter.restype = C.c_int
+    L.tc_rows_scatter.argtypes = [vp, i64, C.c_int, i32, i32, i32, f32, vp, f32, vp, i64, i64, vp, C.c_int, vp]
     L.tc_supervision_free.restype = None
     L.tc_supervision_free.argtypes = [vp]
     for name in ("tc_supervision_num_pdf", "tc_supervision_num_sequence", "tc_supervision_num_frame"):

@@ -653,12 +653,23 @@ int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *inp
                                  dtype, workspace, workspace_bytes, device, stream_v);
 }
 
-int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v,
-                            int three_d, int64_t row_stride, float l2_regularize, float leaky, float xent_regularize,
-                            int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1,
-                            double *xent_objf_dev, const float *deriv_weights, float out_of_range_regularize, int dtype,
-                            void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+// The step in every layout (TC_LAYOUT_*).  batch_stride / frame_stride (sb, st): TC_LAYOUT_CHANNEL_LAST only, checked by the
+// caller.  A channel-last step is the float32 2-D step on gathered rows: input (and xent_input) are gathered into contiguous
+// float32 frame-major matrices (launch_rows_gather), the denominator and the numerator run on those exactly as they run on
+// the widened copies of 16-bit 2-D tensors, with the plain derivative in the scratch as for (B, C, T), and one scatter per
+// gradient (launch_rows_scatter) applies what the (B, C, T) copy back applies -- sign, row weight, penalty, the one rounding --
+// behind chain_objf's soft-failure reset.  The 2-D xent gradient needs one more float32 matrix than the (B, C, T) step has:
+// for 16-bit tensors that is the float32 xent scratch the (B, C, T) step has anyway; for float32 it is the caller's `grad`,
+// which has exactly that size and is written last, by the MMI gradient's scatter.
+static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
+                             int64_t row_stride, int64_t sb, int64_t st, float l2_regularize, float leaky,
+                             float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
+                             float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                             float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                             void *stream_v) {
   if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  const bool cl = layout == TC_LAYOUT_CHANNEL_LAST;  // (rows gathered and scattered: everything between is 2-D scratch)
+  const int three_d = layout != TC_LAYOUT_ROWS;
   if (((uintptr_t)deriv_weights & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
   if (!(out_of_range_regularize >= 0.0f) || std::isinf(out_of_range_regularize)) return TC_ERR_INVALID_ARGUMENT;
   // (16-bit tensors travel as float pointers up to the kernels that read or write them: NumParams::elem, launch_to2d)
@@ -678,7 +689,7 @@ int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *in
   const int64_t rows = (int64_t)S * T;
   if (!three_d && row_stride < P) return TC_ERR_INVALID_ARGUMENT;
   // (tc_from2d's limits; the float32 unweighted call meets them in tc_from2d itself)
-  if ((half || deriv_weights || out_of_range_regularize > 0.0f) && three_d && (S > 65535 || (T + 239) / 240 > 65535))
+  if ((half || deriv_weights || out_of_range_regularize > 0.0f) && three_d && !cl && (S > 65535 || (T + 239) / 240 > 65535))
     return TC_ERR_UNSUPPORTED;
   // Kaldi's deriv_weights ([K] nnet-chain-training.cc: MulRowsVec on both derivatives, after the objectives are formed):
   // ignored by an evaluation step, which writes no gradient.  Every gradient element becomes w[row] * g, one float32
@@ -713,8 +724,24 @@ int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *in
   // here; what remains of the first is this library's own extra, the cross-entropy objective, which is defined on the
   // first call's xent_deriv: the numerator alone on `input` (no denominator, nothing written but the sequences' sums).
   const bool second_only = use_xent && !kaldi_way;
-  const int bct = three_d && use_xent ? 1 : 0;
-  if (three_d) {
+  const int bct = three_d && !cl && use_xent ? 1 : 0;
+  if (cl) {
+    if (!channel_last_strides_ok(S, T, P, sb, st)) return TC_ERR_INVALID_ARGUMENT;
+    DeviceGuard guard(device);
+    if (!guard.ok) return TC_ERR_HIP;
+    // (the chain output's rows are read by the objective, or with kaldi_way == 0 by the numerator-only pass alone)
+    if (!second_only || xent_objf_dev) rc = launch_rows_gather(dtype, input, sb, st, w.y2d, P, S, T, P, stream);
+    if (rc == TC_OK && use_xent) rc = launch_rows_gather(dtype, xent_input, sb, st, w.x2d, P, S, T, P, stream);
+    if (rc != TC_OK) return rc;
+    count_launch(kCntChannelLast);
+    y = second_only ? w.x2d : w.y2d;
+    gr = eval_only ? nullptr : w.g2d;
+    xg = use_xent && !eval_only ? (half ? w.xg : grad) : nullptr;  // (float32: the caller's grad, until its scatter fills it)
+    stride = P;
+    num_in = w.y2d;
+    xent_in = w.x2d;
+    num_stride = xent_stride = P;
+  } else if (three_d) {
     y = second_only ? w.x2d : w.y2d;  // (filled inside chain_objf, beside the numerator: bct_input)
     gr = eval_only ? nullptr : w.g2d;
     // (16-bit: the numerator writes the float32 scratch, rounded into the caller's tensor at the end)
@@ -755,12 +782,12 @@ int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *in
     NumParams np;
     rc = fill_num_params(sup, device, stream, num_in, rows, P, num_stride, nullptr, 0, nullptr, 0, wi.num_lp, &np);
     if (rc != TC_OK) return rc;
-    np.y_bct = three_d ? 1 : 0;
-    np.elem = three_d ? dtype : TC_DTYPE_F32;
+    np.y_bct = three_d && !cl ? 1 : 0;
+    np.elem = three_d && !cl ? dtype : TC_DTYPE_F32;
     np.xent_scale = xscale;
     np.xent_out = xent_in;
     np.xent_out_stride = xent_stride;
-    np.xent_out_bct = three_d ? 1 : 0;
+    np.xent_out_bct = three_d && !cl ? 1 : 0;
     np.seq_xent = wi.xent_lp;
     rc = launch_num(np, stream);
     if (rc == TC_OK) rc = supervision_mark_use(sup, device, stream);
@@ -768,9 +795,23 @@ int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *in
   }
   rc = chain_objf(g, sup, y, rows, P, stride, results_dev3, gr, gstride, xg, gstride, l2_regularize, leaky, dscale, xscale,
                   w.chain, (int64_t)w.chain_bytes, device, stream_v, use_xent && !second_only ? xent_in : nullptr, xent_stride,
-                  use_xent ? xent_objf_dev : nullptr, bct, bct, three_d ? (second_only ? xent_input : input) : nullptr,
-                  second_only && xent_objf_dev != nullptr, loss_dev1, dtype, row_w);
+                  use_xent ? xent_objf_dev : nullptr, bct, bct,
+                  three_d && !cl ? (second_only ? xent_input : input) : nullptr, second_only && xent_objf_dev != nullptr,
+                  loss_dev1, dtype, row_w);
   if (rc != TC_OK) return rc;
+  if (cl) {
+    if (eval_only) return rc;
+    // the way out: dense (B, T, C) gradients of the input's type.  The xent gradient first -- for float32 it lies in `grad`
+    // -- as the numerator left it (scaled and weighted); then the MMI gradient, as the (B, C, T) copy back forms it:
+    // (-1 * w[row]) * g in one multiply, penalised w[row] * (-g + t), reading `input` at the row it writes.
+    DeviceGuard guard(device);
+    if (!guard.ok) return TC_ERR_HIP;
+    const int64_t dense_b = (int64_t)T * P;
+    if (xg) rc = launch_rows_scatter(dtype, xg, P, xent_grad, dense_b, P, nullptr, 0, 0, S, T, P, false, 1.0f, 0.0f, nullptr, stream);
+    if (rc == TC_OK)
+      rc = launch_rows_scatter(dtype, gr, P, grad, dense_b, P, input, sb, st, S, T, P, true, -1.0f, pen_c2, row_w, stream);
+    return rc;
+  }
   if (three_d && !eval_only && !half) {
     if (row_w || pen_c2 > 0.0f) {
       DeviceGuard guard(device);
@@ -805,6 +846,66 @@ int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *in
     if (rc == TC_OK && xg) rc = launch_round(dtype, xg, xent_grad, rows * P, stream);
   }
   return rc;  // (the loss value -objf / weight was written with the results: finalize_kernel)
+}
+
+int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v,
+                            int three_d, int64_t row_stride, float l2_regularize, float leaky, float xent_regularize,
+                            int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1,
+                            double *xent_objf_dev, const float *deriv_weights, float out_of_range_regularize, int dtype,
+                            void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  return chain_step_layout(g, sup, input_v, xent_input_v, three_d ? TC_LAYOUT_BCT : TC_LAYOUT_ROWS, row_stride, 0, 0,
+                           l2_regularize, leaky, xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1,
+                           xent_objf_dev, deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes, device,
+                           stream_v);
+}
+
+int64_t tc_chain_step_strided_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T, int layout, int with_xent,
+                                              int dtype) {
+  if (layout != TC_LAYOUT_ROWS && layout != TC_LAYOUT_BCT && layout != TC_LAYOUT_CHANNEL_LAST) return TC_ERR_INVALID_ARGUMENT;
+  return tc_chain_step_typed_workspace_bytes(g, S, T, layout != TC_LAYOUT_ROWS, with_xent, dtype);
+}
+
+int tc_chain_step_strided(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
+                          int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize, float leaky,
+                          float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
+                          float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                          float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                          void *stream_v) {
+  if (layout == TC_LAYOUT_ROWS || layout == TC_LAYOUT_BCT)
+    return tc_chain_step_penalized(g, sup, input_v, xent_input_v, layout == TC_LAYOUT_BCT, row_stride, l2_regularize, leaky,
+                                   xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev,
+                                   deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v);
+  if (layout != TC_LAYOUT_CHANNEL_LAST || !sup) return TC_ERR_INVALID_ARGUMENT;
+  if (!channel_last_strides_ok(sup->S, sup->T, sup->P, batch_stride, frame_stride)) return TC_ERR_INVALID_ARGUMENT;
+  // (element offsets are multiples of the element size: a base that is not breaks every access)
+  const uintptr_t elem_mask = dtype == TC_DTYPE_F32 ? 3 : 1;
+  if ((((uintptr_t)input_v | (uintptr_t)xent_input_v | (uintptr_t)grad_v | (uintptr_t)xent_grad_v) & elem_mask) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  return chain_step_layout(g, sup, input_v, xent_input_v, layout, 0, batch_stride, frame_stride, l2_regularize, leaky,
+                           xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev,
+                           deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v);
+}
+
+int tc_rows_gather(const void *in, int dtype, int32_t B, int32_t Cn, int32_t T, int64_t batch_stride, int64_t frame_stride,
+                   float *out2d, int64_t out_stride, int device, void *stream_v) {
+  if (!in || !out2d || !known_dtype(dtype) || B <= 0 || Cn <= 0 || T <= 0 || out_stride < Cn) return TC_ERR_INVALID_ARGUMENT;
+  if (!channel_last_strides_ok(B, T, Cn, batch_stride, frame_stride)) return TC_ERR_INVALID_ARGUMENT;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  return launch_rows_gather(dtype, in, batch_stride, frame_stride, out2d, out_stride, B, T, Cn, (hipStream_t)stream_v);
+}
+
+int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, int32_t Cn, int32_t T, float scale,
+                    const float *row_weights, float out_of_range_regularize, const void *input, int64_t batch_stride,
+                    int64_t frame_stride, void *out_btc, int device, void *stream_v) {
+  if (!in2d || !out_btc || !known_dtype(dtype) || B <= 0 || Cn <= 0 || T <= 0 || in_stride < Cn) return TC_ERR_INVALID_ARGUMENT;
+  if (!(out_of_range_regularize >= 0.0f) || std::isinf(2.0f * out_of_range_regularize)) return TC_ERR_INVALID_ARGUMENT;
+  const float pen_c2 = 2.0f * out_of_range_regularize;
+  if (pen_c2 > 0.0f && (!input || !channel_last_strides_ok(B, T, Cn, batch_stride, frame_stride))) return TC_ERR_INVALID_ARGUMENT;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  return launch_rows_scatter(dtype, in2d, in_stride, out_btc, (int64_t)T * Cn, Cn, input, batch_stride, frame_stride, B, T, Cn,
+                             true, scale, pen_c2, row_weights, (hipStream_t)stream_v);
 }
 
 int tc_xent_objf(const float *xent_output, int64_t rows, int32_t cols, int64_t output_stride, const float *xent_deriv,

@@ -553,6 +553,19 @@ int launch_round_penalized(int dtype, const float *in, void *out, int64_t n, con
                            int cols, hipStream_t stream);
 int launch_penalize_rows(float *a, int64_t rows, int cols, const float *y, int64_t y_stride, float pen_c2,
                          const float *row_w, hipStream_t stream);
+// layout_rows_kernels.hip (tc_chain_step_strided, TC_LAYOUT_CHANNEL_LAST): the row copies of a channel-last view, element
+// (b, c, t) at b*sb + t*st + c in a tensor of `dtype`.  Strides of size-1 dimensions are ignored; rows must not overlap.
+bool channel_last_strides_ok(int B, int T, int cols, int64_t sb, int64_t st);
+// out[(t*B + b) * out_stride + c] = widen(x[b*sb + t*st + c])
+int launch_rows_gather(int dtype, const void *x, int64_t sb, int64_t st, float *out, int64_t out_stride, int B, int T, int cols,
+                       hipStream_t stream);
+// out[b*osb + t*ost + c] = in[(t*B + b) * in_stride + c] on its way out as the (B, C, T) copy back sends it (launch_from2d /
+// launch_from2d_penalized, operation for operation), rounded once: !scaled: as it is; scaled: scale * v, or with row_w
+// (scale * row_w[row]) * v; pen_c2 > 0 (scaled only): row_w[row] * penalize(scale * v, y) with y the element b*ysb + t*yst + c
+// of the network output `y` (of `dtype`).
+int launch_rows_scatter(int dtype, const float *in, int64_t in_stride, void *out, int64_t osb, int64_t ost, const void *y,
+                        int64_t ysb, int64_t yst, int B, int T, int cols, bool scaled, float scale, float pen_c2,
+                        const float *row_w, hipStream_t stream);
 
 extern thread_local int g_last_hip_error;
 
@@ -569,7 +582,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

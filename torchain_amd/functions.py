@@ -30,6 +30,13 @@ Same names, argument meaning, defaults and quirks as the reference:
   supervision's weight, in front of ``deriv_weights``.  ``results``, the loss, ``xent_objf`` and the xent gradient do not
   change; without a gradient the option does nothing.  ``0.0`` (the default, not Kaldi's 0.01) keeps the reference's
   behaviour.  The one call adds it in the passes it makes anyway (``tc_chain_step_penalized``).
+* channel-last views: a 3-D input is still ``(B, C, T)``, but a view of that shape whose channel stride is 1 -- a batch-first
+  model's ``out.transpose(1, 2)``, PyTorch's time-major ``out.permute(1, 2, 0)``, the two halves ``out[..., :P]`` /
+  ``out[..., P:]`` of a joint head -- takes the one call as it is (``classify_layout``, ``tc_chain_step_strided``): a
+  time-major view IS the 2-D layout and is passed as such, without a copy; any other one is gathered and its gradients
+  scattered by the library, one pass each.  Values: bit for bit those of the call on ``input.contiguous()`` (float16: up to
+  the sign of an exactly zero gradient element, where the view gives the float32 gradient's ``.to(float16)``).  ``xent_input``
+  must be a view with the same strides (or absent); any other combination takes the routes it took before.
 """
 import ctypes as C
 import inspect
@@ -38,7 +45,8 @@ import torch
 from torch.autograd import Function
 
 from . import io
-from ._lib import TC_DTYPE_BF16, TC_DTYPE_F16, TC_DTYPE_F32, check, lib
+from ._lib import (TC_DTYPE_BF16, TC_DTYPE_F16, TC_DTYPE_F32, TC_LAYOUT_BCT, TC_LAYOUT_CHANNEL_LAST, TC_LAYOUT_ROWS, check,
+                   lib)
 
 # element types tc_chain_step(_typed) takes as they are
 _STEP_DTYPES = {torch.float32: TC_DTYPE_F32, torch.bfloat16: TC_DTYPE_BF16, torch.float16: TC_DTYPE_F16}
@@ -434,12 +442,12 @@ class _ChainStep(Function):
 
 def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
               xent_regularize, kaldi_way, want_grad, deriv_weights=None, out_of_range_regularize=0.0):
-    """One ``tc_chain_step_penalized``.  ``want_grad=False`` is the evaluation step (``grad == NULL``): forward recursions
-    only, no gradient tensors -- [K] ``ComputeChainObjfAndDeriv`` with ``nnet_output_deriv == NULL``; ``deriv_weights``
+    """One ``tc_chain_step_strided``, in the layout ``classify_layout`` finds (a time-major view as the 2-D rows it is;
+    gradients of channel-last views come back as views of dense tensors).  ``want_grad=False`` is the evaluation step
+    (``grad == NULL``): forward recursions only, no gradient tensors -- [K] ``ComputeChainObjfAndDeriv`` with ``nnet_output_deriv == NULL``; ``deriv_weights``
     (checked by ``_deriv_weights``) are then not passed on, and ``out_of_range_regularize`` (checked by ``_out_of_range``)
     has nothing to act on."""
     device = input.device
-    three_d = input.dim() == 3
     use_xent = xent_input is not None and xent_regularize != 0.0
     if isinstance(den_graph, io.DenominatorGraph):
         den_graph.prepare(device)
@@ -450,7 +458,7 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         sup_ptr = supervision
         S, T, P = (lib.tc_supervision_num_sequence(sup_ptr), lib.tc_supervision_num_frame(sup_ptr),
                    lib.tc_supervision_num_pdf(sup_ptr))
-    want = (S, P, T) if three_d else (S * T, P)
+    want = (S, P, T) if input.dim() == 3 else (S * T, P)
     if tuple(input.shape) != want or (use_xent and tuple(xent_input.shape) != want):
         raise ValueError("nnet output of shape %s does not match the supervision (%s expected)" % (tuple(input.shape), want))
     x = input.detach()
@@ -458,20 +466,31 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
     dtype = _STEP_DTYPES[x.dtype]
     if xe is not None and xe.dtype != x.dtype:
         raise ValueError("input and xent_input must have the same dtype (%s, %s)" % (x.dtype, xe.dtype))
-    grad = torch.empty_like(x, memory_format=torch.contiguous_format) if want_grad else None
-    xgrad = torch.empty_like(xe, memory_format=torch.contiguous_format) if use_xent and want_grad else None
+    kind, s0, s1 = _layout(x)
+    if kind == "other" or (xe is not None and _layout(xe)[0] != kind):
+        raise ValueError("input and xent_input must come in one layout the step takes (%s, %s)"
+                         % (tuple(x.stride()), tuple(xe.stride()) if xe is not None else None))
+    if kind in ("time_major", "channel_last") and xe is not None and _layout(xe) != (kind, s0, s1):
+        raise ValueError("input and xent_input must be views with the same strides (%s, %s)"
+                         % (tuple(x.stride()), tuple(xe.stride())))
+    if kind == "time_major":  # the 2-D layout where it lies: row t*S + s at (t*S + s) * s0
+        x = x.as_strided((S * T, P), (s0, 1))
+        xe = xe.as_strided((S * T, P), (s0, 1)) if xe is not None else None
+    layout = {"rows": TC_LAYOUT_ROWS, "time_major": TC_LAYOUT_ROWS, "bct": TC_LAYOUT_BCT}.get(kind, TC_LAYOUT_CHANNEL_LAST)
+    row_stride = x.stride(0) if layout == TC_LAYOUT_ROWS else 0
+    # (gradients: contiguous in the 2-D and the (B, C, T) layout; dense (B, T, C) for a channel-last view)
+    gshape = {TC_LAYOUT_ROWS: (S * T, P), TC_LAYOUT_BCT: (S, P, T), TC_LAYOUT_CHANNEL_LAST: (S, T, P)}[layout]
+    grad = torch.empty(gshape, dtype=x.dtype, device=device) if want_grad else None
+    xgrad = torch.empty(gshape, dtype=x.dtype, device=device) if use_xent and want_grad else None
     with torch.cuda.device(device):
         cur = torch.cuda.current_stream(device)
-        key = (S, T, three_d, use_xent, dtype)
+        key = (S, T, layout != TC_LAYOUT_ROWS, use_xent, dtype)  # (a channel-last step has the (B, C, T) step's workspace)
         sizes = den_graph.__dict__.setdefault("_step_bytes", {}) if isinstance(den_graph, io.DenominatorGraph) else {}
         nbytes = sizes.get(key)
         if nbytes is None:
-            if dtype == TC_DTYPE_F32:
-                nbytes = lib.tc_chain_step_workspace_bytes(den_ptr, S, T, int(three_d), int(use_xent))
-            else:
-                nbytes = lib.tc_chain_step_typed_workspace_bytes(den_ptr, S, T, int(three_d), int(use_xent), dtype)
+            nbytes = lib.tc_chain_step_strided_workspace_bytes(den_ptr, S, T, layout, int(use_xent), dtype)
             if nbytes < 0:
-                check(int(nbytes), "tc_chain_step_workspace_bytes")
+                check(int(nbytes), "tc_chain_step_strided_workspace_bytes")
             sizes[key] = nbytes
         capturing = torch.cuda.is_current_stream_capturing()
         # (inside a graph capture the workspace comes from the graph's own pool and lives as long as the graph does)
@@ -479,15 +498,16 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         # (a CPU vector is copied here; a float32 CUDA vector is read where it lies, so a replay reads its current values)
         w = _weights_on(deriv_weights, device) if want_grad else None
         out = torch.empty(6, dtype=torch.float32, device=device)  # objf, l2_term, weight | loss | xent objective (f64)
-        args = (den_ptr, sup_ptr, _ptr(x), _ptr(xe), int(three_d), 0 if three_d else x.stride(0), float(l2_regularize),
+        cl = layout == TC_LAYOUT_CHANNEL_LAST
+        args = (den_ptr, sup_ptr, _ptr(x), _ptr(xe), layout, row_stride, s0 if cl else 0, s1 if cl else 0, float(l2_regularize),
                 float(leaky_hmm_coefficient), float(xent_regularize), int(bool(kaldi_way)), _ptr(grad), _ptr(xgrad),
                 C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 12),
                 C.c_void_p(out.data_ptr() + 16) if use_xent else None)
         tail = (_ptr(ws), ws.numel(), device.index, C.c_void_p(cur.cuda_stream))
         # (float32, NULL weights and no penalty: tc_chain_step itself; bfloat16 / float16 are widened on the way in and
         # their gradients rounded once on the way out)
-        check(lib.tc_chain_step_penalized(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail),
-              "tc_chain_step_penalized")
+        check(lib.tc_chain_step_strided(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail),
+              "tc_chain_step_strided")
         results._dev = out[:3]
         results._stale = True
         results._ready = None
@@ -501,17 +521,90 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
             results._xent_ready = results._ready
             results._xent_scale = 1.0 / -float(xent_regularize)  # (the library's sum is of the scaled gradient, both layouts)
             results._xent_host = None
+    if want_grad and kind == "time_major":  # (T*S, C) rows back in the shape of the view they answer
+        grad = grad.view(T, S, P).permute(1, 2, 0)
+        xgrad = xgrad.view(T, S, P).permute(1, 2, 0) if xgrad is not None else None
+    elif want_grad and layout == TC_LAYOUT_CHANNEL_LAST:
+        grad = grad.transpose(1, 2)
+        xgrad = xgrad.transpose(1, 2) if xgrad is not None else None
     return out, grad, xgrad
 
 
+_OTHER = ("other", 0, 0)
+
+
+def classify_layout(shape, strides):
+    """Host only: the layout of a network output of ``shape`` with element ``strides`` (sequences of ints: works for CPU
+    tensors, numpy shapes, anything), as ``(kind, s0, s1)``:
+
+    * ``("rows", row_stride, 0)``: 2-D frame-major ``(T*B, C)`` with unit column stride and ``row_stride >= C``.
+    * ``("bct", 0, 0)``: contiguous ``(B, C, T)`` -- checked first among the 3-D cases, so it is always this.
+    * ``("time_major", row_stride, 0)``: a ``(B, C, T)`` view with channel stride 1 whose rows ``t*B + b`` lie at
+      ``(t*B + b) * row_stride``: ``(T, B, C).permute(1, 2, 0)`` and its last-dimension slices.  It is the 2-D layout.
+    * ``("channel_last", batch_stride, frame_stride)``: any other ``(B, C, T)`` view with channel stride 1, element
+      ``(b, c, t)`` at ``b*batch_stride + t*frame_stride + c``, whose rows do not overlap (``tc_chain_step_strided``'s
+      rule): ``(B, T, C).transpose(1, 2)``, its slices along any dimension.
+    * ``("other", 0, 0)``: everything else -- a channel stride that is not 1, zero or negative strides, overlapping rows
+      (``expand``), other ranks, empty tensors.
+
+    The stride of a dimension of size 1 is ignored."""
+    shape, strides = tuple(int(n) for n in shape), tuple(int(n) for n in strides)
+    if len(shape) != len(strides) or any(n <= 0 for n in shape):
+        return _OTHER
+    if len(shape) == 2:
+        return ("rows", strides[0], 0) if strides[1] == 1 and strides[0] >= shape[1] else _OTHER
+    if len(shape) != 3:
+        return _OTHER
+    B, Cn, T = shape
+    sb, sc, st = strides
+    if (T == 1 or st == 1) and (Cn == 1 or sc == T) and (B == 1 or sb == Cn * T):
+        return ("bct", 0, 0)
+    if Cn > 1 and sc != 1:
+        return _OTHER
+    if (B > 1 and sb < Cn) or (T > 1 and st < Cn):
+        return _OTHER
+    if B == 1 or T == 1:  # one run of rows: 2-D whatever the other stride says
+        return ("time_major", Cn if B == T else (st if B == 1 else sb), 0)
+    if st == B * sb:
+        return ("time_major", sb, 0)
+    if sb >= (T - 1) * st + Cn or st >= (B - 1) * sb + Cn:
+        return ("channel_last", sb, st)
+    return _OTHER
+
+
+def _layout(x):
+    return classify_layout(x.shape, x.stride())
+
+
+def _step_tensor(x):
+    return x.is_cuda and x.dtype in _STEP_DTYPES
+
+
 def _one_call(x):
-    """Tensors ``tc_chain_step`` takes as they are: CUDA float32 (or bfloat16 / float16: ``tc_chain_step_typed``),
-    (B, C, T) contiguous or 2-D with unit column stride."""
-    if x is None:
-        return True
-    if not (x.is_cuda and x.dtype in _STEP_DTYPES):
-        return False
-    return (x.dim() == 3 and x.is_contiguous()) or (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1])
+    """Tensors the step takes in the reference's own two layouts (``classify_layout``: ``rows`` or ``bct``): CUDA float32
+    (or bfloat16 / float16), (B, C, T) contiguous or 2-D with unit column stride.  (What the registered operator accepts.)"""
+    return x is None or (_step_tensor(x) and _layout(x)[0] in ("rows", "bct"))
+
+
+def _step_view(x):
+    """... or in any layout ``tc_chain_step_strided`` takes as it is: those two, or a channel-last view of a (B, C, T) shape."""
+    return x is None or (_step_tensor(x) and _layout(x) != _OTHER)
+
+
+def _step_plan(input, xent_input):
+    """The layout ``(kind, s0, s1)`` in which ``input`` and ``xent_input`` go to the one call together, or None when they
+    do not: 2-D rows with one row stride, two contiguous (B, C, T) tensors, or two channel-last views of one shape with the
+    same two strides (a joint head split in two)."""
+    if not _step_view(input) or not _step_view(xent_input):
+        return None
+    a = _layout(input)
+    if xent_input is None:
+        return a
+    if _layout(xent_input) != a:
+        return None
+    if a[0] in ("time_major", "channel_last") and tuple(xent_input.shape) != tuple(input.shape):
+        return None
+    return a
 
 
 def _needs_grad(input, xent_input):
@@ -520,13 +613,17 @@ def _needs_grad(input, xent_input):
     return input.requires_grad or (xent_input is not None and xent_input.requires_grad)
 
 
-def _as_step_input(x):
-    """A tensor ``tc_chain_step`` takes as it is (evaluation steps only: nothing flows back, so a copy is harmless)."""
-    assert x.is_cuda, "Only CUDA implementation is available"
-    x = x.detach()
-    if x.dtype not in _STEP_DTYPES:
-        x = x.float()
-    return x if _one_call(x) else x.contiguous()
+def _as_step_input(x, xe=None):
+    """Tensors ``tc_chain_step`` takes as they are (evaluation steps only: nothing flows back, so a copy is harmless).  A
+    pair of channel-last views with the same strides stays as it is; otherwise a view is copied."""
+    def one(t):
+        assert t.is_cuda, "Only CUDA implementation is available"
+        t = t.detach()
+        return t if t.dtype in _STEP_DTYPES else t.float()
+    x, xe = one(x), (one(xe) if xe is not None else None)
+    if _step_plan(x, xe) is not None:
+        return x, xe
+    return (x if _one_call(x) else x.contiguous()), (xe if _one_call(xe) else xe.contiguous())
 
 
 def _same_dtype(input, xent_input):
@@ -540,7 +637,9 @@ def _same_dtype(input, xent_input):
 def _half_one_call(input, xent_input):
     """16-bit CUDA inputs in a layout ``tc_chain_step_typed`` does not take as it is: made contiguous (tracked by autograd)
     so that the step is still one call; up-cast to float32 when even that does not fit (a 3-D input with a 2-D
-    ``xent_input``)."""
+    ``xent_input``).  Channel-last views that go to the one call together stay as they are."""
+    if _step_plan(input, xent_input) is not None:
+        return input, xent_input
     input = input if _one_call(input) else input.contiguous()
     if xent_input is not None:
         xent_input = xent_input if _one_call(xent_input) else xent_input.contiguous()
@@ -588,14 +687,13 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
     if not _needs_grad(input, xent_input):  # (deriv_weights and the penalty: checked above, not used without a gradient)
         # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the
         # forward recursions only.  The reference has no such check (functions.py:74,82) and pays for a training step.
-        x, xe = _as_step_input(input), (_as_step_input(xent_input) if xent_input is not None else None)
+        x, xe = _as_step_input(input, xent_input)
         out, _, _ = _run_step(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
                               xent_regularize, kaldi_way, want_grad=False)
         return (input.new_zeros(1) if results._defer_host_copy else out[3:4].to(input.dtype)), results
     if input.is_cuda and input.dtype in _HALF:
         input, xent_input = _half_one_call(input, xent_input)
-    if (_one_call(input) and _one_call(xent_input) and (xent_input is None or xent_input.dim() == input.dim())
-            and (xent_input is None or xent_input.dim() == 3 or xent_input.stride(0) == input.stride(0))):
+    if _step_plan(input, xent_input) is not None:
         loss = _ChainStep.apply(input, xent_input, results, den_graph, supervision,
                                 l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights, c)
         return loss, results
