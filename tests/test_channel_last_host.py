@@ -100,8 +100,12 @@ def test_pairs_that_go_together_and_pairs_that_do_not():
     assert _kind(lo) == _kind(hi) and _kind(lo)[0] == "channel_last"
     dense = torch.zeros(B, T, P).transpose(1, 2)
     assert _kind(dense) != _kind(lo)
+    geo = lambda t: (tuple(t.shape), tuple(t.stride()))  # noqa: E731
+    assert functions.pair_layout(geo(lo), geo(hi)) == _kind(lo) == functions.pair_layout(geo(lo))
+    assert functions.pair_layout(geo(dense), geo(lo)) is None and functions.pair_layout(geo(lo), geo(dense)) is None
+    assert functions.pair_layout(geo(lo), geo(hi[:2])) is None  # (the same strides, another shape)
     assert functions._step_plan(lo, hi) is None and not functions._one_call(lo)  # CPU tensors are never taken
-    assert not functions._step_view(lo)
+    assert not functions._step_view(lo) and functions._step_plan(lo, None) is None
 
 
 def test_numpy_statement_of_gather_and_scatter():

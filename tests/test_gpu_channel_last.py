@@ -406,10 +406,15 @@ def test_soft_failure(dtype, kaldi_way):
 
 # ---- 8. mixed inputs keep their routes and their values -----------------------------------------------------------------
 def test_mixed_inputs_take_the_routes_they_took():
-    """Pairs that do not go to the step together keep their routes: float32 3-D pairs go through ``_ChainLoss3d`` (held here to
-    that class called directly on the contiguous copies, which is what it makes of a view), 16-bit pairs are made contiguous
-    and take the one call (held to the one call on the contiguous copies).  No channel-last step is counted."""
-    from torchain_amd.functions import ChainResults, _ChainLoss3d
+    """Pairs that do not go to the step together are made contiguous and take the one call: all five outputs are bit for bit
+    those of ``chain_loss`` on the contiguous copies (what the planner makes of them).  float32 pairs, which went through
+    ``_ChainLoss3d`` before, are held to that class as well, called directly on the contiguous copies: ``results`` and both
+    gradients bit for bit (but for the sign of the xent gradient's exact zeros: ``torch.equal``, as
+    ``test_one_call_step_equals_the_multi_call_wrappers`` compares the two routes), ``loss`` and ``xent_objf`` within the 1e-6
+    relative the two routes are documented to differ by.
+    No channel-last step is counted."""
+    from composed_step import _ChainLoss3d
+    from torchain_amd.functions import ChainResults
     P, B, T = 20, 3, 5
     s = _workload(P, B, T)
     w = _weights(B * T, 9)
@@ -425,14 +430,28 @@ def test_mixed_inputs_take_the_routes_they_took():
         steps = _counter(b"channel_last_steps")
         got = _call(x, xe, s["graph"], s["sup"], True, w=w, c=0.25)
         assert _counter(b"channel_last_steps") == steps, what
+        gx, gxe = leaves()
+        ops = functions.plan_step_inputs(functions._spec(x), functions._spec(xe))
+        assert set(ops[0] + ops[1]) == {"contiguous"} and ops[2] == ("bct", 0, 0), (what, ops)
         xc, xec = x.detach().contiguous().requires_grad_(True), xe.detach().contiguous().requires_grad_(True)
-        want = _call(xc, xec, s["graph"], s["sup"], True, w=w, c=0.25, fn=through_3d if dtype == torch.float32 else chain_loss)
+        want = _call(xc, xec, s["graph"], s["sup"], True, w=w, c=0.25)  # the normalised copies
         _same_bits(got[0], want[0], what + ": loss")
         _same_bits(got[1], want[1], what + ": results")
         assert got[2] == want[2], what
-        gx, gxe = leaves()
         _same_bits(gx, xc.grad, what + ": grad")
         _same_bits(gxe, xec.grad, what + ": xent grad")
+        if dtype != torch.float32:
+            return
+        xc, xec = x.detach().contiguous().requires_grad_(True), xe.detach().contiguous().requires_grad_(True)
+        want = _call(xc, xec, s["graph"], s["sup"], True, w=w, c=0.25, fn=through_3d)  # the composed step
+        _same_bits(got[1], want[1], what + ": results, composed")
+        _same_bits(gx, xc.grad, what + ": grad, composed")
+        # (where the numerator has no posterior the one call leaves the +0 it cleared the gradient with; _ChainLoss3d scaled
+        # that zero by -xent_regularize on its way back: -0.  Every other element has the same bits.)
+        differ = _bits(gxe) != _bits(xec.grad)
+        assert torch.equal(gxe, xec.grad) and not bool((gxe.cpu()[differ] != 0).any()), what + ": xent grad, composed"
+        assert abs(float(got[0]) - float(want[0])) <= 1e-6 * abs(float(want[0])), (what, got[0], want[0])
+        assert abs(got[2] - want[2]) <= 1e-6 * abs(want[2]), (what, got[2], want[2])
 
     def bct(rows, dtype):
         return torch.as_tensor(rows).reshape(T, B, P).permute(1, 2, 0).to(DEV).to(dtype).contiguous()

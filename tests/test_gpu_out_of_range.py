@@ -223,10 +223,18 @@ def test_c3_step():
     _check(graph, sup, S, T, y, None, torch.float32, "2d", None, l2=cfg["l2"], leaky=cfg["leaky"])
 
 
-# ---- the routes that do not take the one call ---------------------------------------------------------------------------
+# ---- the pairs that are normalised in front of the one call -------------------------------------------------------------
+def _close(a, b, what):
+    assert abs(float(a) - float(b)) <= 1e-6 * abs(float(b)), (what, float(a), float(b))
+
+
 def test_fallback_routes_agree_bit_for_bit():
-    """Mixed dimensions / strides go through to2d() and _ChainLoss, float32 (B, C, T) with a 2-D xent_input likewise; a
-    non-contiguous (B, C, T) view goes through _ChainLoss3d: the same g' as the one call gives on the same values."""
+    """2-D tensors of different row strides and a (B, C, T) view whose channel stride is not 1 are made contiguous and take
+    the one call: the same g' as the one call gives on the same values -- all five outputs bit for bit those of chain_loss
+    on the contiguous copies.  They went through to2d() and _ChainLoss, and through _ChainLoss3d: results and both
+    gradients are bit for bit those of these composed classes (tests/composed_step.py), loss and xent_objf within the 1e-6
+    relative the two routes are documented to differ by."""
+    from composed_step import chain_loss_composed
     s = _small("MEDIUM", "sparse")
     S, T, g, sup = s["S"], s["T"], s["graph"], s["sup"]
     kw = dict(l2_regularize=1e-3, leaky_hmm_coefficient=1e-5, xent_regularize=0.1, kaldi_way=True)
@@ -238,6 +246,17 @@ def test_fallback_routes_agree_bit_for_bit():
         for key, (ww, cc) in dict(plain=(None, 0.0), on=(None, c), both=(w, c)).items():
             a, b = _layout(s["y"], S, T, "2d", torch.float32), _layout(s["xe"], S, T, "2d_strided", torch.float32)
             outs[key] = _run(a, b, g, sup, True, 1e-3, 1e-5, w=ww, c=cc)
+            a2, b2 = _layout(s["y"], S, T, "2d", torch.float32), _layout(s["xe"], S, T, "2d", torch.float32)
+            copies = _run(a2, b2, g, sup, True, 1e-3, 1e-5, w=ww, c=cc)  # (what the planner makes of the pair)
+            for i in (0, 1, 3, 4):
+                _same_bits(outs[key][i], copies[i], key + ", contiguous copies, output %d" % i)
+            assert outs[key][2] == copies[2], key
+            a3, b3 = _layout(s["y"], S, T, "2d", torch.float32), _layout(s["xe"], S, T, "2d_strided", torch.float32)
+            comp = _run(a3, b3, g, sup, True, 1e-3, 1e-5, w=ww, c=cc, fn=chain_loss_composed)
+            for i in (1, 3, 4):
+                _same_bits(outs[key][i], comp[i], key + ", composed, output %d" % i)
+            _close(outs[key][0], comp[0], key + ": loss, composed")
+            _close(outs[key][2], comp[2], key + ": xent_objf, composed")
         want = torch.from_numpy(oor.penalized(outs["plain"][3].cpu().numpy(), s["y"], c)).to(DEV)
         _same_bits(outs["on"][3], want, "grad, mixed strides")
         _same_bits(outs["both"][3], want * w.to(DEV).unsqueeze(1), "weighted grad, mixed strides")
@@ -250,6 +269,13 @@ def test_fallback_routes_agree_bit_for_bit():
             loss, res = chain_loss(leaf.permute(0, 2, 1), g, sup, 1e-3, 1e-5, deriv_weights=ww, out_of_range_regularize=cc)
             loss.backward()
             grads[key] = leaf.grad.permute(1, 0, 2).reshape(S * T, -1)  # (frame-major rows again)
+            leaf2 = leaf.detach().clone().requires_grad_(True)
+            loss2, res2 = chain_loss_composed(leaf2.permute(0, 2, 1), g, sup, 1e-3, 1e-5, deriv_weights=ww,
+                                              out_of_range_regularize=cc)
+            loss2.backward()
+            _same_bits(leaf.grad, leaf2.grad, key + ": grad, composed")
+            _same_bits(res.data, res2.data, key + ": results, composed")
+            _close(loss.detach(), loss2.detach(), key + ": loss, composed")
         want = torch.from_numpy(oor.penalized(grads["plain"].cpu().numpy(), s["y"], c)).to(DEV)
         _same_bits(grads["on"], want, "grad, non-contiguous (B, C, T)")
         _same_bits(grads["both"], want * w.to(DEV).unsqueeze(1), "weighted grad, non-contiguous (B, C, T)")

@@ -233,7 +233,8 @@ def test_chain_loss_3d_input_fused_path_matches_2d_path(oracle):
     """chain_loss on a (B, C, T) tensor (fused layout passes) gives the loss and the input / xent-input
     gradients of the reference composition to2d -> 2-D loss -> autograd's inverse permute, bit for bit."""
     from torchain_amd import io
-    from torchain_amd.functions import _ChainLoss, ChainResults, chain_loss, to2d
+    from composed_step import _ChainLoss
+    from torchain_amd.functions import ChainResults, chain_loss, to2d
     fst = synth.random_den_fst(200, 5, 90, seed=13)
     B, T, P = 4, 23, 90
     g = oracle.DenGraph(fst)
@@ -293,7 +294,8 @@ def test_kaldi_way_false_is_the_objective_on_xent_input(oracle, three_d):
 def test_one_call_step_equals_the_multi_call_wrappers(three_d, kaldi_way):
     """``tc_chain_step`` (what ``chain_loss`` calls for CUDA float32 tensors) against ``_ChainLoss`` / ``_ChainLoss3d``
     (four to six library calls): loss, results, xent objective and both gradients, bit for bit."""
-    from torchain_amd.functions import ChainResults, _ChainLoss, _ChainLoss3d, chain_loss
+    from composed_step import _ChainLoss, _ChainLoss3d
+    from torchain_amd.functions import ChainResults, chain_loss
     fst = synth.random_den_fst(300, 4, 96, seed=4)
     S, T, P = 5, 11, 96
     den = io.DenominatorGraph(fst, P)

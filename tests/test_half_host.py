@@ -79,10 +79,16 @@ def test_step_dtypes_of_the_python_wrapper():
                                       torch.float16: TC_DTYPE_F16}
     x = torch.zeros(2, 3, 4, dtype=torch.bfloat16)
     # CPU tensors are not taken (no CPU fallback, as for float32)
-    assert not functions._one_call(x)
-    a, b = functions._same_dtype(x, torch.zeros(2, 3, 4))
-    assert a.dtype == b.dtype == torch.float32
-    a, b = functions._same_dtype(x, x.half())
-    assert a.dtype == b.dtype == torch.float32
-    a, b = functions._same_dtype(x, None)
-    assert a is x and b is None
+    assert functions._step_plan(x, None) is None
+    # different dtypes: the 16-bit one(s) are up-cast, a lone 16-bit tensor is not (the planner, applied as chain_loss does)
+    spec = functions._spec
+
+    def apply(t, ops):
+        for op in ops:
+            t = functions._OPS[op](t)
+        return t
+    for other, ops in ((torch.zeros(2, 3, 4), (("float",), ())), (x.half(), (("float",), ("float",)))):
+        got = functions.plan_step_inputs(spec(x), spec(other))
+        assert got[:2] == ops
+        assert apply(x, got[0]).dtype == apply(other, got[1]).dtype == torch.float32
+    assert functions.plan_step_inputs(spec(x)) == ((), (), ("bct", 0, 0))

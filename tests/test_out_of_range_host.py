@@ -106,8 +106,9 @@ def test_limit_is_one_named_constant():
     assert functions.OUTPUT_LIMIT == 30.0 == float(oor.LIMIT)
     src = open(os.path.join(ROOT, "torchain_amd", "csrc", "chain_internal.h")).read()
     assert "constexpr float kOutputLimit = 30.0f;" in src
-    kernels = open(os.path.join(ROOT, "torchain_amd", "csrc", "penalty_kernels.hip")).read()
-    assert "kOutputLimit" in kernels and "30.0f" not in kernels
+    for name in ("half_io.h", "penalty_kernels.hip"):  # (penalize, and the passes that call it)
+        kernels = open(os.path.join(ROOT, "torchain_amd", "csrc", name)).read()
+        assert "kOutputLimit" in kernels and "30.0f" not in kernels
 
 
 def _inputs():

@@ -452,14 +452,19 @@ int tc_num_forward_backward(tc_supervision *sup, const float *y, int64_t rows, i
 // xent_out / xent_objf_dev (tc_chain_step): the cross-entropy output and where sum(xent_out * xent) goes -- formed from
 // the numerator's posteriors as they are written, not from the dense matrices
 // xent_row_w (tc_chain_step_weighted): the per-row factor of the xent entries the numerator writes (not of its objective sum)
+struct ObjfStep {  // what only the one-call step passes: all unset for the two plain entry points
+  const float *xent_out = nullptr, *bct_input = nullptr, *xent_row_w = nullptr;
+  int64_t xent_out_stride = 0;
+  double *xent_objf_dev = nullptr;
+  float *loss_dev1 = nullptr;
+  int xent_bct = 0, xent_out_bct = 0, bct_dtype = TC_DTYPE_F32;
+  bool xent_sums_ready = false;  // (the numerator-only pass of kaldi_way == 0 has left the sequences' xent sums)
+};
+
 static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int64_t rows, int32_t cols,
                       int64_t y_stride, float *results_dev3, float *deriv, int64_t deriv_stride, float *xent,
                       int64_t xent_stride, float l2_regularize, float leaky, float deriv_scale, float xent_scale,
-                      void *workspace, int64_t workspace_bytes, int device, void *stream_v,
-                      const float *xent_out = nullptr, int64_t xent_out_stride = 0, double *xent_objf_dev = nullptr,
-                      int xent_bct = 0, int xent_out_bct = 0, const float *bct_input = nullptr,
-                      bool xent_sums_ready = false, float *loss_dev1 = nullptr, int bct_dtype = TC_DTYPE_F32,
-                      const float *xent_row_w = nullptr) {
+                      void *workspace, int64_t workspace_bytes, int device, void *stream_v, const ObjfStep &o = ObjfStep()) {
   if (!g || !sup || !y || !results_dev3) return TC_ERR_INVALID_ARGUMENT;
   if (sup->P != g->P) return TC_ERR_INVALID_ARGUMENT;
   if ((int64_t)sup->S * sup->T != rows) return TC_ERR_INVALID_ARGUMENT;
@@ -481,27 +486,27 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   if (rc != TC_OK) return rc;
   np.deriv_scale = deriv_scale;
   np.xent_scale = xent_scale;
-  if (xent_out && xent_objf_dev) {  // (also without the dense xent matrix: an evaluation step's cross-entropy objective)
-    np.xent_out = xent_out;
-    np.xent_out_stride = xent_out_stride;
-    np.xent_out_bct = xent_out_bct;
+  if (o.xent_out && o.xent_objf_dev) {  // (also without the dense xent matrix: an evaluation step's cross-entropy objective)
+    np.xent_out = o.xent_out;
+    np.xent_out_stride = o.xent_out_stride;
+    np.xent_out_bct = o.xent_out_bct;
     np.seq_xent = w.xent_lp;
   }
-  np.xent_bct = xent_bct;  // (a (B, C, T) tensor the caller has cleared: only the posteriors' entries are written)
-  np.xent_row_w = xent ? xent_row_w : nullptr;  // (tc_chain_step_weighted: the numerator is xent's only non-zero writer)
-  if (bct_input) {
-    np.y = bct_input;
+  np.xent_bct = o.xent_bct;  // (a (B, C, T) tensor the caller has cleared: only the posteriors' entries are written)
+  np.xent_row_w = xent ? o.xent_row_w : nullptr;  // (tc_chain_step_weighted: the numerator is xent's only non-zero writer)
+  if (o.bct_input) {
+    np.y = o.bct_input;
     np.y_bct = 1;
-    np.elem = bct_dtype;  // (bct_input and a (B, C, T) xent_out: the caller's tensors, float32 or 16-bit)
+    np.elem = o.bct_dtype;  // (bct_input and a (B, C, T) xent_out: the caller's tensors, float32 or 16-bit)
   }
   auto fill_y = [&]() -> int {  // the frame-major copy the denominator reads
-    return bct_input ? launch_to2d(bct_dtype, bct_input, const_cast<float *>(y), sup->S, cols, sup->T, y_stride, stream) : TC_OK;
+    return o.bct_input ? launch_to2d(o.bct_dtype, o.bct_input, const_cast<float *>(y), sup->S, cols, sup->T, y_stride, stream) : TC_OK;
   };
 
   SideStreams *ss = nullptr;
   rc = side_streams(stream, &ss);
   if (rc != TC_OK) return rc;
-  if (xent && !xent_bct) {
+  if (xent && !o.xent_bct) {
     // xent_deriv is zero outside the numerator's posteriors.  The denominator kernels that write every row of deriv
     // anyway write these zero rows with them (under their arc walks, where stores cost next to nothing); the others get
     // a memset in front: 629 MB at C3, 0.13 ms.
@@ -520,7 +525,7 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   // When the denominator leaves CUs idle (small batches) the numerator's recursion runs beside it on a side
   // stream, leaving its posteriors in the supervision's staging area; the scatter follows the denominator.
   // (a forward-only call overlaps the two forward recursions the same way; its numerator writes nothing but its sums)
-  if ((bct_input || den_cus_used(dp, ss->num_cus) + 16 <= ss->num_cus) && np.t.stage && !debug_flag(kDbgNoNumOverlap)) {
+  if ((o.bct_input || den_cus_used(dp, ss->num_cus) + 16 <= ss->num_cus) && np.t.stage && !debug_flag(kDbgNoNumOverlap)) {
     std::lock_guard<std::recursive_mutex> lock(ss->enqueue);
     np.staged = 1;
     TC_HIP_CHECK(hipEventRecord(ss->num_fork, stream));
@@ -553,11 +558,11 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   rc = supervision_mark_use(sup, device, stream);
   if (rc != TC_OK) return rc;
   rc = launch_finalize(w.den_lp, w.num_lp, w.y2, w.ab, w.gs, sup->S, sup->T, wgt, l2_regularize, deriv != nullptr,
-                       results_dev3, w.fail, stream, (np.seq_xent || xent_sums_ready) && xent_objf_dev ? w.xent_lp : nullptr,
-                       xent_objf_dev, loss_dev1);
+                       results_dev3, w.fail, stream, (np.seq_xent || o.xent_sums_ready) && o.xent_objf_dev ? w.xent_lp : nullptr,
+                       o.xent_objf_dev, o.loss_dev1);
   if (rc != TC_OK) return rc;
   // (a (B, C, T) xent tensor is rows * cols contiguous floats: cleared as such)
-  return launch_zero_on_fail(w.fail, deriv, deriv_stride, xent, xent_bct ? (int64_t)cols : xent_stride, y, y_stride,
+  return launch_zero_on_fail(w.fail, deriv, deriv_stride, xent, o.xent_bct ? (int64_t)cols : xent_stride, y, y_stride,
                              deriv_scale * (wgt * l2_regularize), rows, cols, stream);
 }
 
@@ -625,42 +630,87 @@ int64_t tc_chain_step_typed_workspace_bytes(const tc_den_graph *g, int32_t S, in
   return (int64_t)carve_step(nullptr, g, S, T, g->P, three_d != 0, with_xent != 0, dtype).total;
 }
 
-int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, const float *xent_input, int three_d,
-                  int64_t row_stride, float l2_regularize, float leaky, float xent_regularize, int kaldi_way,
-                  float *grad, float *xent_grad, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
-                  void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
-  return tc_chain_step_typed(g, sup, input, xent_input, three_d, row_stride, l2_regularize, leaky, xent_regularize,
-                             kaldi_way, grad, xent_grad, results_dev3, loss_dev1, xent_objf_dev, TC_DTYPE_F32, workspace,
-                             workspace_bytes, device, stream_v);
+// The step in every layout (TC_LAYOUT_*), in three stages: the way in (gather / widen / clear), the objective (the
+// numerator-only pass of kaldi_way == 0, then chain_objf), and emit_gradients, the last pass over each gradient.  StepIo is
+// what the stages share.  batch_stride / frame_stride (sb, st): TC_LAYOUT_CHANNEL_LAST only, checked by the caller.
+// Between the way in and the way out runs the float32 frame-major step: on float32 2-D tensors as they are, on 16-bit 2-D
+// tensors widened and channel-last views gathered (launch_rows_gather) into contiguous float32 scratch, on (B, C, T) tensors
+// copied into it inside chain_objf, beside the numerator, which reads them where they lie.  The last pass -- the (B, C, T)
+// copy back, the rounding pass, the channel-last scatter -- applies row weight, penalty and the one rounding behind
+// chain_objf's soft-failure reset.  A channel-last step's 2-D xent gradient needs one more float32 matrix than the (B, C, T)
+// step has: for 16-bit tensors the float32 xent scratch that step has anyway; for float32 the caller's `grad`, which has
+// exactly that size and is written last, by the MMI gradient's scatter.
+namespace {
+struct StepIo {
+  const float *y, *bct_input;     // the frame-major matrix the objective reads; the (B, C, T) tensor chain_objf fills it from
+  float *gr, *xg;                 // what the objective writes, P floats a row: MMI and xent gradient (NULL: not wanted)
+  const float *num_in, *xent_in;  // kaldi_way == 0's numerator-only pass reads num_in; the xent objective is formed with xent_in
+  int64_t y_stride, num_stride, xent_stride;
+  int caller_bct, xent_bct;       // num_in / xent_in are the caller's (B, C, T) tensors; xg is a cleared (B, C, T) gradient
+};
+
+// The table.  scratch: the objective runs on the workspace's float32 copies (every case but float32 2-D).  widened: so do
+// the numerator's reads of the network outputs (16-bit 2-D and channel-last; a (B, C, T) tensor is read where it lies).
+// second_only (kaldi_way == 0 with the regulariser): the one objective call is made on xent_input.
+StepIo step_io(const StepWorkspace &w, int layout, bool half, bool eval_only, bool second_only, bool use_xent, int P,
+               int64_t row_stride, const float *input, const float *xent_input, float *grad, float *xent_grad) {
+  const bool cl = layout == TC_LAYOUT_CHANNEL_LAST, bct = layout == TC_LAYOUT_BCT;
+  const bool scratch = layout != TC_LAYOUT_ROWS || half, widened = cl || (half && !bct);
+  StepIo io;
+  io.y = scratch ? (second_only ? w.x2d : w.y2d) : (second_only ? xent_input : input);
+  io.y_stride = scratch ? (int64_t)P : row_stride;
+  io.gr = eval_only ? nullptr : (scratch ? w.g2d : grad);
+  // (16-bit: float32 scratch, rounded at the end; float32 channel-last: the caller's grad, until its scatter fills it)
+  io.xg = !use_xent || eval_only ? nullptr : (half ? w.xg : (cl ? grad : xent_grad));
+  io.num_in = widened ? w.y2d : input;
+  io.num_stride = widened || bct ? (int64_t)P : row_stride;
+  io.xent_in = widened ? w.x2d : xent_input;
+  io.xent_stride = widened ? (int64_t)P : row_stride;
+  io.bct_input = bct ? (second_only ? xent_input : input) : nullptr;
+  io.caller_bct = bct ? 1 : 0;
+  // (xent_deriv has entries only where the numerator has posteriors: written straight into the cleared (B, C, T) gradient)
+  io.xent_bct = bct && use_xent ? 1 : 0;
+  return io;
 }
 
-int tc_chain_step_typed(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int three_d,
-                        int64_t row_stride, float l2_regularize, float leaky, float xent_regularize, int kaldi_way,
-                        void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
-                        int dtype, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
-  return tc_chain_step_weighted(g, sup, input_v, xent_input_v, three_d, row_stride, l2_regularize, leaky, xent_regularize,
-                                kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev, nullptr, dtype,
-                                workspace, workspace_bytes, device, stream_v);
+// The last pass over each gradient, picked from (layout, dtype, penalty, weights): the MMI gradient becomes w[row] * (g + t),
+// (-1 * w[row]) * g in one multiply where the sign is still to come, rounded once for 16-bit tensors.  The xent gradient is
+// final as the numerator left it (scaled and weighted): it is only moved or rounded.
+int emit_gradients(const StepIo &io, int layout, int dtype, const float *input, int64_t row_stride, int64_t sb, int64_t st,
+                   float *grad, float *xent_grad, const float *y2d, int S, int T, int P, float pen_c2, const float *row_w,
+                   int device, void *stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  const bool half = dtype != TC_DTYPE_F32, pen = pen_c2 > 0.0f;
+  const int64_t rows = (int64_t)S * T;
+  int rc = TC_OK;
+  if (layout == TC_LAYOUT_CHANNEL_LAST) {
+    // dense (B, T, C) gradients; the xent gradient first: for float32 it lies in `grad`
+    const int64_t dense_b = (int64_t)T * P;
+    if (io.xg) rc = launch_rows_scatter(dtype, io.xg, P, xent_grad, dense_b, P, nullptr, 0, 0, S, T, P, false, 1.0f, 0.0f, nullptr, stream);
+    if (rc == TC_OK)
+      rc = launch_rows_scatter(dtype, io.gr, P, grad, dense_b, P, input, sb, st, S, T, P, true, -1.0f, pen_c2, row_w, stream);
+    return rc;
+  }
+  if (layout == TC_LAYOUT_BCT) {
+    // (plain float32: tc_from2d itself, whose limits the other cases were held to with the arguments)
+    if (pen) rc = launch_from2d_penalized(dtype, io.gr, P, grad, input, S, P, T, -1.0f, pen_c2, row_w, stream);
+    else if (half || row_w) rc = launch_from2d(dtype, io.gr, P, grad, S, P, T, -1.0f, stream, row_w);
+    else rc = tc_from2d(io.gr, P, S, P, T, -1.0f, grad, device, stream_v);
+  } else if (half) {
+    // the one rounding of every element, from the float32 values tc_chain_step would have returned
+    rc = pen ? launch_round_penalized(dtype, io.gr, grad, rows * P, y2d, pen_c2, row_w, P, stream)
+             : launch_round(dtype, io.gr, grad, rows * P, stream, row_w, P);
+  } else if (pen || row_w) {
+    // float32 2-D: the denominator and the numerator have written the caller's tensor; one pass in place, behind
+    // chain_objf's launch_zero_on_fail, so a soft failure's -l2 * weight * y is penalised and weighted too
+    rc = pen ? launch_penalize_rows(io.gr, rows, P, input, row_stride, pen_c2, row_w, stream)
+             : launch_scale_rows(io.gr, rows, P, row_w, stream);
+  }
+  if (rc == TC_OK && half && io.xg) rc = launch_round(dtype, io.xg, xent_grad, rows * P, stream);
+  return rc;
 }
+}  // namespace
 
-int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v,
-                           int three_d, int64_t row_stride, float l2_regularize, float leaky, float xent_regularize,
-                           int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1,
-                           double *xent_objf_dev, const float *deriv_weights, int dtype, void *workspace,
-                           int64_t workspace_bytes, int device, void *stream_v) {
-  return tc_chain_step_penalized(g, sup, input_v, xent_input_v, three_d, row_stride, l2_regularize, leaky, xent_regularize,
-                                 kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev, deriv_weights, 0.0f,
-                                 dtype, workspace, workspace_bytes, device, stream_v);
-}
-
-// The step in every layout (TC_LAYOUT_*).  batch_stride / frame_stride (sb, st): TC_LAYOUT_CHANNEL_LAST only, checked by the
-// caller.  A channel-last step is the float32 2-D step on gathered rows: input (and xent_input) are gathered into contiguous
-// float32 frame-major matrices (launch_rows_gather), the denominator and the numerator run on those exactly as they run on
-// the widened copies of 16-bit 2-D tensors, with the plain derivative in the scratch as for (B, C, T), and one scatter per
-// gradient (launch_rows_scatter) applies what the (B, C, T) copy back applies -- sign, row weight, penalty, the one rounding --
-// behind chain_objf's soft-failure reset.  The 2-D xent gradient needs one more float32 matrix than the (B, C, T) step has:
-// for 16-bit tensors that is the float32 xent scratch the (B, C, T) step has anyway; for float32 it is the caller's `grad`,
-// which has exactly that size and is written last, by the MMI gradient's scatter.
 static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
                              int64_t row_stride, int64_t sb, int64_t st, float l2_regularize, float leaky,
                              float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
@@ -668,7 +718,7 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
                              float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
                              void *stream_v) {
   if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
-  const bool cl = layout == TC_LAYOUT_CHANNEL_LAST;  // (rows gathered and scattered: everything between is 2-D scratch)
+  const bool cl = layout == TC_LAYOUT_CHANNEL_LAST;
   const int three_d = layout != TC_LAYOUT_ROWS;
   if (((uintptr_t)deriv_weights & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
   if (!(out_of_range_regularize >= 0.0f) || std::isinf(out_of_range_regularize)) return TC_ERR_INVALID_ARGUMENT;
@@ -693,159 +743,108 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
     return TC_ERR_UNSUPPORTED;
   // Kaldi's deriv_weights ([K] nnet-chain-training.cc: MulRowsVec on both derivatives, after the objectives are formed):
   // ignored by an evaluation step, which writes no gradient.  Every gradient element becomes w[row] * g, one float32
-  // multiply of the unweighted value, in whichever pass writes it last: the layout copy back ((B, C, T)), the rounding
-  // pass (16-bit 2-D), the numerator's xent stores (all layouts), and for the float32 2-D MMI gradient, which the
-  // denominator and the numerator write into the caller's tensor, one in-place pass over it.
+  // multiply of the unweighted value, in whichever pass writes it last (emit_gradients; the numerator's stores for xent).
   const float *row_w = eval_only ? nullptr : deriv_weights;
   // The out-of-range penalty (after [K] PenalizeOutOfRange, restated in torchain_hip.h): t = fl32(2c) * p(y) joins the
   // MMI gradient in the same last passes, in front of the row weight; y is always the chain output `input`, also when
-  // kaldi_way == 0 runs the objective on xent_input.  (B, C, T): the layout copy back reads `input` where it lies, at the
-  // index it writes; 16-bit 2-D: the rounding pass reads the widened copy w.y2d; float32 2-D: the in-place pass that
-  // applies the row weights (or one of its own) reads `input` with its row stride.  pen_c2 == 0: none of this runs.
+  // kaldi_way == 0 runs the objective on xent_input.  pen_c2 == 0: none of this runs.
   const float pen_c2 = eval_only ? 0.0f : 2.0f * out_of_range_regularize;
   if (std::isinf(pen_c2)) return TC_ERR_INVALID_ARGUMENT;
   const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype);
   if (!workspace || (int64_t)w.total > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
+  if (cl && !channel_last_strides_ok(S, T, P, sb, st)) return TC_ERR_INVALID_ARGUMENT;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
   hipStream_t stream = (hipStream_t)stream_v;
-  // frame-major views of the tensors: the caller's own for 2-D input, copies for (B, C, T) (torchain/functions.py:118-125)
-  const float *y = input;
-  float *gr = grad, *xg = use_xent ? xent_grad : nullptr;
-  int64_t stride = row_stride, gstride = P;  // (2-D gradients are written as contiguous matrices)
-  // what the numerator reads for the cross-entropy objective (xent_in, xent_stride) and for the objective-only pass of
-  // kaldi_way == 0 (num_in, num_stride): the caller's tensors, or for 16-bit 2-D tensors their float32 copies
-  const float *num_in = input, *xent_in = xent_input;
-  int64_t num_stride = three_d ? (int64_t)P : row_stride, xent_stride = row_stride;
-  int rc = TC_OK;
-  // (B, C, T) with the regulariser: xent_deriv has entries only where the numerator has posteriors, so it is written
-  // straight into the caller's cleared (B, C, T) gradient, and the cross-entropy objective reads xent_input where it
-  // lies -- no frame-major copy of either.
   // The reference's way (kaldi_way == 0, functions.py:96-103) makes a second objective call on xent_input INTO THE SAME
   // results, gradient and xent gradient: everything the first call wrote is overwritten.  Only that second call is made
   // here; what remains of the first is this library's own extra, the cross-entropy objective, which is defined on the
   // first call's xent_deriv: the numerator alone on `input` (no denominator, nothing written but the sequences' sums).
   const bool second_only = use_xent && !kaldi_way;
-  const int bct = three_d && !cl && use_xent ? 1 : 0;
+  const StepIo io = step_io(w, layout, half, eval_only, second_only, use_xent, P, row_stride, input, xent_input, grad, xent_grad);
+  int rc = TC_OK;
+
+  // ---- the way in
   if (cl) {
-    if (!channel_last_strides_ok(S, T, P, sb, st)) return TC_ERR_INVALID_ARGUMENT;
-    DeviceGuard guard(device);
-    if (!guard.ok) return TC_ERR_HIP;
     // (the chain output's rows are read by the objective, or with kaldi_way == 0 by the numerator-only pass alone)
     if (!second_only || xent_objf_dev) rc = launch_rows_gather(dtype, input, sb, st, w.y2d, P, S, T, P, stream);
     if (rc == TC_OK && use_xent) rc = launch_rows_gather(dtype, xent_input, sb, st, w.x2d, P, S, T, P, stream);
     if (rc != TC_OK) return rc;
     count_launch(kCntChannelLast);
-    y = second_only ? w.x2d : w.y2d;
-    gr = eval_only ? nullptr : w.g2d;
-    xg = use_xent && !eval_only ? (half ? w.xg : grad) : nullptr;  // (float32: the caller's grad, until its scatter fills it)
-    stride = P;
-    num_in = w.y2d;
-    xent_in = w.x2d;
-    num_stride = xent_stride = P;
   } else if (three_d) {
-    y = second_only ? w.x2d : w.y2d;  // (filled inside chain_objf, beside the numerator: bct_input)
-    gr = eval_only ? nullptr : w.g2d;
-    // (16-bit: the numerator writes the float32 scratch, rounded into the caller's tensor at the end)
-    xg = use_xent && !eval_only ? (half ? w.xg : xent_grad) : nullptr;
-    stride = P;
-    if (xg) {
-      DeviceGuard guard(device);
-      if (!guard.ok) return TC_ERR_HIP;
-      TC_HIP_CHECK(hipMemsetAsync(xg, 0, (size_t)rows * P * sizeof(float), stream));
-    }
+    if (io.xg) TC_HIP_CHECK(hipMemsetAsync(io.xg, 0, (size_t)rows * P * sizeof(float), stream));
   } else if (half) {
-    // 16-bit 2-D tensors: widened into contiguous float32 matrices, on which the float32 2-D step runs as it is
-    DeviceGuard guard(device);
-    if (!guard.ok) return TC_ERR_HIP;
     rc = launch_widen_rows(dtype, input, row_stride, w.y2d, rows, P, stream);
     if (rc == TC_OK && use_xent) rc = launch_widen_rows(dtype, xent_input, row_stride, w.x2d, rows, P, stream);
     if (rc != TC_OK) return rc;
-    y = second_only ? w.x2d : w.y2d;
-    gr = eval_only ? nullptr : w.g2d;
-    xg = use_xent && !eval_only ? w.xg : nullptr;
-    stride = P;
-    num_in = w.y2d;
-    xent_in = w.x2d;
-    num_stride = xent_stride = P;
-  } else if (second_only) {
-    y = xent_input;
   }
+
+  // ---- the objective
   // 2-D: the matrices leave as the reference's backward returns them (-deriv, -xent_regularize * xent_deriv); 3-D: the
-  // MMI gradient's sign rides on the way back through tc_from2d, so the 2-D scratch holds the plain derivative
-  const float dscale = three_d ? 1.0f : -1.0f, xscale = -xent_regularize;  // (the (B, C, T) xent gradient: final values too)
+  // MMI gradient's sign rides on the way back (copy back or scatter), so the 2-D scratch holds the plain derivative
+  const float dscale = three_d ? 1.0f : -1.0f, xscale = -xent_regularize;  // (the xent gradient: final values everywhere)
   // Kaldi's cross-entropy objective sum(xent_output * xent_deriv) ([K] nnet-chain-training.cc; a TODO in the reference,
   // torchain/functions.py:88-89): xent_objf_dev receives it times `xscale`, summed by the numerator over the entries it
   // writes (tc_xent_objf is the dense statement of the same sum)
-  const Workspace wi = carve((char *)w.chain, hist_states(g), S, T, big_p(g), big_h(g), big_g(g), big_hb(g), split_room(g, S), pair_room(g), planes_room(g));
   if (second_only && xent_objf_dev) {
-    DeviceGuard guard(device);
-    if (!guard.ok) return TC_ERR_HIP;
+    const Workspace wi = carve((char *)w.chain, hist_states(g), S, T, big_p(g), big_h(g), big_g(g), big_hb(g), split_room(g, S), pair_room(g), planes_room(g));
     NumParams np;
-    rc = fill_num_params(sup, device, stream, num_in, rows, P, num_stride, nullptr, 0, nullptr, 0, wi.num_lp, &np);
+    rc = fill_num_params(sup, device, stream, io.num_in, rows, P, io.num_stride, nullptr, 0, nullptr, 0, wi.num_lp, &np);
     if (rc != TC_OK) return rc;
-    np.y_bct = three_d && !cl ? 1 : 0;
-    np.elem = three_d && !cl ? dtype : TC_DTYPE_F32;
+    np.y_bct = io.caller_bct;
+    np.elem = io.caller_bct ? dtype : TC_DTYPE_F32;
     np.xent_scale = xscale;
-    np.xent_out = xent_in;
-    np.xent_out_stride = xent_stride;
-    np.xent_out_bct = three_d && !cl ? 1 : 0;
+    np.xent_out = io.xent_in;
+    np.xent_out_stride = io.xent_stride;
+    np.xent_out_bct = io.caller_bct;
     np.seq_xent = wi.xent_lp;
     rc = launch_num(np, stream);
     if (rc == TC_OK) rc = supervision_mark_use(sup, device, stream);
     if (rc != TC_OK) return rc;
   }
-  rc = chain_objf(g, sup, y, rows, P, stride, results_dev3, gr, gstride, xg, gstride, l2_regularize, leaky, dscale, xscale,
-                  w.chain, (int64_t)w.chain_bytes, device, stream_v, use_xent && !second_only ? xent_in : nullptr, xent_stride,
-                  use_xent ? xent_objf_dev : nullptr, bct, bct,
-                  three_d && !cl ? (second_only ? xent_input : input) : nullptr, second_only && xent_objf_dev != nullptr,
-                  loss_dev1, dtype, row_w);
-  if (rc != TC_OK) return rc;
-  if (cl) {
-    if (eval_only) return rc;
-    // the way out: dense (B, T, C) gradients of the input's type.  The xent gradient first -- for float32 it lies in `grad`
-    // -- as the numerator left it (scaled and weighted); then the MMI gradient, as the (B, C, T) copy back forms it:
-    // (-1 * w[row]) * g in one multiply, penalised w[row] * (-g + t), reading `input` at the row it writes.
-    DeviceGuard guard(device);
-    if (!guard.ok) return TC_ERR_HIP;
-    const int64_t dense_b = (int64_t)T * P;
-    if (xg) rc = launch_rows_scatter(dtype, xg, P, xent_grad, dense_b, P, nullptr, 0, 0, S, T, P, false, 1.0f, 0.0f, nullptr, stream);
-    if (rc == TC_OK)
-      rc = launch_rows_scatter(dtype, gr, P, grad, dense_b, P, input, sb, st, S, T, P, true, -1.0f, pen_c2, row_w, stream);
-    return rc;
-  }
-  if (three_d && !eval_only && !half) {
-    if (row_w || pen_c2 > 0.0f) {
-      DeviceGuard guard(device);
-      if (!guard.ok) return TC_ERR_HIP;
-      // (-w[row] * g, one multiply; penalised: w[row] * (-g + t))
-      rc = pen_c2 > 0.0f ? launch_from2d_penalized(TC_DTYPE_F32, gr, P, grad, input, S, P, T, -1.0f, pen_c2, row_w, stream)
-                         : launch_from2d(TC_DTYPE_F32, gr, P, grad, S, P, T, -1.0f, stream, row_w);
-    } else {
-      rc = tc_from2d(gr, P, S, P, T, -1.0f, grad, device, stream_v);
-    }
-    if (rc != TC_OK) return rc;
-  }
-  if (!three_d && !half && (row_w || pen_c2 > 0.0f)) {
-    // behind chain_objf's launch_zero_on_fail, so a soft failure's -l2 * weight * y is penalised and weighted too
-    DeviceGuard guard(device);
-    if (!guard.ok) return TC_ERR_HIP;
-    rc = pen_c2 > 0.0f ? launch_penalize_rows(gr, rows, P, input, row_stride, pen_c2, row_w, stream)
-                       : launch_scale_rows(gr, rows, P, row_w, stream);
-    if (rc != TC_OK) return rc;
-  }
-  if (half && !eval_only) {
-    // the one rounding of every gradient element, from the float32 values tc_chain_step would have returned (times
-    // the row's weight for the MMI gradient; the numerator has weighted the xent gradient's entries already)
-    DeviceGuard guard(device);
-    if (!guard.ok) return TC_ERR_HIP;
-    if (pen_c2 > 0.0f)
-      rc = three_d ? launch_from2d_penalized(dtype, gr, P, grad, input, S, P, T, -1.0f, pen_c2, row_w, stream)
-                   : launch_round_penalized(dtype, gr, grad, rows * P, w.y2d, pen_c2, row_w, P, stream);
-    else
-      rc = three_d ? launch_from2d(dtype, gr, P, grad, S, P, T, -1.0f, stream, row_w)
-                   : launch_round(dtype, gr, grad, rows * P, stream, row_w, P);
-    if (rc == TC_OK && xg) rc = launch_round(dtype, xg, xent_grad, rows * P, stream);
-  }
-  return rc;  // (the loss value -objf / weight was written with the results: finalize_kernel)
+  ObjfStep o;
+  o.xent_out = use_xent && !second_only ? io.xent_in : nullptr;
+  o.xent_out_stride = io.xent_stride;
+  o.xent_objf_dev = use_xent ? xent_objf_dev : nullptr;
+  o.xent_bct = o.xent_out_bct = io.xent_bct;
+  o.bct_input = io.bct_input;
+  o.xent_sums_ready = second_only && xent_objf_dev != nullptr;
+  o.loss_dev1 = loss_dev1;  // (the loss value -objf / weight is written with the results: finalize_kernel)
+  o.bct_dtype = dtype;
+  o.xent_row_w = row_w;
+  rc = chain_objf(g, sup, io.y, rows, P, io.y_stride, results_dev3, io.gr, P, io.xg, P, l2_regularize, leaky, dscale, xscale,
+                  w.chain, (int64_t)w.chain_bytes, device, stream_v, o);
+  if (rc != TC_OK || eval_only) return rc;
+  return emit_gradients(io, layout, dtype, input, row_stride, sb, st, grad, xent_grad, w.y2d, S, T, P, pen_c2, row_w, device,
+                        stream_v);
+}
+
+int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, const float *xent_input, int three_d,
+                  int64_t row_stride, float l2_regularize, float leaky, float xent_regularize, int kaldi_way,
+                  float *grad, float *xent_grad, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
+                  void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  return chain_step_layout(g, sup, input, xent_input, three_d ? TC_LAYOUT_BCT : TC_LAYOUT_ROWS, row_stride, 0, 0, l2_regularize,
+                           leaky, xent_regularize, kaldi_way, grad, xent_grad, results_dev3, loss_dev1, xent_objf_dev, nullptr,
+                           0.0f, TC_DTYPE_F32, workspace, workspace_bytes, device, stream_v);
+}
+
+int tc_chain_step_typed(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int three_d,
+                        int64_t row_stride, float l2_regularize, float leaky, float xent_regularize, int kaldi_way,
+                        void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
+                        int dtype, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  return chain_step_layout(g, sup, input_v, xent_input_v, three_d ? TC_LAYOUT_BCT : TC_LAYOUT_ROWS, row_stride, 0, 0,
+                           l2_regularize, leaky, xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1,
+                           xent_objf_dev, nullptr, 0.0f, dtype, workspace, workspace_bytes, device, stream_v);
+}
+
+int tc_chain_step_weighted(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v,
+                           int three_d, int64_t row_stride, float l2_regularize, float leaky, float xent_regularize,
+                           int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3, float *loss_dev1,
+                           double *xent_objf_dev, const float *deriv_weights, int dtype, void *workspace,
+                           int64_t workspace_bytes, int device, void *stream_v) {
+  return chain_step_layout(g, sup, input_v, xent_input_v, three_d ? TC_LAYOUT_BCT : TC_LAYOUT_ROWS, row_stride, 0, 0,
+                           l2_regularize, leaky, xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1,
+                           xent_objf_dev, deriv_weights, 0.0f, dtype, workspace, workspace_bytes, device, stream_v);
 }
 
 int tc_chain_step_penalized(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v,
@@ -872,9 +871,9 @@ int tc_chain_step_strided(tc_den_graph *g, tc_supervision *sup, const void *inpu
                           float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
                           void *stream_v) {
   if (layout == TC_LAYOUT_ROWS || layout == TC_LAYOUT_BCT)
-    return tc_chain_step_penalized(g, sup, input_v, xent_input_v, layout == TC_LAYOUT_BCT, row_stride, l2_regularize, leaky,
-                                   xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev,
-                                   deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v);
+    return chain_step_layout(g, sup, input_v, xent_input_v, layout, row_stride, 0, 0, l2_regularize, leaky, xent_regularize,
+                             kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev, deriv_weights,
+                             out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v);
   if (layout != TC_LAYOUT_CHANNEL_LAST || !sup) return TC_ERR_INVALID_ARGUMENT;
   if (!channel_last_strides_ok(sup->S, sup->T, sup->P, batch_stride, frame_stride)) return TC_ERR_INVALID_ARGUMENT;
   // (element offsets are multiples of the element size: a base that is not breaks every access)

@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "chain_internal.h"  // kOutputLimit
+
 namespace tc {
 
 template <typename E>
@@ -45,6 +47,32 @@ struct Elem<__half> {
 template <typename E>
 __device__ __forceinline__ float load_elem(const float *p, int64_t i) {
   return Elem<E>::widen(reinterpret_cast<const typename Elem<E>::bits *>(p)[i]);
+}
+
+// The two element functions of the passes that write a gradient last (layout_kernels.hip, penalty_kernels.hip,
+// layout_rows_kernels.hip).  One definition: a step returns the same bits in every layout because every such pass
+// forms its elements with these statements.
+
+// w * v as a float32 value: the empty asm keeps the backend from fusing the multiply into the float16 conversion
+// (v_fma_mixlo_f16 rounds the exact product straight to 16 bits, and its + 0 addend turns a product of -0 into +0)
+__device__ __forceinline__ float weigh(float w, float v) {
+  float p = w * v;
+  asm volatile("" : "+v"(p));
+  return p;
+}
+
+// g + c2 * p with p = y - L above L, y + L below -L and 0 elsewhere, L = kOutputLimit: a NaN fails both comparisons, +-inf
+// is taken out.  The product and the sum are two float32 operations: the empty asm keeps the backend from contracting
+// them, or a product that formed g, into an FMA (or the sum into a 16-bit conversion).  An element with p == 0 keeps g's
+// bits, a zero's sign included.
+__device__ __forceinline__ float penalize(float g, float y, float c2) {
+  float p = y > kOutputLimit ? y - kOutputLimit : (y < -kOutputLimit ? y + kOutputLimit : 0.0f);
+  p = __builtin_isinf(y) ? 0.0f : p;
+  float t = c2 * p;
+  asm volatile("" : "+v"(t), "+v"(g));  // (g too: the caller's scale * v must not merge with the sum either)
+  float r = g + t;
+  asm volatile("" : "+v"(r));
+  return p != 0.0f ? r : g;
 }
 
 }  // namespace tc

@@ -169,14 +169,6 @@ __global__ __launch_bounds__(kCastThreads) void widen_rows_kernel(const uint16_t
   }
 }
 
-// w * v as a float32 value: the empty asm keeps the backend from fusing the multiply into the float16 conversion
-// (v_fma_mixlo_f16 rounds the exact product straight to 16 bits, and its + 0 addend turns a product of -0 into +0)
-__device__ __forceinline__ float weigh(float w, float v) {
-  float p = w * v;
-  asm volatile("" : "+v"(p));
-  return p;
-}
-
 // float32 -> 16-bit, n contiguous elements, rounded once.  VEC: two 16-byte loads and one 16-byte store per 8 elements
 // (n a multiple of 8, both bases 16-byte aligned; with W, cols a multiple of 8 too).  W (tc_chain_step_weighted): element i
 // is row i / cols of a (rows, cols) matrix and is rounded from row_w[row] * in[i].

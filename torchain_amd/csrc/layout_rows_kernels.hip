@@ -17,23 +17,7 @@ namespace {
 
 constexpr int kRowsThreads = 256, kRowsBlocksMax = 4096;
 
-// w * v as a float32 value that the backend cannot fuse into a 16-bit conversion (layout_kernels.hip: weigh)
-__device__ __forceinline__ float weigh(float w, float v) {
-  float p = w * v;
-  asm volatile("" : "+v"(p));
-  return p;
-}
-
-// g + c2 * p(y), two float32 operations that are never contracted (penalty_kernels.hip: penalize, the same statements)
-__device__ __forceinline__ float penalize(float g, float y, float c2) {
-  float p = y > kOutputLimit ? y - kOutputLimit : (y < -kOutputLimit ? y + kOutputLimit : 0.0f);
-  p = __builtin_isinf(y) ? 0.0f : p;
-  float t = c2 * p;
-  asm volatile("" : "+v"(t), "+v"(g));
-  float r = g + t;
-  asm volatile("" : "+v"(r));
-  return p != 0.0f ? r : g;
-}
+// (weigh and penalize, the element functions of the scatter: half_io.h)
 
 // elements a lane moves with one 16-byte access of the caller's tensor: 4 floats or 8 16-bit values
 template <typename E>

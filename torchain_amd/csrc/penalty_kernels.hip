@@ -14,26 +14,7 @@ namespace {
 constexpr int kTileC = 64, kTileTMax = 240, kLayoutThreads = 512;
 constexpr int kCastThreads = 256, kCastBlocksMax = 4096;
 
-// w * v as a float32 value that the backend cannot fuse into a 16-bit conversion (layout_kernels.hip: weigh)
-__device__ __forceinline__ float weigh(float w, float v) {
-  float p = w * v;
-  asm volatile("" : "+v"(p));
-  return p;
-}
-
-// g + c2 * p with p = y - L above L, y + L below -L and 0 elsewhere, L = kOutputLimit: a NaN fails both comparisons, +-inf
-// is taken out.  The product and the sum are two float32 operations: the empty asm keeps the backend from contracting
-// them, or a product that formed g, into an FMA (or the sum into a 16-bit conversion).  An element with p == 0 keeps g's
-// bits, a zero's sign included.
-__device__ __forceinline__ float penalize(float g, float y, float c2) {
-  float p = y > kOutputLimit ? y - kOutputLimit : (y < -kOutputLimit ? y + kOutputLimit : 0.0f);
-  p = __builtin_isinf(y) ? 0.0f : p;
-  float t = c2 * p;
-  asm volatile("" : "+v"(t), "+v"(g));  // (g too: the caller's scale * v must not merge with the sum either)
-  float r = g + t;
-  asm volatile("" : "+v"(r));
-  return p != 0.0f ? r : g;
-}
+// (weigh and penalize, the element functions of every pass here, the latter with L = kOutputLimit: half_io.h)
 
 // layout_kernel<false, VEC, E, W> with the penalty: in[(t*B + b) * stride2d + c] (float32) -> out (B, C, T) of E,
 //   out = row_w[t*B + b] * penalize(scale * in, y, c2)       (W false: no row factor)

@@ -6,9 +6,11 @@ Same names, argument meaning, defaults and quirks as the reference:
 * ``ChainResults.data`` is a CPU float tensor ``[objf, l2_term, weight]``; ``loss = -objf/weight``
   (l2 not included, ``functions.py:19``).
 * ``chain_loss`` accepts ``(B, C, T)`` or ``(T*B, C)`` input; 3-D input is permuted to frame-major
-  rows ``t*B + b`` (``functions.py:118-125``).  For CUDA float32 3-D inputs the permutation, its inverse
-  and the backward's negation / xent scale are single fused passes (``tc_to2d`` / ``tc_from2d``) with
-  identical values.
+  rows ``t*B + b`` (``functions.py:118-125``) inside the library, which also permutes the gradients back.
+* one route: ``plan_step_inputs`` decides, from shapes, strides and dtypes alone, how any ``(input, xent_input)`` pair becomes
+  one the library takes in ONE call (``_ChainStep`` / ``_run_step``, ``tc_chain_step_strided``) -- as it is, or after
+  ``.float()``, ``to2d`` or ``.contiguous()`` (tracked by autograd when a gradient is wanted).  Training, evaluation and
+  ``ops.chain_loss_op`` share that plan; ``_run_step`` refuses whatever the planner would not have produced.
 * backward returns ``-mmi_grad`` for the input and ``-xent_regularize * xent_grad`` for
   ``xent_input``; ``grad_output`` is ignored and nothing is divided by ``weight``
   (``functions.py:106-115``).
@@ -36,7 +38,7 @@ Same names, argument meaning, defaults and quirks as the reference:
   time-major view IS the 2-D layout and is passed as such, without a copy; any other one is gathered and its gradients
   scattered by the library, one pass each.  Values: bit for bit those of the call on ``input.contiguous()`` (float16: up to
   the sign of an exactly zero gradient element, where the view gives the float32 gradient's ``.to(float16)``).  ``xent_input``
-  must be a view with the same strides (or absent); any other combination takes the routes it took before.
+  must be a view with the same strides (or absent); any other combination is made contiguous first (``plan_step_inputs``).
 """
 import ctypes as C
 import inspect
@@ -223,13 +225,6 @@ def xent_objective(xent_output, xent_output_deriv):
         return out
 
 
-def _device_loss(results, like):
-    """-objf / weight as a one-element tensor on the input's device (the reference's ``input.new([results.loss])``,
-    functions.py:104) computed from the device-side results: no host round trip."""
-    r = results._dev
-    return (-(r[0] / r[2])).reshape(1).to(like.dtype)
-
-
 def _deriv_weights(w, rows):
     """``chain_loss``'s ``deriv_weights`` checked: None, or a 1-D real tensor of ``rows`` (S*T) entries on the CPU or a GPU.
     Raises ``ValueError`` otherwise, and for a CPU tensor under stream capture (its copy could not be captured)."""
@@ -293,55 +288,6 @@ def _rows_of(x):
     return x.shape[0] * x.shape[2] if x.dim() == 3 else x.shape[0]
 
 
-class _ChainLoss(Function):
-    """Lattice-free MMI loss; see the reference docstring ``torchain/functions.py:23-60`` for the
-    meaning of every argument (identical here).  ``deriv_weights``: per-row factors of both gradients, applied in
-    backward (frame-major rows, as the 2-D tensors here)."""
-
-    @staticmethod
-    def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
-                out_of_range_regularize=0.0):
-        assert input.is_cuda, "Only CUDA implementation is available"
-        # The kernels write the two matrices as backward() returns them (-deriv, -xent_regularize * xent_deriv):
-        # the reference scales one and negates both in three more passes over (T*B, C) tensors.
-        mmi_grad = torch.empty_like(input, memory_format=torch.contiguous_format)
-        use_xent = xent_input is not None and xent_regularize != 0.0
-        xent_grad = torch.empty_like(xent_input, memory_format=torch.contiguous_format) if use_xent else None
-        compute_chain_objf_and_deriv(den_graph, supervision, input.detach(), results._host, mmi_grad, xent_grad,
-                                     l2_regularize, leaky_hmm_coefficient, xent_regularize, as_gradients=True,
-                                     holder=results)
-        ctx.mmi_grad = mmi_grad
-        if use_xent:
-            # sum(xent_output * xent_deriv) from the scaled matrix: the scale is one factor of every term
-            results._xent_dev = xent_objective(xent_input.detach(), xent_grad)
-            results._xent_ready = torch.cuda.Event()
-            results._xent_ready.record(torch.cuda.current_stream(xent_input.device))
-            results._xent_scale = 1.0 / -float(xent_regularize)
-            results._xent_host = None
-            if not kaldi_way:  # the reference's second call (functions.py:96-103)
-                compute_chain_objf_and_deriv(den_graph, supervision, xent_input.detach(), results._host, mmi_grad,
-                                             xent_grad, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                                             as_gradients=True, holder=results)
-            ctx.xent_grad = xent_grad
-        ctx.row_w = _weights_on(deriv_weights, input.device)
-        ctx.pen = (input.detach(), float(out_of_range_regularize))  # (always the chain output, never xent_input)
-        if results._defer_host_copy:
-            return input.new_zeros(1)  # (filled in behind the all-reduce: parallel.chain_loss_data_parallel)
-        return _device_loss(results, input)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        g, xg = ctx.mmi_grad, getattr(ctx, "xent_grad", None)
-        if ctx.pen[1] > 0.0:  # (in front of the weights, as tc_chain_step_penalized)
-            g = _penalized(g, *ctx.pen)
-        if ctx.row_w is not None:  # ([K] MulRowsVec on both derivatives)
-            w = ctx.row_w.unsqueeze(1)
-            g = g * w.to(g.dtype)
-            xg = xg * w.to(xg.dtype) if xg is not None else None
-        return (g, xg, None, None, None, None, None, None, None, None, None)
-
-
 def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -367,61 +313,12 @@ def from2d_hip(g2d, shape, scale):
     return out
 
 
-class _ChainLoss3d(Function):
-    """``_ChainLoss`` for ``(B, C, T)`` inputs with the layout conversions fused in: the
-    value and the gradients are those of ``_ChainLoss.apply(to2d(input), ...)`` followed by autograd's
-    inverse permute, without the three extra passes over the activation tensor."""
-
-    @staticmethod
-    def forward(ctx, input, xent_input, results, den_graph, supervision,
-                l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
-                out_of_range_regularize=0.0):
-        assert input.is_cuda, "Only CUDA implementation is available"
-        x2d = to2d_hip(input.detach())
-        mmi_grad = torch.empty_like(x2d)
-        use_xent = xent_input is not None and xent_regularize != 0.0
-        xe2d = to2d_hip(xent_input.detach()) if use_xent else None
-        xent_grad = torch.empty_like(xe2d) if use_xent else None
-        compute_chain_objf_and_deriv(den_graph, supervision, x2d, results._host, mmi_grad, xent_grad,
-                                     l2_regularize, leaky_hmm_coefficient, xent_regularize, holder=results)
-        if use_xent:
-            results._xent_dev = xent_objective(xe2d, xent_grad)
-            results._xent_scale = 1.0
-            results._xent_host = None
-        if use_xent and not kaldi_way:  # the reference's second call (functions.py:96-103)
-            compute_chain_objf_and_deriv(den_graph, supervision, xe2d, results._host, mmi_grad, xent_grad,
-                                         l2_regularize, leaky_hmm_coefficient, xent_regularize, holder=results)
-        ctx.mmi_grad = mmi_grad
-        ctx.in_shape = tuple(input.shape)
-        if use_xent:
-            ctx.xent_grad = xent_grad
-            ctx.xent_shape = tuple(xent_input.shape)
-            ctx.xent_scale = float(xent_regularize)
-        ctx.row_w = _weights_on(deriv_weights, input.device)
-        ctx.pen = (input.detach(), float(out_of_range_regularize))
-        if results._defer_host_copy:
-            return input.new_zeros(1)
-        return _device_loss(results, input)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        g = from2d_hip(ctx.mmi_grad, ctx.in_shape, -1.0)
-        xg = from2d_hip(ctx.xent_grad, ctx.xent_shape, -ctx.xent_scale) if hasattr(ctx, "xent_grad") else None
-        if ctx.pen[1] > 0.0:
-            g = _penalized(g, *ctx.pen)
-        if ctx.row_w is not None:  # ([K] MulRowsVec; row t*B + b is element (b, :, t) here)
-            B, _, T = ctx.in_shape
-            w = ctx.row_w.view(T, B).t().unsqueeze(1)
-            g = g * w
-            xg = xg * w if xg is not None else None
-        return (g, xg, None, None, None, None, None, None, None, None, None)
-
-
 class _ChainStep(Function):
-    """The whole training-side step behind ONE library call (``tc_chain_step``): what ``_ChainLoss`` / ``_ChainLoss3d``
-    above do with four to six calls and as many tensor allocations -- layout copies, objective, the reference's second
-    call for ``kaldi_way=False``, cross-entropy objective, loss value, gradients in the input's own layout.  The
-    reference's step is one FFI call too (``torchain/functions.py:82-86``).  Same values as the classes above (tested)."""
+    """The whole training-side step behind ONE library call (``tc_chain_step_strided``) -- layout copies, objective, the
+    reference's second call for ``kaldi_way=False``, cross-entropy objective, loss value, row weights, penalty, gradients
+    in the input's own layout -- and the one autograd class of ``chain_loss``.  The reference's step is one FFI call too
+    (``torchain/functions.py:82-86``).  Same values as the step composed from the library's single calls
+    (``tests/composed_step.py``)."""
 
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
@@ -449,6 +346,14 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
     has nothing to act on."""
     device = input.device
     use_xent = xent_input is not None and xent_regularize != 0.0
+    x = input.detach()
+    xe = xent_input.detach() if use_xent else None
+    plan = _step_plan(x, xe)  # (before any library call: what is refused has touched nothing)
+    if plan is None:
+        raise ValueError("input and xent_input must be CUDA tensors of one dtype (float32, bfloat16 or float16) in one layout the "
+                         "step takes, with the same strides: got %s, and %s" % (_describe(x), _describe(xe)))
+    kind, s0, s1 = plan
+    dtype = _STEP_DTYPES[x.dtype]
     if isinstance(den_graph, io.DenominatorGraph):
         den_graph.prepare(device)
     den_ptr = den_graph.ptr if isinstance(den_graph, io.DenominatorGraph) else den_graph
@@ -461,23 +366,11 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
     want = (S, P, T) if input.dim() == 3 else (S * T, P)
     if tuple(input.shape) != want or (use_xent and tuple(xent_input.shape) != want):
         raise ValueError("nnet output of shape %s does not match the supervision (%s expected)" % (tuple(input.shape), want))
-    x = input.detach()
-    xe = xent_input.detach() if use_xent else None
-    dtype = _STEP_DTYPES[x.dtype]
-    if xe is not None and xe.dtype != x.dtype:
-        raise ValueError("input and xent_input must have the same dtype (%s, %s)" % (x.dtype, xe.dtype))
-    kind, s0, s1 = _layout(x)
-    if kind == "other" or (xe is not None and _layout(xe)[0] != kind):
-        raise ValueError("input and xent_input must come in one layout the step takes (%s, %s)"
-                         % (tuple(x.stride()), tuple(xe.stride()) if xe is not None else None))
-    if kind in ("time_major", "channel_last") and xe is not None and _layout(xe) != (kind, s0, s1):
-        raise ValueError("input and xent_input must be views with the same strides (%s, %s)"
-                         % (tuple(x.stride()), tuple(xe.stride())))
     if kind == "time_major":  # the 2-D layout where it lies: row t*S + s at (t*S + s) * s0
         x = x.as_strided((S * T, P), (s0, 1))
         xe = xe.as_strided((S * T, P), (s0, 1)) if xe is not None else None
     layout = {"rows": TC_LAYOUT_ROWS, "time_major": TC_LAYOUT_ROWS, "bct": TC_LAYOUT_BCT}.get(kind, TC_LAYOUT_CHANNEL_LAST)
-    row_stride = x.stride(0) if layout == TC_LAYOUT_ROWS else 0
+    row_stride = s0 if layout == TC_LAYOUT_ROWS else 0
     # (gradients: contiguous in the 2-D and the (B, C, T) layout; dense (B, T, C) for a channel-last view)
     gshape = {TC_LAYOUT_ROWS: (S * T, P), TC_LAYOUT_BCT: (S, P, T), TC_LAYOUT_CHANNEL_LAST: (S, T, P)}[layout]
     grad = torch.empty(gshape, dtype=x.dtype, device=device) if want_grad else None
@@ -576,78 +469,91 @@ def _layout(x):
     return classify_layout(x.shape, x.stride())
 
 
-def _step_tensor(x):
-    return x.is_cuda and x.dtype in _STEP_DTYPES
-
-
-def _one_call(x):
-    """Tensors the step takes in the reference's own two layouts (``classify_layout``: ``rows`` or ``bct``): CUDA float32
-    (or bfloat16 / float16), (B, C, T) contiguous or 2-D with unit column stride.  (What the registered operator accepts.)"""
-    return x is None or (_step_tensor(x) and _layout(x)[0] in ("rows", "bct"))
-
-
-def _step_view(x):
-    """... or in any layout ``tc_chain_step_strided`` takes as it is: those two, or a channel-last view of a (B, C, T) shape."""
-    return x is None or (_step_tensor(x) and _layout(x) != _OTHER)
-
-
-def _step_plan(input, xent_input):
-    """The layout ``(kind, s0, s1)`` in which ``input`` and ``xent_input`` go to the one call together, or None when they
-    do not: 2-D rows with one row stride, two contiguous (B, C, T) tensors, or two channel-last views of one shape with the
-    same two strides (a joint head split in two)."""
-    if not _step_view(input) or not _step_view(xent_input):
+def pair_layout(a, b=None):
+    """Host only: the layout ``(kind, s0, s1)`` in which two network outputs go to the one call together, or None when they do
+    not.  ``a``, ``b``: ``(shape, strides)``; ``b`` None for a step without ``xent_input``.  Together go 2-D rows with one row
+    stride, two contiguous (B, C, T) tensors, and two time-major or two channel-last views of one shape with the same strides
+    (a joint head split in two).  The stride of a dimension of size 1 means nothing and counts as the contiguous one."""
+    def layout(shape, strides):
+        dense = _contiguous_strides(shape)
+        return classify_layout(shape, [d if n == 1 else s for n, s, d in zip(shape, strides, dense)])
+    la = layout(*a)
+    if la == _OTHER or b is None:
+        return None if la == _OTHER else la
+    if layout(*b) != la:
         return None
-    a = _layout(input)
-    if xent_input is None:
-        return a
-    if _layout(xent_input) != a:
+    if la[0] in ("time_major", "channel_last") and tuple(b[0]) != tuple(a[0]):
         return None
-    if a[0] in ("time_major", "channel_last") and tuple(xent_input.shape) != tuple(input.shape):
-        return None
-    return a
+    return la
 
 
-def _needs_grad(input, xent_input):
-    if not torch.is_grad_enabled():
-        return False
-    return input.requires_grad or (xent_input is not None and xent_input.requires_grad)
+def _contiguous_strides(shape):
+    strides, n = [], 1
+    for size in reversed(shape):
+        strides.insert(0, n)
+        n *= size
+    return tuple(strides)
 
 
-def _as_step_input(x, xe=None):
-    """Tensors ``tc_chain_step`` takes as they are (evaluation steps only: nothing flows back, so a copy is harmless).  A
-    pair of channel-last views with the same strides stays as it is; otherwise a view is copied."""
-    def one(t):
-        assert t.is_cuda, "Only CUDA implementation is available"
-        t = t.detach()
-        return t if t.dtype in _STEP_DTYPES else t.float()
-    x, xe = one(x), (one(xe) if xe is not None else None)
-    if _step_plan(x, xe) is not None:
-        return x, xe
-    return (x if _one_call(x) else x.contiguous()), (xe if _one_call(xe) else xe.contiguous())
+def _dense(shape, strides, ordered=False):
+    """Whether the elements fill one block of memory without gaps or overlap (then ``.float()`` keeps the strides); ``ordered``:
+    in C order as well, which is ``is_contiguous()``.  The stride of a dimension of size 1 is ignored, as torch ignores it."""
+    dims = [(st, n) for n, st in zip(shape, strides) if n != 1]
+    want = 1
+    for st, n in (reversed(dims) if ordered else sorted(dims)):
+        if st != want:
+            return False
+        want *= n
+    return all(n > 0 for n in shape)
 
 
-def _same_dtype(input, xent_input):
-    """``input`` and ``xent_input`` of different dtypes: the 16-bit one(s) up-cast to float32 (tracked by autograd), which
-    takes the float32 path -- correct, but with the two extra passes the 16-bit one call saves."""
-    if xent_input is None or xent_input.dtype == input.dtype:
-        return input, xent_input
-    return (input.float() if input.dtype in _HALF else input), (xent_input.float() if xent_input.dtype in _HALF else xent_input)
+def plan_step_inputs(a, b=None, want_grad=True):
+    """Host only, a pure function of shapes, strides and dtypes: what to do with any ``(input, xent_input)`` pair so that the
+    one call takes it.  ``a``, ``b``: ``(shape, strides, dtype)``, ``b`` None without ``xent_input``.  Returns ``(ops_a, ops_b,
+    layout)``: per tensor the operations to apply in order -- ``"float"``, ``"contiguous"``, ``"to2d"`` -- and the layout
+    (``pair_layout``) in which the pair then goes.  The rules:
 
+    * different dtypes: the 16-bit one(s) are up-cast to float32 (correct, not the fast path).  A dtype the step does not take
+      is a ``ValueError`` when a gradient is wanted and is up-cast otherwise.  (A view that is not dense is made contiguous in
+      front of the cast, so that the strides behind it are known here.)
+    * a pair that goes together already (``pair_layout``) stays as it is;
+    * (B, C, T) with 2-D: ``to2d`` on the 3-D tensor;
+    * after that, a pair that still does not go together -- 2-D rows with different row strides, channel-last views with
+      different strides, a channel stride that is not 1 -- has every tensor that is not contiguous made so.
 
-def _half_one_call(input, xent_input):
-    """16-bit CUDA inputs in a layout ``tc_chain_step_typed`` does not take as it is: made contiguous (tracked by autograd)
-    so that the step is still one call; up-cast to float32 when even that does not fit (a 3-D input with a 2-D
-    ``xent_input``).  Channel-last views that go to the one call together stay as they are."""
-    if _step_plan(input, xent_input) is not None:
-        return input, xent_input
-    input = input if _one_call(input) else input.contiguous()
-    if xent_input is not None:
-        xent_input = xent_input if _one_call(xent_input) else xent_input.contiguous()
-        if xent_input.dim() != input.dim():
-            return input.float(), xent_input.float()
-        if input.dim() == 2 and xent_input.stride(0) != input.stride(0):
-            input, xent_input = input.contiguous(), xent_input.contiguous()
-    return input, xent_input
+    Every pair leaves as 2-D rows with one row stride, two contiguous (B, C, T) tensors, a time-major pair or a channel-last
+    pair with the same strides; what cannot (other ranks, empty tensors) is a ``ValueError``."""
+    specs = [s for s in (a, b) if s is not None]
+    geo = [(tuple(s[0]), tuple(s[1])) for s in specs]
+    dtypes = [s[2] for s in specs]
+    ops = [[] for _ in specs]
+    if any(len(shape) not in (2, 3) for shape, _ in geo):
+        raise ValueError("chain_loss takes (B, C, T) or (T*B, C) tensors, got shapes %s" % ([g[0] for g in geo],))
+    if want_grad and any(d not in _STEP_DTYPES for d in dtypes):
+        raise ValueError("chain_loss takes float32, bfloat16 or float16 tensors, got %s" % (dtypes,))
+
+    def do(i, op):
+        shape, strides = geo[i]
+        if op == "to2d":
+            shape = (shape[2] * shape[0], shape[1])
+        geo[i] = (shape, strides if op == "float" else _contiguous_strides(shape))
+        ops[i].append(op)
+
+    for i, d in enumerate(dtypes):
+        if d not in _STEP_DTYPES or (len(set(dtypes)) > 1 and d in _HALF):
+            if not _dense(*geo[i]):
+                do(i, "contiguous")
+            do(i, "float")
+    if len(geo) == 2 and len(geo[0][0]) != len(geo[1][0]):
+        do(0 if len(geo[0][0]) == 3 else 1, "to2d")
+    if pair_layout(*geo) is None:
+        for i, g in enumerate(geo):
+            if not _dense(*g, ordered=True):
+                do(i, "contiguous")
+    layout = pair_layout(*geo)
+    if layout is None:
+        raise ValueError("chain_loss cannot take tensors of shapes %s" % ([g[0] for g in geo],))
+    return tuple(ops[0]), tuple(ops[1]) if b is not None else (), layout
 
 
 def to2d(x):
@@ -658,8 +564,56 @@ def to2d(x):
     return x
 
 
-def _fusable(x):
-    return x.dim() == 3 and x.is_cuda and x.dtype == torch.float32
+_OPS = {"float": torch.Tensor.float, "contiguous": torch.Tensor.contiguous, "to2d": to2d}
+
+
+def _spec(x):
+    return None if x is None else (tuple(x.shape), tuple(x.stride()), x.dtype)
+
+
+def _describe(x):
+    return "None" if x is None else "%s %s, shape %s, strides %s" % (x.device.type, x.dtype, tuple(x.shape), tuple(x.stride()))
+
+
+def _step_plan(input, xent_input):
+    """The layout ``(kind, s0, s1)`` in which ``input`` and ``xent_input`` go to the one call as they are, or None when they
+    do not: CUDA tensors of one dtype the step takes, in a layout they share (``pair_layout``).  What ``plan_step_inputs``
+    produces, and all that ``_run_step`` accepts."""
+    for t in (input, xent_input):
+        if t is not None and not (t.is_cuda and t.dtype in _STEP_DTYPES and t.dtype == input.dtype):
+            return None
+    return pair_layout(_spec(input)[:2], _spec(xent_input)[:2] if xent_input is not None else None)
+
+
+def _one_call(x):
+    """One tensor the step takes in the reference's own two layouts (``rows`` or ``bct``), which is what the registered operator
+    accepts: CUDA, a dtype of ``_STEP_DTYPES``, (B, C, T) contiguous or 2-D with unit column stride."""
+    return x is None or (_step_view(x) and _layout(x)[0] in ("rows", "bct"))
+
+
+def _step_view(x):
+    """... or in any layout ``tc_chain_step_strided`` takes as it is: those two, or a channel-last view of a (B, C, T) shape."""
+    return x is None or (x.is_cuda and x.dtype in _STEP_DTYPES and _layout(x) != _OTHER)
+
+
+def _needs_grad(input, xent_input):
+    if not torch.is_grad_enabled():
+        return False
+    return input.requires_grad or (xent_input is not None and xent_input.requires_grad)
+
+
+def _step_inputs(input, xent_input, want_grad):
+    """``plan_step_inputs`` applied: the pair as the one call takes it.  The operations are tracked by autograd when a gradient
+    is wanted (the gradients flow back through them) and applied to detached tensors otherwise."""
+    assert input.is_cuda and (xent_input is None or xent_input.is_cuda), "Only CUDA implementation is available"
+    if not want_grad:
+        input, xent_input = input.detach(), (xent_input.detach() if xent_input is not None else None)
+    ops, xent_ops, _ = plan_step_inputs(_spec(input), _spec(xent_input), want_grad)
+    for op in ops:
+        input = _OPS[op](input)
+    for op in xent_ops:
+        xent_input = _OPS[op](xent_input)
+    return input, xent_input
 
 
 def chain_loss(input, den_graph, supervision,
@@ -680,31 +634,23 @@ chain_loss.__signature__ = inspect.signature(chain_loss).replace(
 def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
                      xent_input, kaldi_way, deriv_weights=None, out_of_range_regularize=0.0):
     """``chain_loss`` with the ``ChainResults`` given (parallel.chain_loss_data_parallel passes one that defers the
-    host copy of the three floats until after its all-reduce)."""
+    host copy of the three floats until after its all-reduce): check the options, plan, one call."""
     deriv_weights = _deriv_weights(deriv_weights, _rows_of(input))
     c = _out_of_range(out_of_range_regularize)
-    input, xent_input = _same_dtype(input, xent_input)
-    if not _needs_grad(input, xent_input):  # (deriv_weights and the penalty: checked above, not used without a gradient)
-        # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the
-        # forward recursions only.  The reference has no such check (functions.py:74,82) and pays for a training step.
-        x, xe = _as_step_input(input, xent_input)
-        out, _, _ = _run_step(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                              xent_regularize, kaldi_way, want_grad=False)
-        return (input.new_zeros(1) if results._defer_host_copy else out[3:4].to(input.dtype)), results
-    if input.is_cuda and input.dtype in _HALF:
-        input, xent_input = _half_one_call(input, xent_input)
-    if _step_plan(input, xent_input) is not None:
-        loss = _ChainStep.apply(input, xent_input, results, den_graph, supervision,
-                                l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights, c)
+    want_grad = _needs_grad(input, xent_input)
+    x, xe = _step_inputs(input, xent_input, want_grad)
+    if want_grad:
+        loss = _ChainStep.apply(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
+                                kaldi_way, deriv_weights, c)
         return loss, results
-    if _fusable(input) and (xent_input is None or _fusable(xent_input)):
-        loss = _ChainLoss3d.apply(input, xent_input, results, den_graph, supervision,
-                                  l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights, c)
-        return loss, results
-    input = to2d(input)
-    if xent_input is not None:
-        xent_input = to2d(xent_input)
+    # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the forward
+    # recursions only; deriv_weights and the penalty are checked above and not used.  The reference has no such check
+    # (functions.py:74,82) and pays for a training step.
+    out, _, _ = _run_step(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
+                          kaldi_way, want_grad=False)
+    # (the loss of an up-cast dtype the step does not take keeps that dtype)
+    like = x if input.dtype in _STEP_DTYPES else input
+    return (like.new_zeros(1) if results._defer_host_copy else out[3:4].to(like.dtype)), results
 
-    loss = _ChainLoss.apply(input, xent_input, results, den_graph, supervision,
-                            l2_regularize, leaky_hmm_coefficient, xent_regularize, kaldi_way, deriv_weights, c)
-    return loss, results
+
+_ChainLoss = _ChainStep  # (the name the reference's module exports, torchain/functions.py)

@@ -109,11 +109,12 @@ def chain_loss_op(input, den_graph, supervision, l2_regularize=0.0, leaky_hmm_co
     ``chain_loss``; a value above 0 goes through ``torchain_amd::chain_step_penalized``."""
     w = functions._deriv_weights(deriv_weights, functions._rows_of(input))
     c = functions._options(options, "chain_loss_op")
-    if not (functions._one_call(input) and functions._one_call(xent_input)):
-        raise ValueError("chain_loss_op needs CUDA float32 / bfloat16 / float16 tensors, (B, C, T) contiguous or 2-D with unit "
-                         "column stride")
-    if xent_input is not None and xent_input.dtype != input.dtype:
-        raise ValueError("chain_loss_op needs input and xent_input of one dtype (%s, %s)" % (input.dtype, xent_input.dtype))
+    # (the traced operator does not normalise: it takes what the planner would leave as it is, in the reference's two layouts)
+    plan = functions._step_plan(input, xent_input)
+    if plan is None or not functions._one_call(input):
+        raise ValueError("chain_loss_op needs CUDA float32 / bfloat16 / float16 tensors of one dtype, both (B, C, T) contiguous or "
+                         "both 2-D with unit column stride and one row stride: got %s, and %s"
+                         % (functions._describe(input), functions._describe(xent_input)))
     if isinstance(den_graph, io.DenominatorGraph):
         den_graph.prepare(input.device)
     want_grad = functions._needs_grad(input, xent_input)
