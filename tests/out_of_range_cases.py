@@ -10,6 +10,9 @@ KINDS = ("none", "sparse", "dense", "edge")
 # (graph, S, T, paths) of the two small workloads the GPU tests run their whole matrix on
 SMALL = dict(fst=(40, 4, 20, 6), S=2, T=6)
 MEDIUM = dict(fst=(700, 5, 300, 19), S=4, T=30)
+# a second tile of the (B, C, T) copy back along the frames (240 a tile) and along the channels (64 a tile); the leftover is
+# one frame (element-wise stores), two (4-byte stores) and four (8-byte stores of a 16-bit tensor)
+TILED = {T: dict(fst=(120, 4, 72, 6), S=2, T=T) for T in (241, 242, 244)}
 
 
 def excess(y):

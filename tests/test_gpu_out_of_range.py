@@ -177,6 +177,23 @@ def test_unaligned_shapes_take_the_scalar_paths(T):
             _check(graph, sup, S, T, y, xe, dtype, layout, None)
 
 
+@pytest.mark.parametrize("kind", ["sparse", "dense"])
+@pytest.mark.parametrize("T", sorted(oor.TILED))
+def test_second_tile_of_the_copy_back(T, kind):
+    """2 x 72 x T with T just past 240: a second tile of the (B, C, T) copy back along the frames and along the channels.
+    In the second frame tile the frames' factors in LDS are indexed by the tile-local frame and loaded from the rows of
+    frame 240 on; the leftover is one frame (element-wise stores), two (4-byte) or four (8-byte, 16-bit tensors)."""
+    spec = oor.TILED[T]
+    fst, sup, y, n = oor.workload(spec, kind)
+    assert n > 0 and spec["S"] == 2 and fst.num_pdfs == 72
+    graph = io.DenominatorGraph(fst, fst.num_pdfs).prepare(DEV)
+    hsup = io.Supervision.from_synth(sup)
+    xe = synth.random_nnet_output(2, T, fst.num_pdfs, seed=2)
+    for dtype in DTYPES:
+        for xent in (None, False):
+            _check(graph, hsup, 2, T, y, xe, dtype, "3d", xent, c=0.25, w=_weights(2, T, 4))
+
+
 # ---- kernel families, numerator modes, e2e supervisions, C3 -----------------------------------------------------------
 @pytest.mark.parametrize("family", [None, "force_general", "force_streamed", "force_pair", "force_mitm", "no_num_overlap"])
 def test_kernel_families(kernel_family, family):

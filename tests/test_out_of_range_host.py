@@ -106,9 +106,11 @@ def test_limit_is_one_named_constant():
     assert functions.OUTPUT_LIMIT == 30.0 == float(oor.LIMIT)
     src = open(os.path.join(ROOT, "torchain_amd", "csrc", "chain_internal.h")).read()
     assert "constexpr float kOutputLimit = 30.0f;" in src
-    for name in ("half_io.h", "penalty_kernels.hip"):  # (penalize, and the passes that call it)
+    for name in ("half_io.h", "layout_kernels.hip", "layout_rows_kernels.hip"):  # (penalize, and the passes that call it)
         kernels = open(os.path.join(ROOT, "torchain_amd", "csrc", name)).read()
-        assert "kOutputLimit" in kernels and "30.0f" not in kernels
+        assert "penalize(" in kernels or "last_elem<" in kernels, name
+        assert "30.0f" not in kernels, name
+    assert "kOutputLimit" in open(os.path.join(ROOT, "torchain_amd", "csrc", "half_io.h")).read().split("float penalize(")[1]
 
 
 def _inputs():
@@ -171,7 +173,8 @@ def test_torch_statement_of_the_fallback_routes_is_bit_for_bit(c):
         np.testing.assert_array_equal(got.view(np.int32)[inside], g.view(np.int32)[inside])
 
 
-@pytest.mark.parametrize("spec", [oor.SMALL, oor.MEDIUM], ids=["small", "medium"])
+@pytest.mark.parametrize("spec", [oor.SMALL, oor.MEDIUM] + list(oor.TILED.values()),
+                         ids=["small", "medium"] + ["tiled%d" % T for T in oor.TILED])
 def test_oracle_takes_no_soft_failure_on_the_gpu_tests_inputs(oracle, spec):
     """The inputs of the 'step succeeded' GPU tests: objf finite and not -10 * weight, for every kind of input."""
     objf = {}

@@ -680,33 +680,39 @@ int emit_gradients(const StepIo &io, int layout, int dtype, const float *input, 
                    float *grad, float *xent_grad, const float *y2d, int S, int T, int P, float pen_c2, const float *row_w,
                    int device, void *stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
-  const bool half = dtype != TC_DTYPE_F32, pen = pen_c2 > 0.0f;
+  const bool half = dtype != TC_DTYPE_F32, cl = layout == TC_LAYOUT_CHANNEL_LAST, bct = layout == TC_LAYOUT_BCT;
   const int64_t rows = (int64_t)S * T;
+  // 3-D: the sign is still to come.  y where the pass's output lies: the caller's tensor, or its widened copy (16-bit 2-D)
+  LastPass lp;
+  lp.scale = cl || bct ? -1.0f : 1.0f;
+  lp.row_w = row_w;
+  lp.pen_c2 = pen_c2;
+  lp.y = !cl && !bct && half ? y2d : input;
+  lp.y_stride = cl ? sb : row_stride;
+  lp.y_st = st;
   int rc = TC_OK;
-  if (layout == TC_LAYOUT_CHANNEL_LAST) {
+  if (cl) {
     // dense (B, T, C) gradients; the xent gradient first: for float32 it lies in `grad`
     const int64_t dense_b = (int64_t)T * P;
-    if (io.xg) rc = launch_rows_scatter(dtype, io.xg, P, xent_grad, dense_b, P, nullptr, 0, 0, S, T, P, false, 1.0f, 0.0f, nullptr, stream);
-    if (rc == TC_OK)
-      rc = launch_rows_scatter(dtype, io.gr, P, grad, dense_b, P, input, sb, st, S, T, P, true, -1.0f, pen_c2, row_w, stream);
+    LastPass moved;
+    moved.scaled = false;
+    if (io.xg) rc = launch_rows_scatter(dtype, io.xg, P, xent_grad, dense_b, P, S, T, P, moved, stream);
+    if (rc == TC_OK) rc = launch_rows_scatter(dtype, io.gr, P, grad, dense_b, P, S, T, P, lp, stream);
     return rc;
   }
-  if (layout == TC_LAYOUT_BCT) {
+  if (bct) {
     // (plain float32: tc_from2d itself, whose limits the other cases were held to with the arguments)
-    if (pen) rc = launch_from2d_penalized(dtype, io.gr, P, grad, input, S, P, T, -1.0f, pen_c2, row_w, stream);
-    else if (half || row_w) rc = launch_from2d(dtype, io.gr, P, grad, S, P, T, -1.0f, stream, row_w);
-    else rc = tc_from2d(io.gr, P, S, P, T, -1.0f, grad, device, stream_v);
+    if (half || row_w || pen_c2 > 0.0f) rc = launch_from2d(dtype, io.gr, P, grad, S, P, T, lp, stream);
+    else rc = tc_from2d(io.gr, P, S, P, T, lp.scale, grad, device, stream_v);
   } else if (half) {
     // the one rounding of every element, from the float32 values tc_chain_step would have returned
-    rc = pen ? launch_round_penalized(dtype, io.gr, grad, rows * P, y2d, pen_c2, row_w, P, stream)
-             : launch_round(dtype, io.gr, grad, rows * P, stream, row_w, P);
-  } else if (pen || row_w) {
+    rc = launch_round(dtype, io.gr, grad, rows * P, P, lp, stream);
+  } else if (row_w || pen_c2 > 0.0f) {
     // float32 2-D: the denominator and the numerator have written the caller's tensor; one pass in place, behind
     // chain_objf's launch_zero_on_fail, so a soft failure's -l2 * weight * y is penalised and weighted too
-    rc = pen ? launch_penalize_rows(io.gr, rows, P, input, row_stride, pen_c2, row_w, stream)
-             : launch_scale_rows(io.gr, rows, P, row_w, stream);
+    rc = launch_scale_rows(io.gr, rows, P, lp, stream);
   }
-  if (rc == TC_OK && half && io.xg) rc = launch_round(dtype, io.xg, xent_grad, rows * P, stream);
+  if (rc == TC_OK && half && io.xg) rc = launch_round(dtype, io.xg, xent_grad, rows * P, P, LastPass{}, stream);
   return rc;
 }
 }  // namespace
@@ -739,7 +745,7 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   const int64_t rows = (int64_t)S * T;
   if (!three_d && row_stride < P) return TC_ERR_INVALID_ARGUMENT;
   // (tc_from2d's limits; the float32 unweighted call meets them in tc_from2d itself)
-  if ((half || deriv_weights || out_of_range_regularize > 0.0f) && three_d && !cl && (S > 65535 || (T + 239) / 240 > 65535))
+  if ((half || deriv_weights || out_of_range_regularize > 0.0f) && three_d && !cl && !layout_grid_ok(S, T))
     return TC_ERR_UNSUPPORTED;
   // Kaldi's deriv_weights ([K] nnet-chain-training.cc: MulRowsVec on both derivatives, after the objectives are formed):
   // ignored by an evaluation step, which writes no gradient.  Every gradient element becomes w[row] * g, one float32
@@ -903,8 +909,14 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
   if (pen_c2 > 0.0f && (!input || !channel_last_strides_ok(B, T, Cn, batch_stride, frame_stride))) return TC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(device);
   if (!guard.ok) return TC_ERR_HIP;
-  return launch_rows_scatter(dtype, in2d, in_stride, out_btc, (int64_t)T * Cn, Cn, input, batch_stride, frame_stride, B, T, Cn,
-                             true, scale, pen_c2, row_weights, (hipStream_t)stream_v);
+  LastPass lp;
+  lp.scale = scale;
+  lp.row_w = row_weights;
+  lp.pen_c2 = pen_c2;
+  lp.y = input;
+  lp.y_stride = batch_stride;
+  lp.y_st = frame_stride;
+  return launch_rows_scatter(dtype, in2d, in_stride, out_btc, (int64_t)T * Cn, Cn, B, T, Cn, lp, (hipStream_t)stream_v);
 }
 
 int tc_xent_objf(const float *xent_output, int64_t rows, int32_t cols, int64_t output_stride, const float *xent_deriv,
@@ -922,19 +934,21 @@ int tc_xent_objf(const float *xent_output, int64_t rows, int32_t cols, int64_t o
 int tc_to2d(const float *in_bct, int32_t B, int32_t Cn, int32_t T, float *out2d, int64_t out_stride, int device,
             void *stream_v) {
   if (!in_bct || !out2d || B <= 0 || Cn <= 0 || T <= 0 || out_stride < Cn) return TC_ERR_INVALID_ARGUMENT;
-  if (B > 65535 || (T + 239) / 240 > 65535) return TC_ERR_UNSUPPORTED;  // grid y / z limits
+  if (!layout_grid_ok(B, T)) return TC_ERR_UNSUPPORTED;
   DeviceGuard guard(device);
   if (!guard.ok) return TC_ERR_HIP;
-  return launch_layout(true, in_bct, out2d, B, Cn, T, out_stride, 1.0f, (hipStream_t)stream_v);
+  return launch_to2d(TC_DTYPE_F32, in_bct, out2d, B, Cn, T, out_stride, (hipStream_t)stream_v);
 }
 
 int tc_from2d(const float *in2d, int64_t in_stride, int32_t B, int32_t Cn, int32_t T, float scale, float *out_bct,
               int device, void *stream_v) {
   if (!in2d || !out_bct || B <= 0 || Cn <= 0 || T <= 0 || in_stride < Cn) return TC_ERR_INVALID_ARGUMENT;
-  if (B > 65535 || (T + 239) / 240 > 65535) return TC_ERR_UNSUPPORTED;
+  if (!layout_grid_ok(B, T)) return TC_ERR_UNSUPPORTED;
   DeviceGuard guard(device);
   if (!guard.ok) return TC_ERR_HIP;
-  return launch_layout(false, in2d, out_bct, B, Cn, T, in_stride, scale, (hipStream_t)stream_v);
+  LastPass lp;
+  lp.scale = scale;
+  return launch_from2d(TC_DTYPE_F32, in2d, in_stride, out_bct, B, Cn, T, lp, (hipStream_t)stream_v);
 }
 
 }  // extern "C"

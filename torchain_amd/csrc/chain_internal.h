@@ -525,47 +525,44 @@ int launch_trace_mat_mat(const float *a, int64_t a_stride, const float *b, int64
 // (den_device.h:72-73, den_tied_device.h:83, den_slab_kernel.hip:47-48 spell the value out), and the out-of-range penalty
 // of tc_chain_step_penalized (after [K] PenalizeOutOfRange, restated in torchain_hip.h) acts outside the same range.
 constexpr float kOutputLimit = 30.0f;
-// row_w (the way back, !to2d; tc_chain_step_weighted): a per-row factor of the 2-D side, out = scale * row_w[row] * in
-// formed as (scale * row_w[row]) * in; null: out = scale * in
-int launch_layout(bool to2d, const float *in, float *out, int B, int Cn, int T, int64_t stride2d, float scale,
-                  hipStream_t stream, const float *row_w = nullptr);
-// the caller's tensors of tc_chain_step_typed (dtype: TC_DTYPE_*): the layout copies with the (B, C, T) side of that type
-// (TC_DTYPE_F32: launch_layout), the widening copy of 16-bit 2-D rows into a contiguous float32 matrix and the rounding
-// copy of n contiguous floats into 16 bits (these two: TC_DTYPE_BF16 / TC_DTYPE_F16 only).  row_w: as launch_layout's
-// for launch_from2d; for launch_round the factor of row i / cols of the n floats, rounded once from row_w[row] * in[i]
+// The passes that write a gradient last -- the (B, C, T) copy back, the 16-bit rounding pass, the in-place float32 row
+// pass and the channel-last scatter -- and what each is told.  Every element leaves as half_io.h's last_elem states it:
+//   scale * v;  with row_w, (scale * row_w[row]) * v in one multiply (tc_chain_step_weighted);
+//   with pen_c2 = fl32(2 * c) > 0 (tc_chain_step_penalized), row_w[row] * penalize(scale * v, y), row_w NULL taken as 1,
+//   an element whose y lies in range keeping the bits of scale * v.
+// y is the network output of the element, laid out as the pass's OUTPUT is: the caller's (B, C, T) tensor of `dtype`; the
+// n contiguous widened floats; float32 rows of y_stride; or a channel-last view of `dtype` with batch stride y_stride and
+// frame stride y_st.  !scaled (the scatter alone): the values are final and are only moved and rounded.
+struct LastPass {
+  float scale = 1.0f;
+  const float *row_w = nullptr;
+  float pen_c2 = 0.0f;
+  const void *y = nullptr;
+  int64_t y_stride = 0, y_st = 0;
+  bool scaled = true;
+};
+// layout_kernels.hip.  The tiled copies between a (B, C, T) tensor of `dtype` (TC_DTYPE_*) and frame-major float32 rows;
+// layout_grid_ok: whether their grid takes B sequences of T frames (else TC_ERR_UNSUPPORTED)
+bool layout_grid_ok(int B, int T);
 int launch_to2d(int dtype, const void *in_bct, float *out, int B, int Cn, int T, int64_t stride2d, hipStream_t stream);
-int launch_from2d(int dtype, const float *in, int64_t stride2d, void *out_bct, int B, int Cn, int T, float scale,
-                  hipStream_t stream, const float *row_w = nullptr);
+int launch_from2d(int dtype, const float *in, int64_t stride2d, void *out_bct, int B, int Cn, int T, const LastPass &lp,
+                  hipStream_t stream);
+// 16-bit 2-D tensors (TC_DTYPE_BF16 / TC_DTYPE_F16 only): the widening copy of strided rows into a contiguous float32
+// matrix, and the rounding copy of n contiguous floats, `cols` a row (read with row_w only), whose sign is final (scale 1)
 int launch_widen_rows(int dtype, const void *in, int64_t in_stride, float *out, int64_t rows, int cols, hipStream_t stream);
-int launch_round(int dtype, const float *in, void *out, int64_t n, hipStream_t stream, const float *row_w = nullptr,
-                 int cols = 0);
-// a[r][c] *= row_w[r] in place on a contiguous float32 (rows, cols) matrix (the 2-D float32 MMI gradient of
-// tc_chain_step_weighted, which the denominator and the numerator write straight into the caller's tensor)
-int launch_scale_rows(float *a, int64_t rows, int cols, const float *row_w, hipStream_t stream);
-// penalty_kernels.hip (tc_chain_step_penalized, pen_c2 = fl32(2 * c) > 0): launch_from2d, launch_round and launch_scale_rows
-// with the out-of-range penalty in the same pass.  Each element becomes row_w[row] * fl32(g + fl32(pen_c2 * p(y))), with g
-// what the unpenalised pass writes for row_w == NULL, row_w NULL taken as 1, and y the network output of the element, laid
-// out as the pass's OUTPUT is: the caller's (B, C, T) tensor of `dtype`, the n contiguous widened floats, rows of y_stride.
-// An element with p == 0 keeps g's bits (times row_w).
-int launch_from2d_penalized(int dtype, const float *in, int64_t stride2d, void *out_bct, const void *y_bct, int B, int Cn,
-                            int T, float scale, float pen_c2, const float *row_w, hipStream_t stream);
-int launch_round_penalized(int dtype, const float *in, void *out, int64_t n, const float *y, float pen_c2, const float *row_w,
-                           int cols, hipStream_t stream);
-int launch_penalize_rows(float *a, int64_t rows, int cols, const float *y, int64_t y_stride, float pen_c2,
-                         const float *row_w, hipStream_t stream);
+int launch_round(int dtype, const float *in, void *out, int64_t n, int cols, const LastPass &lp, hipStream_t stream);
+// in place on a contiguous float32 (rows, cols) matrix whose sign is final (scale 1): the 2-D float32 MMI gradient, which
+// the denominator and the numerator write straight into the caller's tensor.  Needs row_w or the penalty.
+int launch_scale_rows(float *a, int64_t rows, int cols, const LastPass &lp, hipStream_t stream);
 // layout_rows_kernels.hip (tc_chain_step_strided, TC_LAYOUT_CHANNEL_LAST): the row copies of a channel-last view, element
 // (b, c, t) at b*sb + t*st + c in a tensor of `dtype`.  Strides of size-1 dimensions are ignored; rows must not overlap.
 bool channel_last_strides_ok(int B, int T, int cols, int64_t sb, int64_t st);
 // out[(t*B + b) * out_stride + c] = widen(x[b*sb + t*st + c])
 int launch_rows_gather(int dtype, const void *x, int64_t sb, int64_t st, float *out, int64_t out_stride, int B, int T, int cols,
                        hipStream_t stream);
-// out[b*osb + t*ost + c] = in[(t*B + b) * in_stride + c] on its way out as the (B, C, T) copy back sends it (launch_from2d /
-// launch_from2d_penalized, operation for operation), rounded once: !scaled: as it is; scaled: scale * v, or with row_w
-// (scale * row_w[row]) * v; pen_c2 > 0 (scaled only): row_w[row] * penalize(scale * v, y) with y the element b*ysb + t*yst + c
-// of the network output `y` (of `dtype`).
-int launch_rows_scatter(int dtype, const float *in, int64_t in_stride, void *out, int64_t osb, int64_t ost, const void *y,
-                        int64_t ysb, int64_t yst, int B, int T, int cols, bool scaled, float scale, float pen_c2,
-                        const float *row_w, hipStream_t stream);
+// out[b*osb + t*ost + c] = in[(t*B + b) * in_stride + c] on its way out, rounded once
+int launch_rows_scatter(int dtype, const float *in, int64_t in_stride, void *out, int64_t osb, int64_t ost, int B, int T,
+                        int cols, const LastPass &lp, hipStream_t stream);
 
 extern thread_local int g_last_hip_error;
 

@@ -49,9 +49,38 @@ __device__ __forceinline__ float load_elem(const float *p, int64_t i) {
   return Elem<E>::widen(reinterpret_cast<const typename Elem<E>::bits *>(p)[i]);
 }
 
-// The two element functions of the passes that write a gradient last (layout_kernels.hip, penalty_kernels.hip,
-// layout_rows_kernels.hip).  One definition: a step returns the same bits in every layout because every such pass
-// forms its elements with these statements.
+// f(Tag<E>) with E the element type of a runtime TC_DTYPE_*; F32 false: the 16-bit types only
+template <typename E>
+struct Tag {
+  using type = E;
+};
+template <bool F32 = true, typename F>
+int with_elem(int dtype, F f) {
+  if constexpr (F32)
+    if (dtype == TC_DTYPE_F32) return f(Tag<float>{});
+  if (dtype == TC_DTYPE_BF16) return f(Tag<__hip_bfloat16>{});
+  if (dtype == TC_DTYPE_F16) return f(Tag<__half>{});
+  return TC_ERR_INVALID_ARGUMENT;
+}
+
+inline bool aligned(const void *p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
+
+// f(std::bool_constant...) of runtime bools: the template arguments of a kernel picked at its launch
+template <typename F>
+void with_bools(F f) {
+  f();
+}
+template <typename F, typename... B>
+void with_bools(F f, bool b, B... rest) {
+  if (b)
+    with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else
+    with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// The element functions of the passes that write a gradient last (layout_kernels.hip, layout_rows_kernels.hip).  One
+// definition: a step returns the same bits in every layout because every such pass forms its elements with these
+// statements.
 
 // w * v as a float32 value: the empty asm keeps the backend from fusing the multiply into the float16 conversion
 // (v_fma_mixlo_f16 rounds the exact product straight to 16 bits, and its + 0 addend turns a product of -0 into +0)
@@ -74,5 +103,47 @@ __device__ __forceinline__ float penalize(float g, float y, float c2) {
   asm volatile("" : "+v"(r));
   return p != 0.0f ? r : g;
 }
+
+// What a last pass does to an element v on its way out, in float32 (w: the factor of its row, y: its network output)
+//   kCopy  : nothing (the xent gradient, or values an earlier stage of the pass made final)
+//   kScale : scale * v
+//   kWeigh : (scale * w) * v
+// PEN (kScale / kWeigh): penalize(scale * v, y, c2), then times w -- the penalty precedes the weight, so the one factor
+// of kWeigh cannot be formed.  F32: the value is stored as float32; otherwise it is rounded to 16 bits next, and the
+// product is kept a float32 value (weigh).  A pass whose values carry their sign already passes scale = 1.0f, which
+// folds away.
+enum ScatterMode { kCopy = 0, kScale, kWeigh };
+template <int MODE, bool PEN, bool F32>
+__device__ __forceinline__ float last_elem(float v, float y, float w, float scale, float c2) {
+  static_assert(!(PEN && MODE == kCopy), "the penalty acts on the scaled MMI gradient");
+  if constexpr (MODE == kCopy) {
+    return v;
+  } else if constexpr (PEN) {
+    const float g = penalize(scale * v, y, c2);
+    return MODE == kWeigh ? weigh(w, g) : g;
+  } else if constexpr (MODE == kWeigh) {
+    const float f = scale * w;  // (the one factor of the element)
+    return F32 ? f * v : weigh(f, v);
+  } else {
+    // (16-bit: a float32 product on every path -- left to the backend, an element-wise path alone would fuse it into
+    // v_fma_mixlo_f16, whose + 0 addend turns a product of -0 into +0)
+    return F32 ? scale * v : weigh(scale, v);
+  }
+}
+
+// What a penalised pass takes beyond its plain form: the network output where the pass's output lies (stride: of its
+// rows, where the pass has rows) and c2 = fl32(2c).  Without the penalty it is empty and takes no kernel argument.
+template <bool PEN, typename Y>
+struct PenArgs {
+  const Y *y;
+  int64_t stride;
+  float c2;
+};
+template <typename Y>
+struct PenArgs<false, Y> {
+  static constexpr const Y *y = nullptr;
+  static constexpr int64_t stride = 0;
+  static constexpr float c2 = 0.0f;
+};
 
 }  // namespace tc

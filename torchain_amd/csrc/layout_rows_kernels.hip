@@ -4,10 +4,9 @@
 // a permuted row index, not transposes: no LDS, one wave per row at a time, 16-byte lanes where every address allows them.
 //   gather  : y2d[(t*B + b) * stride + c] = widen(x[b*sb + t*st + c])                      (float32 / bfloat16 / float16 in)
 //   scatter : out[b*osb + t*ost + c] = round(f(in2d[(t*B + b) * stride + c]))              (float32 in)
-// with f exactly what the (B, C, T) copy back computes (layout_kernels.hip: layout_kernel, penalty_kernels.hip:
-// from2d_penalized_kernel), operation for operation -- plain scale * v; with row weights (scale * w[row]) * v; with the
-// penalty w[row] * penalize(scale * v, y) -- so that a channel-last step returns the bits of the step on the contiguous copy.
-// A file of its own: no existing code object changes.
+// with f the element function of every last pass (half_io.h: last_elem), the one the (B, C, T) copy back calls -- plain
+// scale * v; with row weights (scale * w[row]) * v; with the penalty w[row] * penalize(scale * v, y) -- so that a channel-last
+// step returns the bits of the step on the contiguous copy.
 #include "chain_internal.h"
 #include "half_io.h"
 
@@ -16,8 +15,6 @@ namespace tc {
 namespace {
 
 constexpr int kRowsThreads = 256, kRowsBlocksMax = 4096;
-
-// (weigh and penalize, the element functions of the scatter: half_io.h)
 
 // elements a lane moves with one 16-byte access of the caller's tensor: 4 floats or 8 16-bit values
 template <typename E>
@@ -81,15 +78,8 @@ __global__ __launch_bounds__(kRowsThreads) void rows_gather_kernel(const typenam
   }
 }
 
-// what the scatter does to an element on its way out
-//   kCopy  : nothing (the xent gradient: the numerator wrote final values)
-//   kScale : scale * v
-//   kWeigh : (scale * row_w[row]) * v
-// PEN (kScale / kWeigh): penalize(scale * v, y, c2), then times row_w[row]; y = widen(yx[b*ysb + t*yst + c]), the network
-// output at the index the element is written to.
-enum ScatterMode { kCopy = 0, kScale, kWeigh };
-
-// in[(t*B + b) * in_stride + c] (float32) -> out[b*osb + t*ost + c] (E), rounded once.
+// in[(t*B + b) * in_stride + c] (float32) -> out[b*osb + t*ost + c] (E), each element as last_elem<MODE, PEN> sends it out,
+// rounded once.  PEN: y = widen(yx[b*ysb + t*yst + c]), the network output at the index the element is written to.
 // VEC: cols, osb, ost (PEN: ysb, yst too) multiples of Lane<E>::kN, in_stride a multiple of 4, all bases 16-byte aligned.
 template <typename E, bool VEC, int MODE, bool PEN>
 __global__ __launch_bounds__(kRowsThreads) void rows_scatter_kernel(const float *__restrict__ in, int64_t in_stride,
@@ -97,7 +87,6 @@ __global__ __launch_bounds__(kRowsThreads) void rows_scatter_kernel(const float 
                                                                     int64_t ost, const typename Elem<E>::bits *__restrict__ yx,
                                                                     int64_t ysb, int64_t yst, int B, int64_t rows, int cols,
                                                                     float scale, float c2, const float *__restrict__ row_w) {
-  static_assert(!(PEN && MODE == kCopy), "the penalty acts on the scaled MMI gradient");
   constexpr bool kF32 = std::is_same<E, float>::value;
   constexpr int kN = Lane<E>::kN;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -107,22 +96,7 @@ __global__ __launch_bounds__(kRowsThreads) void rows_scatter_kernel(const float 
     typename Elem<E>::bits *dst = out + b * osb + t * ost;
     const typename Elem<E>::bits *yr = PEN ? yx + b * ysb + t * yst : nullptr;
     const float w = MODE == kWeigh ? row_w[r] : 1.0f;
-    const float f = scale * w;  // (kWeigh without the penalty: the one factor of the element)
-    // element as it leaves, in float32
-    auto fin = [&](float v, float y) -> float {
-      if constexpr (MODE == kCopy) {
-        return v;
-      } else if constexpr (PEN) {
-        const float g = penalize(scale * v, y, c2);
-        return MODE == kWeigh ? weigh(w, g) : g;
-      } else if constexpr (MODE == kWeigh) {
-        return kF32 ? f * v : weigh(f, v);
-      } else {
-        // (16-bit: a float32 product on every path -- left to the backend, the element-wise path alone would fuse it into
-        // v_fma_mixlo_f16, whose + 0 addend turns a product of -0 into +0)
-        return kF32 ? scale * v : weigh(scale, v);
-      }
-    };
+    auto fin = [&](float v, float y) -> float { return last_elem<MODE, PEN, kF32>(v, y, w, scale, c2); };
     if (VEC) {
       for (int c = lane * kN; c < cols; c += 64 * kN) {
         float v[kN], y[kN] = {};
@@ -155,8 +129,6 @@ int rows_blocks(int64_t rows) {
   return (int)(b < 1 ? 1 : b > kRowsBlocksMax ? kRowsBlocksMax : b);
 }
 
-bool aligned(const void *p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
-
 template <typename E>
 int launch_rows_gather_e(const void *x_v, int64_t sb, int64_t st, float *out, int64_t out_stride, int B, int T, int cols,
                          hipStream_t stream) {
@@ -168,53 +140,38 @@ int launch_rows_gather_e(const void *x_v, int64_t sb, int64_t st, float *out, in
   // (a stride of a size-1 dimension is never multiplied by anything but 0)
   const bool vec = cols % kN == 0 && (B == 1 || sb % kN == 0) && (T == 1 || st % kN == 0) && out_stride % 4 == 0 &&
                    aligned(x_v, 16) && aligned(out, 16);
-  if (vec)
-    hipLaunchKernelGGL((rows_gather_kernel<E, true>), blocks, threads, 0, stream, x, sb, st, out, out_stride, B, rows, cols);
-  else
-    hipLaunchKernelGGL((rows_gather_kernel<E, false>), blocks, threads, 0, stream, x, sb, st, out, out_stride, B, rows, cols);
+  with_bools(
+      [&](auto v) {
+        hipLaunchKernelGGL((rows_gather_kernel<E, decltype(v)::value>), blocks, threads, 0, stream, x, sb, st, out, out_stride, B,
+                           rows, cols);
+      },
+      vec);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }
 
-template <typename E, bool VEC>
-void launch_rows_scatter_v(int mode, bool pen, dim3 blocks, hipStream_t stream, const float *in, int64_t in_stride,
-                           typename Elem<E>::bits *out, int64_t osb, int64_t ost, const typename Elem<E>::bits *y, int64_t ysb,
-                           int64_t yst, int B, int64_t rows, int cols, float scale, float c2, const float *row_w) {
-  const dim3 threads(kRowsThreads);
-#define TC_ROWS_SCATTER(MODE, PEN)                                                                                      \
-  hipLaunchKernelGGL((rows_scatter_kernel<E, VEC, MODE, PEN>), blocks, threads, 0, stream, in, in_stride, out, osb, ost, y, \
-                     ysb, yst, B, rows, cols, scale, c2, row_w)
-  if (mode == kCopy)
-    TC_ROWS_SCATTER(kCopy, false);
-  else if (mode == kScale && !pen)
-    TC_ROWS_SCATTER(kScale, false);
-  else if (mode == kScale)
-    TC_ROWS_SCATTER(kScale, true);
-  else if (!pen)
-    TC_ROWS_SCATTER(kWeigh, false);
-  else
-    TC_ROWS_SCATTER(kWeigh, true);
-#undef TC_ROWS_SCATTER
-}
-
 template <typename E>
-int launch_rows_scatter_e(const float *in, int64_t in_stride, void *out_v, int64_t osb, int64_t ost, const void *y_v,
-                          int64_t ysb, int64_t yst, int B, int T, int cols, int mode, float scale, float c2,
-                          const float *row_w, hipStream_t stream) {
+int launch_rows_scatter_e(const float *in, int64_t in_stride, void *out_v, int64_t osb, int64_t ost, int B, int T, int cols,
+                          const LastPass &lp, hipStream_t stream) {
   using bits = typename Elem<E>::bits;
   constexpr int kN = Lane<E>::kN;
   bits *out = static_cast<bits *>(out_v);
-  const bits *y = static_cast<const bits *>(y_v);
-  const bool pen = y != nullptr;
-  const int64_t rows = (int64_t)B * T;
-  const dim3 blocks(rows_blocks(rows));
+  const bool pen = lp.pen_c2 > 0.0f;
+  const bits *y = pen ? static_cast<const bits *>(lp.y) : nullptr;
+  const int64_t rows = (int64_t)B * T, ysb = lp.y_stride, yst = lp.y_st;
+  const dim3 blocks(rows_blocks(rows)), threads(kRowsThreads);
   const bool vec = cols % kN == 0 && (B == 1 || osb % kN == 0) && (T == 1 || ost % kN == 0) && in_stride % 4 == 0 &&
                    aligned(in, 16) && aligned(out_v, 16) &&
-                   (!pen || ((B == 1 || ysb % kN == 0) && (T == 1 || yst % kN == 0) && aligned(y_v, 16)));
-  if (vec)
-    launch_rows_scatter_v<E, true>(mode, pen, blocks, stream, in, in_stride, out, osb, ost, y, ysb, yst, B, rows, cols, scale, c2, row_w);
-  else
-    launch_rows_scatter_v<E, false>(mode, pen, blocks, stream, in, in_stride, out, osb, ost, y, ysb, yst, B, rows, cols, scale, c2, row_w);
+                   (!pen || ((B == 1 || ysb % kN == 0) && (T == 1 || yst % kN == 0) && aligned(y, 16)));
+  with_bools(
+      [&](auto v, auto scaled, auto weighted, auto p) {
+        constexpr bool kScaled = decltype(scaled)::value, kW = decltype(weighted)::value, kPen = decltype(p)::value;
+        constexpr int kMode = !kScaled ? kCopy : (kW ? kWeigh : kScale);
+        if constexpr (kScaled || !(kW || kPen))
+          hipLaunchKernelGGL((rows_scatter_kernel<E, decltype(v)::value, kMode, kPen>), blocks, threads, 0, stream, in, in_stride,
+                             out, osb, ost, y, ysb, yst, B, rows, cols, lp.scale, lp.pen_c2, lp.row_w);
+      },
+      vec, lp.scaled, lp.row_w != nullptr, pen);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }
@@ -235,33 +192,21 @@ int launch_rows_gather(int dtype, const void *x, int64_t sb, int64_t st, float *
                        hipStream_t stream) {
   if (!x || !out || out_stride < cols || !channel_last_strides_ok(B, T, cols, sb, st)) return TC_ERR_INVALID_ARGUMENT;
   count_launch(kCntLayout);
-  switch (dtype) {
-    case TC_DTYPE_F32: return launch_rows_gather_e<float>(x, sb, st, out, out_stride, B, T, cols, stream);
-    case TC_DTYPE_BF16: return launch_rows_gather_e<__hip_bfloat16>(x, sb, st, out, out_stride, B, T, cols, stream);
-    case TC_DTYPE_F16: return launch_rows_gather_e<__half>(x, sb, st, out, out_stride, B, T, cols, stream);
-  }
-  return TC_ERR_INVALID_ARGUMENT;
+  return with_elem(dtype, [&](auto e) {
+    return launch_rows_gather_e<typename decltype(e)::type>(x, sb, st, out, out_stride, B, T, cols, stream);
+  });
 }
 
-int launch_rows_scatter(int dtype, const float *in, int64_t in_stride, void *out, int64_t osb, int64_t ost, const void *y,
-                        int64_t ysb, int64_t yst, int B, int T, int cols, bool scaled, float scale, float pen_c2,
-                        const float *row_w, hipStream_t stream) {
+int launch_rows_scatter(int dtype, const float *in, int64_t in_stride, void *out, int64_t osb, int64_t ost, int B, int T,
+                        int cols, const LastPass &lp, hipStream_t stream) {
   if (!in || !out || in_stride < cols || !channel_last_strides_ok(B, T, cols, osb, ost)) return TC_ERR_INVALID_ARGUMENT;
-  const bool pen = pen_c2 > 0.0f;
-  if (pen && (!y || !scaled || !channel_last_strides_ok(B, T, cols, ysb, yst))) return TC_ERR_INVALID_ARGUMENT;
-  if (!scaled && row_w) return TC_ERR_INVALID_ARGUMENT;
-  const int mode = !scaled ? kCopy : (row_w ? kWeigh : kScale);
-  const void *yp = pen ? y : nullptr;
+  if (lp.pen_c2 > 0.0f && (!lp.y || !lp.scaled || !channel_last_strides_ok(B, T, cols, lp.y_stride, lp.y_st)))
+    return TC_ERR_INVALID_ARGUMENT;
+  if (!lp.scaled && lp.row_w) return TC_ERR_INVALID_ARGUMENT;
   count_launch(kCntLayout);
-  switch (dtype) {
-    case TC_DTYPE_F32:
-      return launch_rows_scatter_e<float>(in, in_stride, out, osb, ost, yp, ysb, yst, B, T, cols, mode, scale, pen_c2, row_w, stream);
-    case TC_DTYPE_BF16:
-      return launch_rows_scatter_e<__hip_bfloat16>(in, in_stride, out, osb, ost, yp, ysb, yst, B, T, cols, mode, scale, pen_c2, row_w, stream);
-    case TC_DTYPE_F16:
-      return launch_rows_scatter_e<__half>(in, in_stride, out, osb, ost, yp, ysb, yst, B, T, cols, mode, scale, pen_c2, row_w, stream);
-  }
-  return TC_ERR_INVALID_ARGUMENT;
+  return with_elem(dtype, [&](auto e) {
+    return launch_rows_scatter_e<typename decltype(e)::type>(in, in_stride, out, osb, ost, B, T, cols, lp, stream);
+  });
 }
 
 }  // namespace tc
