@@ -276,7 +276,9 @@ int64_t tc_chain_workspace_bytes(const tc_den_graph *graph, int32_t num_sequence
  *   objf = w*num - w*den;  weight = w*S*T;  l2_term = -0.5*w*l2*sum(y^2)
  *   deriv = w*gamma_num - w*gamma_den - w*l2*y      (written, not accumulated; may be NULL)
  *   xent_deriv = w*gamma_num                        (written when non-NULL)
- * and on NaN/inf or a failed alpha.beta check: deriv = xent_deriv = 0, objf = -10*weight.
+ * and on NaN/inf or a failed alpha.beta check: deriv = xent_deriv = 0, objf = -10*weight.  Any NaN or +-inf element of
+ * nnet_output fails the call, whichever denominator kernel runs and whether or not an arc carries its pdf; so does a finite
+ * element whose square overflows float32 (|y| above about 1.8e19): the failure is carried by the sequence's sum of y^2.
  * results_dev3 is DEVICE memory for {objf, l2_term, weight} (the reference writes a CPU
  * THFloatTensor, src/my_lib_chain.cpp:126,130; the host wrapper copies the 12 bytes).
  * Stream capture: this call, tc_chain_objf_and_grad, tc_chain_step and tc_den_forward_backward may be captured in a HIP

@@ -68,6 +68,29 @@ def hip_den(fst, y, S, leaky=1e-5, deriv_weight=1.0, l2_scale=0.0, accumulate=Fa
                 graph=graph)
 
 
+def hip_den_on(graph, S, yt, deriv=None, leaky=0.1, deriv_weight=1.0, l2_scale=0.0, accumulate=False):
+    """tc_den_forward_backward on device tensors where they lie: ``yt`` and ``deriv`` (or None: the forward-only call) are
+    (rows, cols) float32 views with unit column stride and any row stride and base address; ``deriv`` is written in place.
+    Returns dict(logprob, status)."""
+    rows, cols = yt.shape
+    assert yt.is_cuda and yt.dtype == torch.float32 and yt.stride(1) == 1
+    assert deriv is None or (deriv.shape == yt.shape and deriv.dtype == torch.float32 and deriv.stride(1) == 1)
+    graph.prepare(yt.device)
+    nbytes = lib.tc_chain_workspace_bytes(graph.ptr, S, rows // S)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=yt.device)
+    lp = torch.zeros(1, dtype=torch.float64, device=yt.device)
+    st = torch.full((1,), -1, dtype=torch.int32, device=yt.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = lib.tc_den_forward_backward(
+        graph.ptr, S, C.c_void_p(yt.data_ptr()), rows, cols, yt.stride(0), leaky, deriv_weight, l2_scale,
+        1 if accumulate else 0, C.c_void_p(deriv.data_ptr()) if deriv is not None else None,
+        deriv.stride(0) if deriv is not None else cols, C.c_void_p(lp.data_ptr()), C.c_void_p(st.data_ptr()),
+        C.c_void_p(ws.data_ptr()), nbytes, torch.cuda.current_device(), C.c_void_p(stream))
+    check(rc, "tc_den_forward_backward")
+    torch.cuda.synchronize()
+    return dict(logprob=float(lp.item()), status=int(st.item()))
+
+
 def hip_num(sup, y, want_deriv=True, device="cuda:0", init=0.0):
     """Runs tc_num_forward_backward; returns dict(logprob_weighted, deriv).  ``sup``: a ``synth.SupFst`` or a handle
     (``io.Supervision``, end-to-end ones included); ``init``: what the derivative matrix holds before the call adds to it."""

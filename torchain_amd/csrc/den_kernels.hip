@@ -266,7 +266,7 @@ __global__ __launch_bounds__(kThreads) void den_fwd_bwd_kernel(const DenParams p
   {
     const double y2d = (double)block_sum(y2, red + 2 * kWaves, wave, lane);
     if (tid == 0) {
-      p.seq_logprob[s] = logsum + (double)__logf(tot);
+      p.seq_logprob[s] = logsum + (double)__logf(tot) + (y2d - y2d);  // (+ 0, or NaN for a NaN / inf input: exp_limited clamps +-inf)
       p.seq_y2[s] = y2d;
     }
   }

@@ -381,7 +381,7 @@ __global__ __launch_bounds__(kBT) void slab_total_kernel(const DenParams p) {
   p.seq_y2[s] = y2;
   double lp = (double)__logf(tot);
   for (int t = 0; t < p.T; ++t) lp += (double)__logf(sm.asum[(int64_t)t * Sp + s]);
-  p.seq_logprob[s] = lp;
+  p.seq_logprob[s] = lp + (y2 - y2);  // (+ 0, or NaN for a NaN / inf input: big_exp clamps +-inf, and no arc may carry the pdf)
 }
 
 template <int G>
