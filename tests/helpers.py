@@ -246,11 +246,17 @@ def compare_at_size(oracle, cfg, S, T, seed, expect_tied):
     assert out["graph"].stats()["tied"] == expect_tied, out["graph"].stats()
     assert out["status"] == 0
     ref_lp, ref = oracle_den(oracle, fst, y, S, T, c["leaky"])
-    assert abs(out["logprob"] - ref_lp) <= REL * abs(ref_lp), (out["logprob"], ref_lp)
-    assert rel_err(out["deriv"], ref, floor=1.0) <= REL
-    elementwise(out["deriv"], ref, "%s %dx%d" % (cfg, S, T))
-    rows = out["deriv"].sum(axis=1, dtype=np.float64)
-    assert np.abs(rows - 1.0).max() <= 1e-4, np.abs(rows - 1.0).max()
+    check_den_at_size(out["logprob"], out["deriv"], ref_lp, ref, "%s %dx%d" % (cfg, S, T))
+
+
+def check_den_at_size(logprob, deriv, ref_lp, ref, what):
+    """A denominator at size against the CPU oracle on all sequences, deriv_weight 1: log-prob 1e-4 relative, derivative
+    max |d - ref| <= 1e-4 * max(max |ref|, 1) and element-wise (``elementwise``), rows summing to 1 within 1e-4."""
+    assert abs(logprob - ref_lp) <= REL * abs(ref_lp), (what, logprob, ref_lp)
+    assert rel_err(deriv, ref, floor=1.0) <= REL, what
+    elementwise(deriv, ref, what)
+    rows = deriv.sum(axis=1, dtype=np.float64)
+    assert np.abs(rows - 1.0).max() <= 1e-4, (what, np.abs(rows - 1.0).max())
 
 
 @functools.lru_cache(maxsize=None)
