@@ -116,8 +116,35 @@ int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t num_se
                               int32_t label_dim, const int32_t *seq_state_begin, const int32_t *start,
                               const int32_t *arc_begin, const int32_t *arc_ilabel, const float *arc_weight,
                               const int32_t *arc_nextstate, const float *final_weight);
-/* 1 for a handle of tc_supervision_create_e2e, else 0. */
+/* 1 for a handle of tc_supervision_create_e2e or tc_supervision_create_e2e_ragged, else 0. */
 int32_t tc_supervision_is_e2e(const tc_supervision *supervision);
+
+/* End-to-end minibatch of UNEQUAL sequence lengths ("ragged"): tc_supervision_create_e2e with one frame count per
+ * sequence, frames_per_sequence[s] >= 1 (host memory, num_sequences entries; a smaller entry: TC_ERR_INVALID_ARGUMENT).
+ * T = the longest length is the handle's tc_supervision_num_frame and the T of every tensor shape, row count
+ * (num_rows = num_sequences * T, row t * num_sequences + s), workspace size and of the size limits above; frames
+ * t >= frames_per_sequence[s] of sequence s are PADDING.  Every entry that takes a supervision takes such a handle:
+ *   - nothing in the padding of an input influences any output (NaN and inf included);
+ *   - every padding element of an output (deriv, xent_deriv, grad, xent_grad, in every layout and dtype, with
+ *     deriv_weights, with the out-of-range penalty, on the soft-failure route) is +0.0;
+ *   - the objective's weight is weight * sum of the lengths, its failure value -10 times that, the l2 term sums over the
+ *     sequences' own frames; a sequence with no path of exactly its own number of arcs fails the minibatch softly.
+ * The lengths travel to the device with the tables (no allocation, no synchronisation once the pool is warm; the step
+ * stays capturable).  The denominator takes the one-workgroup-per-sequence kernel of the graph's class whatever the batch
+ * size -- the two-workgroup forms of small batches and the two-sequence kernel are not taken -- and a graph on the streamed
+ * path (tc_den_graph_stats) is refused: TC_ERR_UNSUPPORTED from every entry, before anything is launched.  A handle made
+ * here is ragged also when all its lengths are equal; tc_supervision_create_e2e's handles are untouched.
+ * tc_supervision_frames: the num_sequences lengths (all equal to tc_supervision_num_frame for any other handle) into host
+ * memory.  tc_supervision_is_ragged: 1 for a handle of tc_supervision_create_e2e_ragged, else 0.
+ * tc_debug_counter("ragged_steps") counts the objective calls made on a ragged handle.
+ * Regular (merged-FST) supervisions have one frames_per_sequence, as [K] Supervision has: no ragged form. */
+int tc_supervision_create_e2e_ragged(tc_supervision **out, float weight, int32_t num_sequences,
+                                     const int32_t *frames_per_sequence, int32_t label_dim,
+                                     const int32_t *seq_state_begin, const int32_t *start, const int32_t *arc_begin,
+                                     const int32_t *arc_ilabel, const float *arc_weight, const int32_t *arc_nextstate,
+                                     const float *final_weight);
+int tc_supervision_frames(const tc_supervision *supervision, int32_t *frames_host);
+int32_t tc_supervision_is_ragged(const tc_supervision *supervision);
 
 /* Merges the supervision FSTs of a minibatch's examples into the one acceptor tc_supervision_create takes: what the
  * reference reaches natively through kaldi::nnet3::MergeChainExamples -> [K] chain::AppendSupervision
@@ -488,6 +515,20 @@ int tc_den_forward_backward(tc_den_graph *graph, int32_t num_sequences, const fl
                             float *deriv, int64_t deriv_stride, double *logprob_dev, int32_t *status_dev,
                             void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* tc_den_forward_backward on a ragged batch: seq_frames_dev[s] (DEVICE memory, int32, num_sequences entries, 4-byte
+ * aligned) frames of sequence s, max_frames the longest and num_rows == max_frames * num_sequences.  A sequence reads and
+ * writes rows t * num_sequences + s of its own frames only; with accumulate == 0 the derivative's padding rows are +0,
+ * with accumulate != 0 they are not touched.  Entries outside 1 .. max_frames are taken as the nearer bound.  logprob_dev:
+ * the sum of the sequences' log-probs over their own frames.  The workspace is tc_chain_workspace_bytes(graph,
+ * num_sequences, max_frames).  The kernel is the graph class's one-workgroup-per-sequence form whatever the batch size and
+ * the launch switches; TC_ERR_UNSUPPORTED for a graph on the streamed path (nothing is launched or written). */
+int tc_den_forward_backward_ragged(tc_den_graph *graph, int32_t num_sequences, const float *nnet_output,
+                                   int64_t num_rows, int32_t num_cols, int64_t row_stride,
+                                   float leaky_hmm_coefficient, float deriv_weight, float l2_scale, int accumulate,
+                                   float *deriv, int64_t deriv_stride, const int32_t *seq_frames_dev, int32_t max_frames,
+                                   double *logprob_dev, int32_t *status_dev, void *workspace, int64_t workspace_bytes,
+                                   int device, void *stream);
+
 /* [K] NumeratorComputation::Forward() + Backward() (src/chain-supervision-test.hpp:99-107):
  *   logprob_dev : device double[1] = weight * log Z_num
  *   deriv       : nullable; deriv[row, pdf] += weight * occupation at the supervision's (row, pdf)s */
@@ -628,7 +669,8 @@ int tc_debug_set(const char *key, int value);
  * numerator launches that ran beside the denominator and left their posteriors for the scatter kernel;
  * "num_windowed_launches" = regular numerator launches that took the level-windowed kernel (counted in "num_launches" too);
  * "channel_last_steps" = tc_chain_step_strided calls taken in TC_LAYOUT_CHANNEL_LAST (their row gathers and scatters, and
- * tc_rows_gather / tc_rows_scatter, count as "layout_launches").
+ * tc_rows_gather / tc_rows_scatter, count as "layout_launches"); "ragged_steps" = objective calls made on a ragged
+ * supervision (tc_supervision_create_e2e_ragged; their padding kernels are not counted as "layout_launches").
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -108,6 +108,12 @@ def _load():
     L.tc_supervision_create_e2e.argtypes = [C.POINTER(vp), f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.tc_supervision_is_e2e.restype = i32
     L.tc_supervision_is_e2e.argtypes = [vp]
+    L.tc_supervision_create_e2e_ragged.restype = C.c_int
+    L.tc_supervision_create_e2e_ragged.argtypes = [C.POINTER(vp), f32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tc_supervision_frames.restype = C.c_int
+    L.tc_supervision_frames.argtypes = [vp, vp]
+    L.tc_supervision_is_ragged.restype = i32
+    L.tc_supervision_is_ragged.argtypes = [vp]
     L.tc_example_output_e2e.restype = C.c_int
     L.tc_example_output_e2e.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.tc_rand_reader_new.restype = C.c_int
@@ -176,6 +182,9 @@ def _load():
     L.tc_den_forward_backward.restype = C.c_int
     L.tc_den_forward_backward.argtypes = [vp, i32, vp, i64, i32, i64, f32, f32, f32, C.c_int, vp, i64, vp, vp, vp,
                                           i64, C.c_int, vp]
+    L.tc_den_forward_backward_ragged.restype = C.c_int
+    L.tc_den_forward_backward_ragged.argtypes = [vp, i32, vp, i64, i32, i64, f32, f32, f32, C.c_int, vp, i64, vp, i32, vp, vp,
+                                                 vp, i64, C.c_int, vp]
     L.tc_xent_objf.restype = C.c_int
     L.tc_xent_objf.argtypes = [vp, i64, i32, i64, vp, i64, vp, vp, i64, C.c_int, vp]
     L.tc_num_forward_backward.restype = C.c_int

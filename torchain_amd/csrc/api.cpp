@@ -124,8 +124,11 @@ struct DeviceGuard {
 
 int fill_den_params(tc_den_graph *g, int device, int32_t S, const float *y, int64_t rows, int32_t cols,
                     int64_t y_stride, float leaky, float deriv_weight, float l2_scale, float *deriv,
-                    int64_t deriv_stride, const Workspace &w, DenParams *p, const DenGraphDev *tuning = nullptr) {
+                    int64_t deriv_stride, const Workspace &w, DenParams *p, const DenGraphDev *tuning = nullptr,
+                    const int32_t *seq_frames = nullptr) {
   if (!g || !y || S <= 0 || rows <= 0 || rows % S != 0) return TC_ERR_INVALID_ARGUMENT;
+  // a ragged batch on a graph of the streamed path (lanes run over sequences: one frame count), before anything is launched
+  if (seq_frames && g->big) return TC_ERR_UNSUPPORTED;
   if (cols != g->P || y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
   if (deriv && deriv_stride < cols) return TC_ERR_INVALID_ARGUMENT;
   if (!(leaky > 0.0f && leaky < 1.0f)) return TC_ERR_INVALID_ARGUMENT;  // [K] KALDI_ASSERT in the ctor
@@ -197,6 +200,7 @@ int fill_den_params(tc_den_graph *g, int device, int32_t S, const float *y, int6
   p->stamps = (long long *)w.scalar;
   p->y_vec = (cols % 4 == 0 && y_stride % 4 == 0 && aligned16(y)) ? 1 : 0;
   p->d_vec = (deriv && cols % 4 == 0 && deriv_stride % 4 == 0 && aligned16(deriv)) ? 1 : 0;
+  p->set_seq_frames(seq_frames);
   return TC_OK;
 }
 
@@ -211,6 +215,7 @@ int fill_num_params(tc_supervision *sup, int device, hipStream_t stream, const f
   {
     std::lock_guard<std::mutex> lock(sup->mu);
     p->t = sup->dev[device];
+    if (!sup->frames.empty()) p->seq_frames = sup->frames_dev[device];  // (in the same pool slot, uploaded with the tables)
   }
   p->y = y;
   p->y_stride = y_stride;
@@ -422,6 +427,36 @@ int tc_den_forward_backward(tc_den_graph *g, int32_t S, const float *y, int64_t 
   return rc;
 }
 
+int tc_den_forward_backward_ragged(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols,
+                                   int64_t y_stride, float leaky, float deriv_weight, float l2_scale, int accumulate,
+                                   float *deriv, int64_t deriv_stride, const int32_t *seq_frames_dev, int32_t max_frames,
+                                   double *logprob_dev, int32_t *status_dev, void *workspace, int64_t workspace_bytes,
+                                   int device, void *stream_v) {
+  if (!g || S <= 0 || rows <= 0 || !seq_frames_dev || max_frames <= 0 || rows != (int64_t)max_frames * S)
+    return TC_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)seq_frames_dev & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
+  if (g->big) return TC_ERR_UNSUPPORTED;  // (the streamed path: fill_den_params says why)
+  const int T = max_frames;
+  Workspace w = carve((char *)workspace, hist_states(g), S, T, big_p(g), big_h(g), big_g(g), big_hb(g), split_room(g, S), pair_room(g), planes_room(g));
+  if (!workspace || (int64_t)w.total > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  hipStream_t stream = (hipStream_t)stream_v;
+  DenParams p;
+  int rc = fill_den_params(g, device, S, y, rows, cols, y_stride, leaky, deriv_weight, l2_scale, deriv, deriv_stride, w,
+                           &p, nullptr, seq_frames_dev);
+  if (rc != TC_OK) return rc;
+  rc = launch_den_mode(p, accumulate, stream);
+  if (rc != TC_OK) return rc;
+  // the kernels touch no padding row: written mode leaves +0 there, Kaldi's accumulating mode leaves them alone
+  if (deriv && !accumulate)
+    rc = launch_zero_padding(deriv, 4, deriv_stride, (int64_t)S * deriv_stride, 1, S, T, cols, seq_frames_dev, stream);
+  if (rc != TC_OK) return rc;
+  if (logprob_dev || status_dev)
+    rc = launch_den_reduce(w.den_lp, deriv ? w.ab : nullptr, w.gs, S, logprob_dev, status_dev, stream);
+  return rc;
+}
+
 int tc_num_forward_backward(tc_supervision *sup, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
                             float *deriv, int64_t deriv_stride, double *logprob_dev, void *workspace,
                             int64_t workspace_bytes, int device, void *stream_v) {
@@ -459,6 +494,8 @@ struct ObjfStep {  // what only the one-call step passes: all unset for the two 
   float *loss_dev1 = nullptr;
   int xent_bct = 0, xent_out_bct = 0, bct_dtype = TC_DTYPE_F32;
   bool xent_sums_ready = false;  // (the numerator-only pass of kaldi_way == 0 has left the sequences' xent sums)
+  // the step moves deriv / xent on (emit_gradients) and zeroes a ragged minibatch's padding in the caller's tensors itself
+  bool outputs_move_on = false;
 };
 
 static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int64_t rows, int32_t cols,
@@ -480,12 +517,20 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   int rc = fill_den_params(g, device, sup->S, y, rows, cols, y_stride, leaky, deriv_scale * -wgt,
                            deriv_scale * (wgt * l2_regularize), deriv, deriv_stride, w, &dp);
   if (rc != TC_OK) return rc;
+  // A ragged supervision: its lengths, in the pool slot with its tables, are the denominator's loop bounds too (the
+  // numerator's upload below is enqueued on this stream in front of both).  The kernels touch no padding row.
+  const bool ragged = !sup->frames.empty();
+  if (ragged && g->big) return TC_ERR_UNSUPPORTED;
   NumParams np;
   rc = fill_num_params(sup, device, stream, y, rows, cols, y_stride, deriv, deriv_stride, xent, xent_stride, w.num_lp,
                        &np);
   if (rc != TC_OK) return rc;
   np.deriv_scale = deriv_scale;
   np.xent_scale = xent_scale;
+  if (ragged) {
+    dp.set_seq_frames(np.seq_frames);
+    count_launch(kCntRagged);
+  }
   if (o.xent_out && o.xent_objf_dev) {  // (also without the dense xent matrix: an evaluation step's cross-entropy objective)
     np.xent_out = o.xent_out;
     np.xent_out_stride = o.xent_out_stride;
@@ -559,11 +604,17 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   if (rc != TC_OK) return rc;
   rc = launch_finalize(w.den_lp, w.num_lp, w.y2, w.ab, w.gs, sup->S, sup->T, wgt, l2_regularize, deriv != nullptr,
                        results_dev3, w.fail, stream, (np.seq_xent || o.xent_sums_ready) && o.xent_objf_dev ? w.xent_lp : nullptr,
-                       o.xent_objf_dev, o.loss_dev1);
+                       o.xent_objf_dev, o.loss_dev1, ragged ? sup->total_frames : 0);
   if (rc != TC_OK) return rc;
   // (a (B, C, T) xent tensor is rows * cols contiguous floats: cleared as such)
-  return launch_zero_on_fail(w.fail, deriv, deriv_stride, xent, o.xent_bct ? (int64_t)cols : xent_stride, y, y_stride,
-                             deriv_scale * (wgt * l2_regularize), rows, cols, stream);
+  rc = launch_zero_on_fail(w.fail, deriv, deriv_stride, xent, o.xent_bct ? (int64_t)cols : xent_stride, y, y_stride,
+                           deriv_scale * (wgt * l2_regularize), rows, cols, stream);
+  // ragged: +0 in the padding rows, which no kernel wrote (and the failure route just filled from y's padding)
+  if (rc == TC_OK && ragged && !o.outputs_move_on) {
+    if (deriv) rc = launch_zero_padding(deriv, 4, deriv_stride, (int64_t)sup->S * deriv_stride, 1, sup->S, sup->T, cols, np.seq_frames, stream);
+    if (rc == TC_OK && xent) rc = launch_zero_padding(xent, 4, xent_stride, (int64_t)sup->S * xent_stride, 1, sup->S, sup->T, cols, np.seq_frames, stream);
+  }
+  return rc;
 }
 
 extern "C" {
@@ -818,11 +869,27 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   o.loss_dev1 = loss_dev1;  // (the loss value -objf / weight is written with the results: finalize_kernel)
   o.bct_dtype = dtype;
   o.xent_row_w = row_w;
+  o.outputs_move_on = true;
   rc = chain_objf(g, sup, io.y, rows, P, io.y_stride, results_dev3, io.gr, P, io.xg, P, l2_regularize, leaky, dscale, xscale,
                   w.chain, (int64_t)w.chain_bytes, device, stream_v, o);
   if (rc != TC_OK || eval_only) return rc;
-  return emit_gradients(io, layout, dtype, input, row_stride, sb, st, grad, xent_grad, w.y2d, S, T, P, pen_c2, row_w, device,
-                        stream_v);
+  rc = emit_gradients(io, layout, dtype, input, row_stride, sb, st, grad, xent_grad, w.y2d, S, T, P, pen_c2, row_w, device,
+                      stream_v);
+  if (rc != TC_OK || sup->frames.empty()) return rc;
+  // A ragged minibatch: the objective wrote no padding row, the last passes moved whatever lay there; +0 into the padding
+  // of the caller's gradients, each where its layout puts element (sequence, frame, channel).  (The (B, C, T) xent gradient
+  // was cleared on the way in and has entries only at the numerator's posteriors.)
+  const int32_t *frames_dev = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(sup->mu);
+    frames_dev = sup->frames_dev[device];
+  }
+  const bool bct = layout == TC_LAYOUT_BCT;
+  const int eb = half ? 2 : 4;
+  const int64_t zb = bct || cl ? (int64_t)T * P : (int64_t)P, zt = bct ? 1 : (cl ? (int64_t)P : (int64_t)S * P), zc = bct ? T : 1;
+  rc = launch_zero_padding(grad, eb, zb, zt, zc, S, T, P, frames_dev, stream);
+  if (rc == TC_OK && xent_grad && use_xent && !bct) rc = launch_zero_padding(xent_grad, eb, zb, zt, zc, S, T, P, frames_dev, stream);
+  return rc;
 }
 
 int tc_chain_step(tc_den_graph *g, tc_supervision *sup, const float *input, const float *xent_input, int three_d,

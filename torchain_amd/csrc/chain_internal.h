@@ -211,6 +211,7 @@ struct DenParams {
   int S, T, H, P;
   float leaky, deriv_weight, l2_scale;
   int y_vec, d_vec;     // rows 16-byte aligned -> float4 path
+  uint32_t seq_frames_lo = 0;  // (seq_frames() below)
   // The cross-entropy output's derivative is zero outside the numerator's posteriors: kernels that write every
   // derivative row anyway (den_tied_frames.h) also write its zero rows, so that the objective call needs no memset of
   // the whole matrix in front of them (629 MB at C3: 0.13 ms).  Null: the caller has zeroed it.
@@ -221,6 +222,7 @@ struct DenParams {
   const uint32_t *tied_fs;  // non-null selects the tied-graph kernel (see tc_den_graph below)
   const float *tied_w;
   int gen_owner = 0;        // general graph on owner-computes schedules: den_general_owner.hip
+  uint32_t seq_frames_hi = 0;
   BigDev big;           // streamed path only
   float *big_expy;      // [slab][P][16]  exp(y_t) of the current frame, transposed; or [T][slab][P][16], every frame (big_exp_stride)
   int64_t big_exp_stride = 0;  // floats between consecutive frames of big_expy (0: one frame at a time)
@@ -244,7 +246,29 @@ struct DenParams {
   int pair_extra_slots = 0;     // secondary-row slots of the graph's schedules (LDS layout of the pair kernel)
   int pair_choice = 0;        // the graph's tuned choice (DenGraphDev::pair_choice > 0)
   uint32_t *mitm_sync = nullptr;  // den_tied_mitm.hip: ticket + hand-over words (workspace of batches the two-CU forms may take)
+  // Ragged minibatch (tc_den_forward_backward_ragged, a ragged end-to-end supervision): [S] frames of each sequence, device
+  // memory.  T above stays the longest (row count, history, frame sums, LDS layout); the one-workgroup-per-sequence kernels'
+  // RAGGED instantiations read their loop bound here.  Null: every sequence has T frames.  The pointer travels as two
+  // 32-bit halves in what were the structure's two padding words: a new 8-byte member would move whatever follows the
+  // structure among a kernel's arguments (den_tied_planes_mitm_kernel has a second one), and the uniform instantiations
+  // keep their instruction streams to the byte (profiles/ragged/kernel_isa.txt).
+  __host__ __device__ const int32_t *seq_frames() const {
+    return reinterpret_cast<const int32_t *>(((uint64_t)seq_frames_hi << 32) | seq_frames_lo);
+  }
+  void set_seq_frames(const int32_t *f) {
+    seq_frames_lo = (uint32_t)(uintptr_t)f;
+    seq_frames_hi = (uint32_t)((uint64_t)(uintptr_t)f >> 32);
+  }
 };
+
+// a ragged batch's loop bound of sequence s, held to 1 .. T: tc_den_forward_backward_ragged's lengths are device memory that
+// no host code has seen, and a bound outside that range would address rows outside the caller's tensors
+// (readfirstlane: DenParams rebuilds the pointer from two integers, so the compiler takes the load for a per-lane one; the
+// bound must be a scalar or every frame loop's control becomes vector code)
+__device__ __forceinline__ int ragged_frames(const int32_t *seq_frames, int s, int T) {
+  const int f = __builtin_amdgcn_readfirstlane(seq_frames[s]);
+  return f < 1 ? 1 : (f > T ? T : f);
+}
 
 }  // namespace tc
 
@@ -415,6 +439,9 @@ struct NumParams {
   // t*S + s): xent[...] = xent_row_w[row] * (xent_scale * v).  seq_xent keeps summing the unweighted xent_scale * v, and
   // deriv is not weighted here.  Null: no factor.
   const float *xent_row_w = nullptr;
+  // ragged end-to-end supervision: [S] frames of each sequence (device, in the supervision's pool slot); T above is the
+  // longest -- the tensors' and the scratch's T.  Null: uniform.  (The last member, as DenParams::seq_frames.)
+  const int32_t *seq_frames = nullptr;
 };
 
 }  // namespace tc
@@ -425,9 +452,13 @@ struct tc_supervision {
   bool e2e = false;  // tc_supervision_create_e2e: `e2e_tab` holds the tables, `tab` is empty
   tc::NumTables tab;
   tc::E2eTables e2e_tab;
+  // tc_supervision_create_e2e_ragged: the sequences' lengths (S entries, T above is the longest); empty: uniform
+  std::vector<int32_t> frames;
+  int64_t total_frames = 0;        // their sum (S * T for a uniform handle)
   std::vector<size_t> blob_off;    // offsets of the tables inside a pool slot
   std::mutex mu;
   std::map<int, tc::NumDev> dev;
+  std::map<int, const int32_t *> frames_dev;  // ragged: the lengths in the device's pool slot, behind the tables
 };
 
 namespace tc {
@@ -507,10 +538,16 @@ void side_streams_forget(hipStream_t stream);              // ... before a calle
 // CUs a denominator launch of S sequences occupies (two per sequence in the two-CU form, all for the streamed path)
 int den_cus_used(const DenParams &p, int num_cus);
 bool den_zeroes_xent(const DenParams &p, int num_cus);  // whether the kernel launch_den_mode will take honours xent_zero
+// (total_frames: a ragged minibatch's sum of lengths, the objective's weight is sup_weight times it; 0: S * T)
 int launch_finalize(const double *den_lp, const double *num_lp, const double *y2, const float *ab, const float *gs,
                     int S, int T, float sup_weight, float l2, int have_deriv, float *results, int32_t *fail_flag,
                     hipStream_t stream, const double *xent_lp = nullptr, double *xent_total = nullptr,
-                    float *loss_out = nullptr);
+                    float *loss_out = nullptr, int64_t total_frames = 0);
+// Ragged minibatches: +0 into the elements of frames >= seq_frames[b] of an output tensor whose element (b, t, c) lies at
+// b*sb + t*st + c*sc (element strides; elem_bytes 4 or 2) -- every layout and dtype of the entries; costs what the padding
+// costs.  (layout_rows_kernels.hip)
+int launch_zero_padding(void *out, int elem_bytes, int64_t sb, int64_t st, int64_t sc, int B, int T, int cols,
+                        const int32_t *seq_frames, hipStream_t stream);
 int launch_zero_on_fail(const int32_t *fail_flag, float *a, int64_t a_stride, float *b, int64_t b_stride,
                         const float *y, int64_t y_stride, float l2_scale, int64_t rows, int cols, hipStream_t stream);
 int launch_den_reduce(const double *den_lp, const float *ab, const float *gs, int S, double *logprob_out,
@@ -579,7 +616,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -112,13 +112,14 @@ __device__ __forceinline__ void walk8(const Chunk8 (&res)[RES > 0 ? RES : 1], Ch
 #define TC_GEN_RES 2
 #endif
 
-template <int PV, bool ACCUM, bool WANT_DERIV>
+// RAGGED (DenParams::seq_frames): the sequence runs its own T_s frames; the frame sums' row keeps the stride of p.T
+template <int PV, bool ACCUM, bool WANT_DERIV, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void den_general_owner_kernel(const DenParams p) {
   constexpr int JV = kJvSmall, RES = TC_GEN_RES;
   constexpr uint32_t kPB = 0u, kA0 = PV * 16u * kThreads;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), s = blockIdx.x;
-  const int S = p.S, T = p.T, Hs = p.L.Hs, Ps = p.L.Ps;
+  const int S = p.S, T = RAGGED ? ragged_frames(p.seq_frames(), s, p.T) : p.T, Hs = p.L.Hs, Ps = p.L.Ps;
   const int planes = Hs / (4 * kThreads), K = Hs / kThreads;
   const uint32_t own16 = 16u * tid, lane16 = 16u * lane;
   const uint32_t aACC = 4u * (uint32_t)p.L.off_acc, aGM = 4u * (uint32_t)p.L.off_g, aOCC = 4u * (uint32_t)p.L.off_al;
@@ -373,17 +374,22 @@ __global__ __launch_bounds__(kThreads) void den_general_owner_kernel(const DenPa
   }
 }
 
-template <int PV>
-int launch_pv(const DenParams &p, int accumulate, size_t lds, hipStream_t stream) {
+template <int PV, bool RAGGED>
+int launch_pv_r(const DenParams &p, int accumulate, size_t lds, hipStream_t stream) {
   void (*k)(const DenParams) = nullptr;
   if (!p.deriv)
-    k = den_general_owner_kernel<PV, false, false>;
+    k = den_general_owner_kernel<PV, false, false, RAGGED>;
   else
-    k = accumulate ? den_general_owner_kernel<PV, true, true> : den_general_owner_kernel<PV, false, true>;
+    k = accumulate ? den_general_owner_kernel<PV, true, true, RAGGED> : den_general_owner_kernel<PV, false, true, RAGGED>;
   TC_HIP_CHECK(allow_dynamic_lds((const void *)k, lds));
   hipLaunchKernelGGL(k, dim3(p.S), dim3(kThreads), lds, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
+}
+
+template <int PV>
+int launch_pv(const DenParams &p, int accumulate, size_t lds, hipStream_t stream) {
+  return p.seq_frames() ? launch_pv_r<PV, true>(p, accumulate, lds, stream) : launch_pv_r<PV, false>(p, accumulate, lds, stream);
 }
 
 }  // namespace

@@ -132,13 +132,14 @@ __device__ __forceinline__ void walk_rows(const ScheduleDev &sc, int wave, int l
   __builtin_amdgcn_s_setprio(0);
 }
 
-template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, bool WANT_DERIV>
+// RAGGED (DenParams::seq_frames): the sequence runs its own T_s frames; rows t*S + s of frames >= T_s are not touched
+template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, bool WANT_DERIV, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void den_fwd_bwd_kernel(const DenParams p) {
   extern __shared__ __align__(16) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int s = blockIdx.x;
-  const int H = p.H, P = p.P, S = p.S, T = p.T;
+  const int H = p.H, P = p.P, S = p.S, T = RAGGED ? ragged_frames(p.seq_frames(), s, p.T) : p.T;
   const int Hs = p.L.Hs, Ps = p.L.Ps;
   float *const PB = lds;                          // exp(y_t), at LDS offset 0
   float *const A0 = lds + PV * 4 * kThreads;      // alpha'_t (forward) / beta_{t+1} (backward): gather source
@@ -416,17 +417,17 @@ __global__ __launch_bounds__(kThreads) void den_fwd_bwd_kernel(const DenParams p
   }
 }
 
-template <int JV, int PV>
+template <int JV, int PV, bool RAGGED>
 static int launch_jp(const DenParams &p, int accumulate, size_t lds_bytes, hipStream_t stream) {
   const bool want = p.deriv != nullptr;
   const bool al = p.L.alpha_in_lds;
   void (*k)(const DenParams) = nullptr;
   if (!want)
-    k = den_fwd_bwd_kernel<JV, PV, true, false, false>;
+    k = den_fwd_bwd_kernel<JV, PV, true, false, false, RAGGED>;
   else if (accumulate)
-    k = al ? den_fwd_bwd_kernel<JV, PV, true, true, true> : den_fwd_bwd_kernel<JV, PV, false, true, true>;
+    k = al ? den_fwd_bwd_kernel<JV, PV, true, true, true, RAGGED> : den_fwd_bwd_kernel<JV, PV, false, true, true, RAGGED>;
   else
-    k = al ? den_fwd_bwd_kernel<JV, PV, true, false, true> : den_fwd_bwd_kernel<JV, PV, false, false, true>;
+    k = al ? den_fwd_bwd_kernel<JV, PV, true, false, true, RAGGED> : den_fwd_bwd_kernel<JV, PV, false, false, true, RAGGED>;
   TC_HIP_CHECK(allow_dynamic_lds((const void *)k, lds_bytes));
   hipLaunchKernelGGL(k, dim3(p.S), dim3(kThreads), lds_bytes, stream, p);
   TC_HIP_CHECK(hipGetLastError());
@@ -485,6 +486,7 @@ static bool planes_two_cus(const DenParams &p, int num_cus) {
 
 int den_cus_used(const DenParams &p, int num_cus) {
   if (p.big.in.rows) return num_cus;
+  if (p.seq_frames()) return p.S < num_cus ? p.S : num_cus;  // ragged: one workgroup per sequence whatever the batch
   if (p.L.planewise) return planes_two_cus(p, num_cus) ? 2 * p.S : (p.S < num_cus ? p.S : num_cus);
   if (pair_wanted(p, num_cus)) return std::min(num_cus, 2 * ((p.S + 1) / 2));
   if (split_wanted(p) && 2 * p.S <= num_cus) return 2 * p.S;
@@ -497,6 +499,7 @@ bool den_zeroes_xent(const DenParams &p, int num_cus) {
   if (p.big.in.rows || !p.tied_fs || !p.deriv) return false;
   if ((size_t)layout_lds_bytes(p.L, p.T) > (size_t)kLdsLimitBytes) return false;
   if (p.L.planewise) return true;  // (both forms of den_tied_planes.hip write the rows)
+  if (p.seq_frames()) return true;   // (ragged: the fused kernel, the rows of the sequences' own frames)
   if (pair_wanted(p, num_cus)) return false;
   if (split_wanted(p) && 2 * p.S <= num_cus) return mitm_wanted(p);
   return true;
@@ -507,7 +510,10 @@ int launch_den_mode(const DenParams &p, int accumulate, hipStream_t stream) {
   count_launch(kCntDen);
   if (p.deriv) count_launch(kCntDenBackward);
   if (!p.big.in.rows && p.L.asum_global) count_launch(kCntDenAsumGlobal);
-  if (p.big.in.rows) return launch_den_big(p, accumulate, stream);  // graph beyond the on-chip layout
+  // Ragged batch (seq_frames): the streamed path runs lanes over sequences and has one frame count -- refused; every
+  // on-chip class takes its one-workgroup-per-sequence form whatever the batch size (no pair, meet-in-the-middle, two-pass
+  // or two-workgroup form, and no launch switch decides anything).
+  if (p.big.in.rows) return p.seq_frames() ? TC_ERR_UNSUPPORTED : launch_den_big(p, accumulate, stream);  // graph beyond the on-chip layout
   const size_t lds = (size_t)layout_lds_bytes(p.L, p.T);
   if (lds > (size_t)kLdsLimitBytes) return TC_ERR_UNSUPPORTED;
   const int JV = p.L.JV, PV = p.L.PV;
@@ -515,6 +521,11 @@ int launch_den_mode(const DenParams &p, int accumulate, hipStream_t stream) {
     SideStreams *c = nullptr;
     const int src = side_streams(stream, &c);
     if (src != TC_OK) return src;
+    if (p.seq_frames()) {
+      DenParams pq = p;
+      pq.fwd_norm = pq.bwd_norm = pq.beta_hist = nullptr;
+      return p.L.planewise ? launch_den_tied_planes(pq, accumulate, stream) : launch_den_tied(pq, accumulate, stream);
+    }
     if (p.L.planewise) {  // den_tied_planes.hip
       if (planes_two_cus(p, c->num_cus)) return launch_den_tied_planes_mitm(p, accumulate, stream);
       return launch_den_tied_planes(p, accumulate, stream);
@@ -533,7 +544,7 @@ int launch_den_mode(const DenParams &p, int accumulate, hipStream_t stream) {
   }
   if (p.gen_owner) return launch_den_general_owner(p, accumulate, stream);  // den_general_owner.hip
 #define TC_DISPATCH(J, V) \
-  if (JV == J && PV == V) return launch_jp<J, V>(p, accumulate, lds, stream);
+  if (JV == J && PV == V) return p.seq_frames() ? launch_jp<J, V, true>(p, accumulate, lds, stream) : launch_jp<J, V, false>(p, accumulate, lds, stream);
   TC_DISPATCH(kJvSmall, kPvSmall)
   TC_DISPATCH(kJvSmall, kPvMid)
   TC_DISPATCH(kJvSmall, kPvLarge)

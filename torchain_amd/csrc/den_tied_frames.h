@@ -151,9 +151,11 @@ struct TiedSeq {
   long long st_prev, st_acc[8];
 #endif
 
-  __device__ __forceinline__ TiedSeq(const DenParams &pp, int seq, int meet)
+  // frames: a ragged batch's length of this sequence (DenParams::seq_frames), the loop bound T; 0: pp.T.  The strides of
+  // the normalisers (fn, bn) and of the frame sums stay on pp.T.
+  __device__ __forceinline__ TiedSeq(const DenParams &pp, int seq, int meet, int frames = 0)
       : p(pp), tid(threadIdx.x), lane(threadIdx.x & 63u), wave(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)), s(seq),
-        H(pp.H), P(pp.P), S(pp.S), T(pp.T), Hs(pp.L.Hs), Ps(pp.L.Ps), planes(pp.L.Hs / (4 * kThreads)), K(pp.L.Hs / kThreads),
+        H(pp.H), P(pp.P), S(pp.S), T(frames > 0 ? frames : pp.T), Hs(pp.L.Hs), Ps(pp.L.Ps), planes(pp.L.Hs / (4 * kThreads)), K(pp.L.Hs / kThreads),
         own16(16u * threadIdx.x), lane16(16u * (threadIdx.x & 63u)), aACC(4u * (uint32_t)pp.L.off_acc),
         vrow(4u * (uint32_t)pp.L.off_acc + 256u * (uint32_t)((pp.L.Hs / kThreads) * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) +
              4u * (threadIdx.x & 63u)),

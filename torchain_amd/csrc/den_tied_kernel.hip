@@ -27,9 +27,10 @@ namespace tc {
 namespace {
 
 // (the frames themselves: den_tied_frames.h, shared with den_tied_mitm.hip)
-template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, bool WANT_DERIV, int RESF, int RESB>
+// RAGGED (DenParams::seq_frames): the sequence runs its own T_s frames (launch_den_mode passes no fwd_norm then)
+template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, bool WANT_DERIV, int RESF, int RESB, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void den_tied_kernel(const DenParams p) {
-  TiedSeq<JV, PV, ALPHA_LDS, ACCUM, RESF, RESB, false> q(p, (int)blockIdx.x, 0);
+  TiedSeq<JV, PV, ALPHA_LDS, ACCUM, RESF, RESB, false> q(p, (int)blockIdx.x, 0, RAGGED ? ragged_frames(p.seq_frames(), (int)blockIdx.x, p.T) : 0);
   const int T = q.T;
   // ---- forward: alpha'_0, frames 1..T, total probability
   q.forward_begin();
@@ -67,18 +68,18 @@ __global__ __launch_bounds__(kThreads) void den_tied_kernel(const DenParams p) {
 constexpr int res_fwd(int jv, int pv) { return jv > 3 ? (pv == 1 ? TC_RES_JV4 : 0) : jv == 3 ? (pv == 1 ? TC_RES_JV3 : 0) : pv == 1 ? TC_RESF : 2; }
 constexpr int res_bwd(int jv, int pv) { return jv > 3 ? (pv == 1 ? TC_RES_JV4 : 0) : jv == 3 ? (pv == 1 ? TC_RES_JV3 : 0) : pv == 1 ? TC_RESB : 2; }
 
-template <int JV, int PV>
+template <int JV, int PV, bool RAGGED>
 int launch_jp(const DenParams &p, int accumulate, size_t lds_bytes, hipStream_t stream) {
   constexpr int RF = res_fwd(JV, PV), RB = res_bwd(JV, PV);
   const bool want = p.deriv != nullptr;
   const bool al = p.L.alpha_in_lds;
   void (*k)(const DenParams) = nullptr;
   if (!want)
-    k = den_tied_kernel<JV, PV, true, false, false, RF, RB>;
+    k = den_tied_kernel<JV, PV, true, false, false, RF, RB, RAGGED>;
   else if (accumulate)
-    k = al ? den_tied_kernel<JV, PV, true, true, true, RF, RB> : den_tied_kernel<JV, PV, false, true, true, RF, RB>;
+    k = al ? den_tied_kernel<JV, PV, true, true, true, RF, RB, RAGGED> : den_tied_kernel<JV, PV, false, true, true, RF, RB, RAGGED>;
   else
-    k = al ? den_tied_kernel<JV, PV, true, false, true, RF, RB> : den_tied_kernel<JV, PV, false, false, true, RF, RB>;
+    k = al ? den_tied_kernel<JV, PV, true, false, true, RF, RB, RAGGED> : den_tied_kernel<JV, PV, false, false, true, RF, RB, RAGGED>;
   TC_HIP_CHECK(allow_dynamic_lds((const void *)k, lds_bytes));
   hipLaunchKernelGGL(k, dim3(p.S), dim3(kThreads), lds_bytes, stream, p);
   TC_HIP_CHECK(hipGetLastError());
@@ -93,7 +94,8 @@ int launch_den_tied(const DenParams &p, int accumulate, hipStream_t stream) {
   const size_t lds = (size_t)layout_lds_bytes(p.L, p.T);
   if (lds > (size_t)kLdsLimitBytes) return TC_ERR_UNSUPPORTED;
   const int JV = p.L.JV, PV = p.L.PV;
-#define TC_CALL(J, V) launch_jp<J, V>(p, accumulate, lds, stream)
+  if (p.seq_frames() && p.fwd_norm) return TC_ERR_INVALID_ARGUMENT;  // (a ragged batch has no two-CU form)
+#define TC_CALL(J, V) (p.seq_frames() ? launch_jp<J, V, true>(p, accumulate, lds, stream) : launch_jp<J, V, false>(p, accumulate, lds, stream))
   TC_TIED_DISPATCH(TC_CALL)
 #undef TC_CALL
   return TC_ERR_UNSUPPORTED;

@@ -107,9 +107,10 @@ struct PlaneSeq {
 #endif
 
   // role: which of a sequence's two workgroups (two-workgroup form; the split source's scratch rows are per workgroup)
-  __device__ __forceinline__ PlaneSeq(const DenParams &pp, int seq, int role = 0)
+  // (frames: a ragged batch's length of this sequence, the loop bound T; 0: pp.T -- as TiedSeq)
+  __device__ __forceinline__ PlaneSeq(const DenParams &pp, int seq, int role = 0, int frames = 0)
       : p(pp), tid(threadIdx.x), lane(threadIdx.x & 63u), wave(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)), s(seq), H(pp.H), S(pp.S),
-        T(pp.T), Hs(pp.L.Hs), Ps(pp.L.Ps), planes(pp.L.Hs / (4 * kThreads)), own16(16u * threadIdx.x), lane16(16u * (threadIdx.x & 63u)),
+        T(frames > 0 ? frames : pp.T), Hs(pp.L.Hs), Ps(pp.L.Ps), planes(pp.L.Hs / (4 * kThreads)), own16(16u * threadIdx.x), lane16(16u * (threadIdx.x & 63u)),
         aACC(4u * (uint32_t)pp.L.off_acc),
         vrow(4u * (uint32_t)pp.L.off_acc + 1024u * (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) + 4u * (threadIdx.x & 63u)),
         aGM(4u * (uint32_t)pp.L.off_g), aRed(4u * (uint32_t)pp.L.off_red), aAsum(4u * (uint32_t)pp.L.off_asum), asums(pp, seq), row_bytes(4u * (uint32_t)pp.P),
@@ -706,9 +707,9 @@ struct PlaneSeq {
   }
 };
 
-template <bool ACCUM, bool WANT_DERIV, int MAXP, bool SPLIT = false>
+template <bool ACCUM, bool WANT_DERIV, int MAXP, bool SPLIT = false, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void den_tied_planes_kernel(const DenParams p) {
-  PlaneSeq<ACCUM, MAXP, TC_PW_BUFFERS_FUSED, SPLIT, SPLIT> q(p, (int)blockIdx.x);
+  PlaneSeq<ACCUM, MAXP, TC_PW_BUFFERS_FUSED, SPLIT, SPLIT> q(p, (int)blockIdx.x, 0, RAGGED ? ragged_frames(p.seq_frames(), (int)blockIdx.x, p.T) : 0);
   const int T = q.T;
   // ---- forward: alpha'_0, frames 1..T, total probability
   q.forward_begin();
@@ -821,8 +822,25 @@ int launch_den_tied_planes(const DenParams &p, int accumulate, hipStream_t strea
   const size_t lds = (size_t)layout_lds_bytes(p.L, p.T);
   if (!p.L.planewise || lds > (size_t)kLdsLimitBytes || p.L.PV != kPvSmall || p.L.JV < 5 || p.L.JV > kJvPlanesSplit) return TC_ERR_UNSUPPORTED;
   void (*k)(const DenParams) = nullptr;
-  if (p.L.src_planes < p.L.JV) {  // split gather source (28673..40960 positions)
-    if (!p.src_scratch || !p.part_scratch) return TC_ERR_WORKSPACE;
+  if (p.L.src_planes < p.L.JV && (!p.src_scratch || !p.part_scratch)) return TC_ERR_WORKSPACE;
+  if (p.seq_frames()) {  // ragged batch: the same three size classes, each sequence on its own frame count
+    if (p.L.src_planes < p.L.JV) {
+      if (!p.deriv)
+        k = den_tied_planes_kernel<false, false, kJvPlanesSplit, true, true>;
+      else
+        k = accumulate ? den_tied_planes_kernel<true, true, kJvPlanesSplit, true, true> : den_tied_planes_kernel<false, true, kJvPlanesSplit, true, true>;
+    } else if (p.L.JV <= 6) {
+      if (!p.deriv)
+        k = den_tied_planes_kernel<false, false, 6, false, true>;
+      else
+        k = accumulate ? den_tied_planes_kernel<true, true, 6, false, true> : den_tied_planes_kernel<false, true, 6, false, true>;
+    } else {
+      if (!p.deriv)
+        k = den_tied_planes_kernel<false, false, kJvPlanes, false, true>;
+      else
+        k = accumulate ? den_tied_planes_kernel<true, true, kJvPlanes, false, true> : den_tied_planes_kernel<false, true, kJvPlanes, false, true>;
+    }
+  } else if (p.L.src_planes < p.L.JV) {  // split gather source (28673..40960 positions)
     if (!p.deriv)
       k = den_tied_planes_kernel<false, false, kJvPlanesSplit, true>;
     else

@@ -7,6 +7,8 @@
 // with f the element function of every last pass (half_io.h: last_elem), the one the (B, C, T) copy back calls -- plain
 // scale * v; with row weights (scale * w[row]) * v; with the penalty w[row] * penalize(scale * v, y) -- so that a channel-last
 // step returns the bits of the step on the contiguous copy.
+#include <algorithm>
+
 #include "chain_internal.h"
 #include "half_io.h"
 
@@ -176,7 +178,45 @@ int launch_rows_scatter_e(const float *in, int64_t in_stride, void *out_v, int64
   return TC_OK;
 }
 
+// Ragged minibatches: +0 into the padding of an output tensor, frames seq_frames[b] .. T - 1 of sequence b.  A block takes
+// one sequence's share; consecutive threads take consecutive frames where those are the tensor's unit stride ((B, C, T)),
+// else consecutive channels.  A sequence of full length costs its blocks one scalar load.
+template <typename Bits>
+__global__ __launch_bounds__(kRowsThreads) void zero_padding_kernel(Bits *out, int64_t sb, int64_t st, int64_t sc, int B, int T,
+                                                                    int cols, const int32_t *__restrict__ seq_frames) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int first = ragged_frames(seq_frames, b, T), pad = T - first;
+    if (pad <= 0) continue;
+    const int64_t n = (int64_t)pad * cols;
+    Bits *const base = out + (int64_t)b * sb;
+    for (int64_t i = (int64_t)blockIdx.x * kRowsThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowsThreads) {
+      int64_t f, c;
+      if (st < sc) {
+        c = i / pad;
+        f = i - c * pad;
+      } else {
+        f = i / cols;
+        c = i - f * cols;
+      }
+      base[(first + f) * st + c * sc] = Bits(0);
+    }
+  }
+}
+
 }  // namespace
+
+int launch_zero_padding(void *out, int elem_bytes, int64_t sb, int64_t st, int64_t sc, int B, int T, int cols,
+                        const int32_t *seq_frames, hipStream_t stream) {
+  if (!out || !seq_frames || B <= 0 || T <= 0 || cols <= 0 || (elem_bytes != 4 && elem_bytes != 2)) return TC_ERR_INVALID_ARGUMENT;
+  const int64_t per_seq = ((int64_t)T * cols + kRowsThreads - 1) / kRowsThreads;
+  const dim3 blocks((unsigned)std::min<int64_t>(per_seq, 64), (unsigned)std::min(B, 65535)), threads(kRowsThreads);
+  if (elem_bytes == 4)
+    hipLaunchKernelGGL(zero_padding_kernel<uint32_t>, blocks, threads, 0, stream, static_cast<uint32_t *>(out), sb, st, sc, B, T, cols, seq_frames);
+  else
+    hipLaunchKernelGGL(zero_padding_kernel<uint16_t>, blocks, threads, 0, stream, static_cast<uint16_t *>(out), sb, st, sc, B, T, cols, seq_frames);
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
 
 bool channel_last_strides_ok(int B, int T, int cols, int64_t sb, int64_t st) {
   if (B <= 0 || T <= 0 || cols <= 0) return false;

@@ -119,7 +119,9 @@ __device__ __forceinline__ void e2e_xent_sum(double v, double *out, int tid) {
 
 }  // namespace
 
-template <typename El = float>
+// RAGGED (a ragged supervision, NumParams::seq_frames): the sequence walks its own T_s frames; p.T stays the T of the tensors
+// and of the scratch's strides (load_y, write_posterior, seq_view), so nothing at frames >= T_s is read or written.
+template <typename El = float, bool RAGGED = false>
 __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int MS = (p.t.e2e_tab.max_states + 3) & ~3, MP = (p.t.e2e_tab.max_pdfs + 3) & ~3;
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
   __shared__ float red_c[4];
 
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = p.T;
+  const int T = RAGGED ? p.seq_frames[q] : p.T;
   const SeqView v = seq_view(p, q);
   const int start = p.t.e2e_tab.start[q];
   const bool want_beta = p.deriv != nullptr || p.xent != nullptr || p.seq_xent != nullptr;
@@ -287,7 +289,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
 
 // Second half of a staged e2e numerator: deriv[row, pdf] += weight * posterior, xent_deriv[row, pdf] = it.  Each
 // (frame, pdf) of a sequence has one owner; the sequence's cross-entropy sum is added in a fixed order.
-template <typename El = float>
+template <typename El = float, bool RAGGED = false>
 __global__ __launch_bounds__(kE2eThreads) void num_e2e_scatter_kernel(const NumParams p) {
   const int q = blockIdx.x, tid = threadIdx.x;
   const E2eDev &e = p.t.e2e_tab;
@@ -295,7 +297,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_scatter_kernel(const NumP
   const float *stage = p.t.stage + (int64_t)p.T * ub;
   const int32_t *pdf_of = e.pdf_of + ub;
   double xo = 0.0;
-  const int64_t n = (int64_t)p.T * np;
+  const int64_t n = (int64_t)(RAGGED ? p.seq_frames[q] : p.T) * np;  // (stage is [frame][upid]: the padding lies behind)
   for (int64_t i = tid; i < n; i += kE2eThreads) {
     const int t = (int)(i / np), k = (int)(i - (int64_t)t * np);
     xo += write_posterior<El>(p, q, t, pdf_of[k], stage[i]);
@@ -315,28 +317,33 @@ int launch_num_e2e(const NumParams &p, hipStream_t stream) {
   if (e.max_states > TC_E2E_MAX_STATES || e.max_arcs > TC_E2E_MAX_ARCS || e.max_pdfs > TC_E2E_MAX_PDFS)
     return TC_ERR_UNSUPPORTED;
   const size_t lds = num_e2e_lds_bytes(e.max_states, e.max_arcs, e.max_pdfs);
-  const void *kernel = p.elem == TC_DTYPE_BF16 ? (const void *)num_e2e_kernel<__hip_bfloat16>
-                       : p.elem == TC_DTYPE_F16 ? (const void *)num_e2e_kernel<__half>
-                                                : (const void *)num_e2e_kernel<float>;
-  TC_HIP_CHECK(allow_dynamic_lds(kernel, lds));
-  if (p.elem == TC_DTYPE_BF16)
-    hipLaunchKernelGGL(num_e2e_kernel<__hip_bfloat16>, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
-  else if (p.elem == TC_DTYPE_F16)
-    hipLaunchKernelGGL(num_e2e_kernel<__half>, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
+  void (*kernel)(const NumParams) = nullptr;
+  if (p.seq_frames)
+    kernel = p.elem == TC_DTYPE_BF16 ? num_e2e_kernel<__hip_bfloat16, true>
+             : p.elem == TC_DTYPE_F16 ? num_e2e_kernel<__half, true>
+                                      : num_e2e_kernel<float, true>;
   else
-    hipLaunchKernelGGL(num_e2e_kernel<float>, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
+    kernel = p.elem == TC_DTYPE_BF16 ? num_e2e_kernel<__hip_bfloat16>
+             : p.elem == TC_DTYPE_F16 ? num_e2e_kernel<__half>
+                                      : num_e2e_kernel<float>;
+  TC_HIP_CHECK(allow_dynamic_lds((const void *)kernel, lds));
+  hipLaunchKernelGGL(kernel, dim3(p.S), dim3(kE2eThreads), lds, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }
 
 int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream) {
   if (!p.deriv && !p.xent && !p.seq_xent) return TC_OK;
-  if (p.elem == TC_DTYPE_BF16)
-    hipLaunchKernelGGL(num_e2e_scatter_kernel<__hip_bfloat16>, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
-  else if (p.elem == TC_DTYPE_F16)
-    hipLaunchKernelGGL(num_e2e_scatter_kernel<__half>, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
+  void (*kernel)(const NumParams) = nullptr;
+  if (p.seq_frames)
+    kernel = p.elem == TC_DTYPE_BF16 ? num_e2e_scatter_kernel<__hip_bfloat16, true>
+             : p.elem == TC_DTYPE_F16 ? num_e2e_scatter_kernel<__half, true>
+                                      : num_e2e_scatter_kernel<float, true>;
   else
-    hipLaunchKernelGGL(num_e2e_scatter_kernel<float>, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
+    kernel = p.elem == TC_DTYPE_BF16 ? num_e2e_scatter_kernel<__hip_bfloat16>
+             : p.elem == TC_DTYPE_F16 ? num_e2e_scatter_kernel<__half>
+                                      : num_e2e_scatter_kernel<float>;
+  hipLaunchKernelGGL(kernel, dim3(p.S), dim3(kE2eThreads), 0, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double *den_lp, con
                                                        const float *ab, const float *gs, int S, int T,
                                                        float sup_weight, float l2, int have_deriv, float *results,
                                                        int32_t *fail_flag, const double *xent_lp, double *xent_total,
-                                                       float *loss_out) {
+                                                       float *loss_out, int64_t total_frames) {
   __shared__ double sh[4][256];
   const int tid = threadIdx.x;
   double d = 0, n = 0, q = 0, a = 0, g = 0, x = 0;
@@ -240,7 +240,8 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double *den_lp, con
     const float num_logprob_weighted = (float)(N * (double)sup_weight);
     const float den_logprob = (float)D;
     float objf = num_logprob_weighted - sup_weight * den_logprob;
-    const float weight = sup_weight * (float)S * (float)T;
+    // (a ragged minibatch: its frames in all; y2 and the checks below already are per sequence over its own frames)
+    const float weight = total_frames > 0 ? sup_weight * (float)total_frames : sup_weight * (float)S * (float)T;
     bool ok = true;
     if (have_deriv) {
       // [K] BetaGeneralFrameDebug(0)
@@ -267,9 +268,9 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double *den_lp, con
 
 int launch_finalize(const double *den_lp, const double *num_lp, const double *y2, const float *ab, const float *gs,
                     int S, int T, float sup_weight, float l2, int have_deriv, float *results, int32_t *fail_flag,
-                    hipStream_t stream, const double *xent_lp, double *xent_total, float *loss_out) {
+                    hipStream_t stream, const double *xent_lp, double *xent_total, float *loss_out, int64_t total_frames) {
   hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, stream, den_lp, num_lp, y2, ab, gs, S, T, sup_weight, l2,
-                     have_deriv, results, fail_flag, xent_lp, xent_total, loss_out);
+                     have_deriv, results, fail_flag, xent_lp, xent_total, loss_out, total_frames);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }

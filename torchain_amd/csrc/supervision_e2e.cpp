@@ -29,6 +29,7 @@ int stage_e2e_locked(tc_supervision *sup, int device) {
       {tb.pdf_of.data(), tb.pdf_of.size() * 4},       {tb.in_key.data(), tb.in_key.size() * 4},
       {tb.out_key.data(), tb.out_key.size() * 4},     {tb.in_lw.data(), tb.in_lw.size() * 4},
       {tb.out_lw.data(), tb.out_lw.size() * 4},       {tb.final_lw.data(), tb.final_lw.size() * 4},
+      {sup->frames.data(), sup->frames.size() * 4},  // ragged handles: the sequences' lengths travel with the tables
   };
   const int nparts = (int)(sizeof(parts) / sizeof(parts[0]));
   size_t total = 0;
@@ -70,19 +71,19 @@ int stage_e2e_locked(tc_supervision *sup, int device) {
   e.max_pdfs = tb.max_pdfs;
   d.stage = (float *)(blob + stage_off);
   sup->dev[device] = d;
+  if (!sup->frames.empty()) sup->frames_dev[device] = P(14);
   return TC_OK;
 }
 
 }  // namespace tc
 
-extern "C" {
+namespace {
 
-int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t S, int32_t T, int32_t label_dim,
-                              const int32_t *seq_state_begin, const int32_t *start, const int32_t *arc_begin,
-                              const int32_t *ilabel, const float *arc_weight, const int32_t *nextstate,
-                              const float *final_weight) {
-  if (!out) return TC_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
+// T: frames of every sequence, or -- seq_frames given (S entries, each 1..T) -- of the longest: the T of every shape, row
+// count, workspace and scratch rule.  A handle made with seq_frames is ragged whatever the lengths are.
+int create_e2e(tc_supervision **out, float weight, int32_t S, int32_t T, const int32_t *seq_frames, int32_t label_dim,
+               const int32_t *seq_state_begin, const int32_t *start, const int32_t *arc_begin, const int32_t *ilabel,
+               const float *arc_weight, const int32_t *nextstate, const float *final_weight) {
   if (S <= 0 || T <= 0 || label_dim <= 0 || !seq_state_begin || !start || !arc_begin || !final_weight)
     return TC_ERR_INVALID_ARGUMENT;
   if ((int64_t)S * T > ((int64_t)1 << 26)) return TC_ERR_UNSUPPORTED;  // the egs readers' bound on a minibatch
@@ -144,6 +145,12 @@ int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t S, int
   sup->S = S;
   sup->T = T;
   sup->P = label_dim;
+  sup->total_frames = (int64_t)S * T;
+  if (seq_frames) {
+    sup->frames.assign(seq_frames, seq_frames + S);
+    sup->total_frames = 0;
+    for (int32_t s = 0; s < S; ++s) sup->total_frames += seq_frames[s];
+  }
   E2eTables &tb = sup->e2e_tab;
   tb.state_off.assign(seq_state_begin, seq_state_begin + S + 1);
   tb.start.assign(start, start + S);
@@ -217,6 +224,44 @@ int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t S, int
   *out = sup;
   return TC_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t S, int32_t T, int32_t label_dim,
+                              const int32_t *seq_state_begin, const int32_t *start, const int32_t *arc_begin,
+                              const int32_t *ilabel, const float *arc_weight, const int32_t *nextstate,
+                              const float *final_weight) {
+  if (!out) return TC_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  return create_e2e(out, weight, S, T, nullptr, label_dim, seq_state_begin, start, arc_begin, ilabel, arc_weight, nextstate,
+                    final_weight);
+}
+
+int tc_supervision_create_e2e_ragged(tc_supervision **out, float weight, int32_t S, const int32_t *frames_per_sequence,
+                                     int32_t label_dim, const int32_t *seq_state_begin, const int32_t *start,
+                                     const int32_t *arc_begin, const int32_t *ilabel, const float *arc_weight,
+                                     const int32_t *nextstate, const float *final_weight) {
+  if (!out) return TC_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (S <= 0 || !frames_per_sequence) return TC_ERR_INVALID_ARGUMENT;
+  int32_t tmax = 0;
+  for (int32_t s = 0; s < S; ++s) {
+    if (frames_per_sequence[s] < 1) return TC_ERR_INVALID_ARGUMENT;
+    tmax = std::max(tmax, frames_per_sequence[s]);
+  }
+  return create_e2e(out, weight, S, tmax, frames_per_sequence, label_dim, seq_state_begin, start, arc_begin, ilabel,
+                    arc_weight, nextstate, final_weight);
+}
+
+int tc_supervision_frames(const tc_supervision *s, int32_t *out_host) {
+  if (!s || !out_host) return TC_ERR_INVALID_ARGUMENT;
+  for (int32_t i = 0; i < s->S; ++i) out_host[i] = s->frames.empty() ? s->T : s->frames[i];
+  return TC_OK;
+}
+
+int32_t tc_supervision_is_ragged(const tc_supervision *s) { return s && !s->frames.empty() ? 1 : 0; }
 
 int32_t tc_supervision_is_e2e(const tc_supervision *s) { return s && s->e2e ? 1 : 0; }
 

@@ -40,11 +40,16 @@ class EgsFormatError(ValueError):
 class E2eSup:
     """An end-to-end supervision ([K] ``Supervision::e2e_fsts``, ``<End2End>`` true): ``fsts`` holds one
     ``(start, arc_begin, ilabel, arc_weight, nextstate, final)`` per sequence, what ``io.Supervision.from_e2e_fsts``
-    takes."""
+    takes.  ``frames_per_sequence`` may be a list of ``num_sequences`` lengths (a ragged minibatch built by the caller; the
+    readers merge only egs of equal length, as Kaldi does)."""
 
     def __init__(self, weight, num_sequences, frames_per_sequence, label_dim, fsts):
         self.weight, self.num_sequences = float(weight), int(num_sequences)
-        self.frames_per_sequence, self.label_dim = int(frames_per_sequence), int(label_dim)
+        if np.ndim(frames_per_sequence) > 0:
+            self.frames_per_sequence = [int(t) for t in frames_per_sequence]
+        else:
+            self.frames_per_sequence = int(frames_per_sequence)
+        self.label_dim = int(label_dim)
         self.fsts = list(fsts)
 
 

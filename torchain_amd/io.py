@@ -163,10 +163,21 @@ class Supervision:
     def from_e2e_fsts(cls, weight, frames_per_sequence, label_dim, fsts):
         """End-to-end supervision ([K] ``Supervision::e2e_fsts``): one acceptor per sequence, not unfolded in time.
         ``fsts`` is a list of per-sequence ``(start, arc_begin, ilabel, arc_weight, nextstate, final)`` in CSR form
-        (``ilabel`` = pdf_id + 1, tropical costs, ``final`` = inf for a state that is not final)."""
+        (``ilabel`` = pdf_id + 1, tropical costs, ``final`` = inf for a state that is not final).
+
+        ``frames_per_sequence``: an int, or one length per sequence (a "ragged" minibatch of whole utterances).  Then
+        ``n_frame`` and ``shape`` use the longest length ``Tmax``: every tensor keeps its ``(B, C, Tmax)`` / ``(Tmax * B, C)``
+        shape, frames ``t >= frames[s]`` of sequence ``s`` are padding that influences nothing, and every gradient is
+        exactly zero there.  The lengths live in the handle: ``chain_loss`` and the other calls take no new argument."""
         fsts = list(fsts)
         if not fsts:
             raise ValueError("from_e2e_fsts: no FSTs")
+        ragged = not np.isscalar(frames_per_sequence) and np.ndim(frames_per_sequence) > 0
+        if ragged:
+            lengths = np.asarray(frames_per_sequence)
+            if lengths.shape != (len(fsts),) or lengths.dtype.kind not in "iu":
+                raise ValueError("from_e2e_fsts: frames_per_sequence must be an int or one int per sequence")
+            lengths = _i32(lengths)
         seq_begin, starts, ab, il, aw, nx, fin = [0], [], [np.zeros(1, np.int32)], [], [], [], []
         arcs = 0
         for start, arc_begin, ilabel, arc_weight, nextstate, final in fsts:
@@ -189,6 +200,11 @@ class Supervision:
         ab, il, nx = _i32(np.concatenate(ab)), _i32(np.concatenate(il)), _i32(np.concatenate(nx))
         aw, fin = _f32(np.concatenate(aw)), _f32(np.concatenate(fin))
         handle = C.c_void_p()
+        if ragged:
+            check(lib.tc_supervision_create_e2e_ragged(C.byref(handle), float(weight), len(fsts), _p(lengths), int(label_dim),
+                                                       _p(sb), _p(st), _p(ab), _p(il), _p(aw), _p(nx), _p(fin)),
+                  "tc_supervision_create_e2e_ragged")
+            return cls(handle)
         check(lib.tc_supervision_create_e2e(C.byref(handle), float(weight), len(fsts), int(frames_per_sequence),
                                             int(label_dim), _p(sb), _p(st), _p(ab), _p(il), _p(aw), _p(nx), _p(fin)),
               "tc_supervision_create_e2e")
@@ -198,6 +214,18 @@ class Supervision:
     def is_e2e(self):
         """True for an end-to-end supervision (``from_e2e_fsts``)."""
         return bool(lib.tc_supervision_is_e2e(self.ptr))
+
+    @property
+    def is_ragged(self):
+        """True for an end-to-end supervision made with one length per sequence."""
+        return bool(lib.tc_supervision_is_ragged(self.ptr))
+
+    @property
+    def frames(self):
+        """The sequences' lengths (numpy int32, ``n_batch`` entries; all ``n_frame`` unless ``is_ragged``)."""
+        out = np.zeros(self.n_batch, dtype=np.int32)
+        check(lib.tc_supervision_frames(self.ptr, _p(out)), "tc_supervision_frames")
+        return out
 
     @classmethod
     def from_synth(cls, sup):
