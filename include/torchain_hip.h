@@ -130,8 +130,11 @@ int32_t tc_supervision_is_e2e(const tc_supervision *supervision);
  *   - the objective's weight is weight * sum of the lengths, its failure value -10 times that, the l2 term sums over the
  *     sequences' own frames; a sequence with no path of exactly its own number of arcs fails the minibatch softly.
  * The lengths travel to the device with the tables (no allocation, no synchronisation once the pool is warm; the step
- * stays capturable).  The denominator takes the one-workgroup-per-sequence kernel of the graph's class whatever the batch
- * size -- the two-workgroup forms of small batches and the two-sequence kernel are not taken -- and a graph on the streamed
+ * stays capturable).  On a tied graph a batch of 8 sequences up to half the device's CUs runs on two workgroups per
+ * sequence that meet at half the sequence's own length when a derivative is asked for (the workspace is the same;
+ * "no_mitm" or "no_phase_split" set: not; tc_debug_counter("ragged_two_cu_launches")); every other batch takes the
+ * one-workgroup-per-sequence kernel of the graph's class -- the two-pass form and the two-sequence kernel are never
+ * taken, and below 8 sequences no launch switch decides anything -- and a graph on the streamed
  * path (tc_den_graph_stats) is refused: TC_ERR_UNSUPPORTED from every entry, before anything is launched.  A handle made
  * here is ragged also when all its lengths are equal; tc_supervision_create_e2e's handles are untouched.
  * tc_supervision_frames: the num_sequences lengths (all equal to tc_supervision_num_frame for any other handle) into host
@@ -520,8 +523,11 @@ int tc_den_forward_backward(tc_den_graph *graph, int32_t num_sequences, const fl
  * writes rows t * num_sequences + s of its own frames only; with accumulate == 0 the derivative's padding rows are +0,
  * with accumulate != 0 they are not touched.  Entries outside 1 .. max_frames are taken as the nearer bound.  logprob_dev:
  * the sum of the sequences' log-probs over their own frames.  The workspace is tc_chain_workspace_bytes(graph,
- * num_sequences, max_frames).  The kernel is the graph class's one-workgroup-per-sequence form whatever the batch size and
- * the launch switches; TC_ERR_UNSUPPORTED for a graph on the streamed path (nothing is launched or written). */
+ * num_sequences, max_frames).  The kernel is the graph class's one-workgroup-per-sequence form, whatever the launch
+ * switches, for fewer than 8 sequences, for more than half the device's CUs, without a derivative and on general graphs;
+ * a tied graph's batch in between takes two workgroups per sequence, each sequence meeting at half its own length, unless
+ * "no_mitm" or "no_phase_split" is set (the lengths are read on the device only: a sequence of one frame is run by one
+ * of its two workgroups alone).  TC_ERR_UNSUPPORTED for a graph on the streamed path (nothing is launched or written). */
 int tc_den_forward_backward_ragged(tc_den_graph *graph, int32_t num_sequences, const float *nnet_output,
                                    int64_t num_rows, int32_t num_cols, int64_t row_stride,
                                    float leaky_hmm_coefficient, float deriv_weight, float l2_scale, int accumulate,
@@ -670,7 +676,10 @@ int tc_debug_set(const char *key, int value);
  * "num_windowed_launches" = regular numerator launches that took the level-windowed kernel (counted in "num_launches" too);
  * "channel_last_steps" = tc_chain_step_strided calls taken in TC_LAYOUT_CHANNEL_LAST (their row gathers and scatters, and
  * tc_rows_gather / tc_rows_scatter, count as "layout_launches"); "ragged_steps" = objective calls made on a ragged
- * supervision (tc_supervision_create_e2e_ragged; their padding kernels are not counted as "layout_launches").
+ * supervision (tc_supervision_create_e2e_ragged; their padding kernels are not counted as "layout_launches");
+ * "ragged_two_cu_launches" = denominator launches of a ragged batch that took two workgroups per sequence, each sequence
+ * meeting at half its own length (tied graphs, 8 sequences up to half the device's CUs, a derivative asked for, neither
+ * "no_mitm" nor "no_phase_split" set; counted in "den_launches" too).
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

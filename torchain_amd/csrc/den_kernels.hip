@@ -484,9 +484,24 @@ static bool planes_two_cus(const DenParams &p, int num_cus) {
   return p.L.planewise && planes_mitm_fits(p) && 2 * p.S <= num_cus && !debug_flag(kDbgNoPhaseSplit) && !debug_flag(kDbgNoMitm);
 }
 
+// Ragged batch: two workgroups per sequence, each sequence meeting at half its own length (the RAGGED instantiations of
+// den_tied_mitm.hip and of den_tied_planes.hip's two-workgroup form), while both roles of every sequence are resident (they
+// spin on each other).  The uniform thresholds 32 / 48 / 64 of mitm_wanted separate meet-in-the-middle from the two-pass
+// form, which a ragged batch does not have: here the other choice is the fused kernel on S of the chip's CUs.
+// Why not below 8: batches of 3 to 5 sequences are held, by tests/test_gpu_ragged.py, to the bits of the single-sequence
+// fused calls and to independence from the launch switches -- that contract stays; from 8 on the two switches below decide.
+constexpr int kRaggedTwoCuFrom = 8;
+static bool ragged_two_cus(const DenParams &p, int num_cus) {
+  if (!p.seq_frames() || !p.tied_fs || p.big.in.rows || !p.deriv) return false;  // (the evaluation step stays one-workgroup)
+  if (p.S < kRaggedTwoCuFrom || 2 * p.S > num_cus) return false;
+  if (debug_flag(kDbgNoMitm) || debug_flag(kDbgNoPhaseSplit)) return false;
+  if (!p.beta_hist || !p.fwd_norm || !p.bwd_norm || !p.mitm_sync) return false;
+  return p.L.planewise ? planes_mitm_fits(p) : mitm_fits(p.L, p.T);  // (on the longest sequence's T)
+}
+
 int den_cus_used(const DenParams &p, int num_cus) {
   if (p.big.in.rows) return num_cus;
-  if (p.seq_frames()) return p.S < num_cus ? p.S : num_cus;  // ragged: one workgroup per sequence whatever the batch
+  if (p.seq_frames()) return ragged_two_cus(p, num_cus) ? 2 * p.S : (p.S < num_cus ? p.S : num_cus);
   if (p.L.planewise) return planes_two_cus(p, num_cus) ? 2 * p.S : (p.S < num_cus ? p.S : num_cus);
   if (pair_wanted(p, num_cus)) return std::min(num_cus, 2 * ((p.S + 1) / 2));
   if (split_wanted(p) && 2 * p.S <= num_cus) return 2 * p.S;
@@ -499,7 +514,7 @@ bool den_zeroes_xent(const DenParams &p, int num_cus) {
   if (p.big.in.rows || !p.tied_fs || !p.deriv) return false;
   if ((size_t)layout_lds_bytes(p.L, p.T) > (size_t)kLdsLimitBytes) return false;
   if (p.L.planewise) return true;  // (both forms of den_tied_planes.hip write the rows)
-  if (p.seq_frames()) return true;   // (ragged: the fused kernel, the rows of the sequences' own frames)
+  if (p.seq_frames()) return true;   // (ragged: the fused kernel or -- ragged_two_cus -- meet-in-the-middle, the rows of the sequences' own frames)
   if (pair_wanted(p, num_cus)) return false;
   if (split_wanted(p) && 2 * p.S <= num_cus) return mitm_wanted(p);
   return true;
@@ -510,9 +525,10 @@ int launch_den_mode(const DenParams &p, int accumulate, hipStream_t stream) {
   count_launch(kCntDen);
   if (p.deriv) count_launch(kCntDenBackward);
   if (!p.big.in.rows && p.L.asum_global) count_launch(kCntDenAsumGlobal);
-  // Ragged batch (seq_frames): the streamed path runs lanes over sequences and has one frame count -- refused; every
-  // on-chip class takes its one-workgroup-per-sequence form whatever the batch size (no pair, meet-in-the-middle, two-pass
-  // or two-workgroup form, and no launch switch decides anything).
+  // Ragged batch (seq_frames): the streamed path runs lanes over sequences and has one frame count -- refused; a tied
+  // graph's batch of kRaggedTwoCuFrom sequences up to half the chip takes two workgroups per sequence (ragged_two_cus);
+  // everything else the one-workgroup-per-sequence form of its class (no pair or two-pass form; below kRaggedTwoCuFrom
+  // no launch switch decides anything).
   if (p.big.in.rows) return p.seq_frames() ? TC_ERR_UNSUPPORTED : launch_den_big(p, accumulate, stream);  // graph beyond the on-chip layout
   const size_t lds = (size_t)layout_lds_bytes(p.L, p.T);
   if (lds > (size_t)kLdsLimitBytes) return TC_ERR_UNSUPPORTED;
@@ -522,6 +538,10 @@ int launch_den_mode(const DenParams &p, int accumulate, hipStream_t stream) {
     const int src = side_streams(stream, &c);
     if (src != TC_OK) return src;
     if (p.seq_frames()) {
+      if (ragged_two_cus(p, c->num_cus)) {
+        count_launch(kCntRaggedTwoCu);
+        return p.L.planewise ? launch_den_tied_planes_mitm(p, accumulate, stream) : launch_den_tied_mitm(p, p.mitm_sync, accumulate, stream);
+      }
       DenParams pq = p;
       pq.fwd_norm = pq.bwd_norm = pq.beta_hist = nullptr;
       return p.L.planewise ? launch_den_tied_planes(pq, accumulate, stream) : launch_den_tied(pq, accumulate, stream);

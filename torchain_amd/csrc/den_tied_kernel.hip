@@ -27,7 +27,8 @@ namespace tc {
 namespace {
 
 // (the frames themselves: den_tied_frames.h, shared with den_tied_mitm.hip)
-// RAGGED (DenParams::seq_frames): the sequence runs its own T_s frames (launch_den_mode passes no fwd_norm then)
+// RAGGED (DenParams::seq_frames): the sequence runs its own T_s frames (launch_den_mode passes no fwd_norm then; batches
+// of 8 sequences up to half the chip take den_tied_mitm.hip's RAGGED instantiation instead)
 template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, bool WANT_DERIV, int RESF, int RESB, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void den_tied_kernel(const DenParams p) {
   TiedSeq<JV, PV, ALPHA_LDS, ACCUM, RESF, RESB, false> q(p, (int)blockIdx.x, 0, RAGGED ? ragged_frames(p.seq_frames(), (int)blockIdx.x, p.T) : 0);
@@ -94,7 +95,7 @@ int launch_den_tied(const DenParams &p, int accumulate, hipStream_t stream) {
   const size_t lds = (size_t)layout_lds_bytes(p.L, p.T);
   if (lds > (size_t)kLdsLimitBytes) return TC_ERR_UNSUPPORTED;
   const int JV = p.L.JV, PV = p.L.PV;
-  if (p.seq_frames() && p.fwd_norm) return TC_ERR_INVALID_ARGUMENT;  // (a ragged batch has no two-CU form)
+  if (p.seq_frames() && p.fwd_norm) return TC_ERR_INVALID_ARGUMENT;  // (a ragged batch has no two-pass form: the normalisers' stride is the longest sequence's; its two-workgroup form is den_tied_mitm.hip's)
 #define TC_CALL(J, V) (p.seq_frames() ? launch_jp<J, V, true>(p, accumulate, lds, stream) : launch_jp<J, V, false>(p, accumulate, lds, stream))
   TC_TIED_DISPATCH(TC_CALL)
 #undef TC_CALL

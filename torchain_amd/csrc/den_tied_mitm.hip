@@ -19,6 +19,14 @@
 // The frames are den_tied_frames.h's, the ones the fused kernel runs (same LDS layout, same resident chunks): role F =
 // forward_frame<GAMMA>, role B = backward_frame<PURE>; this file holds the pairing, the hand-over and the two drivers.  [K] = kaldi chain-denominator.cc, reached by the reference through
 // src/my_lib_chain.cpp:129-131.
+//
+// RAGGED (DenParams::seq_frames, batches of kRaggedTwoCuFrom sequences up to half the chip): both roles of sequence s read
+// its frame count T_s and meet at M_s = T_s / 2; the rows, the history and the normalisers keep the strides of the longest
+// sequence, and no row of a frame >= T_s (no history row > T_s) is touched.  A sequence of ONE frame cannot meet: with
+// M = 0 role F has no un-dashed alpha_0 in registers and, worse, role B has no frame with gamma, and that frame (frame 0)
+// is where the two checks of [K] BetaGeneralFrameDebug(0) come from -- sum alpha'_0 beta'_0 with Kaldi's scale and the sum
+// of gamma_0, of which role F would hold one half and role B the other.  Role F runs such a sequence alone, as the fused
+// kernel would (one forward frame, the total, one backward frame with gamma), and role B returns at once: neither waits.
 #include "den_handover.h"
 #include "den_tied_frames.h"
 
@@ -29,12 +37,23 @@ namespace {
 // =========================================================================================================
 // ROLE F: the forward frame (den_tied_frames.h); frames M+1..T also form gamma_{t-1}.
 // =========================================================================================================
-template <int JV, int PV, bool ACCUM, int RESF>
-__device__ __forceinline__ void mitm_forward(const DenParams &p, const MitmParams &mq, int s) {
-  TiedSeq<JV, PV, false, ACCUM, RESF, 0, true> q(p, s, mq.M);
+// (frames: RAGGED, the sequence's own frame count; the meeting frame is then frames / 2)
+template <int JV, int PV, bool ACCUM, int RESF, bool RAGGED = false>
+__device__ __forceinline__ void mitm_forward(const DenParams &p, const MitmParams &mq, int s, int frames = 0) {
+  TiedSeq<JV, PV, false, ACCUM, RESF, 0, true> q(p, s, RAGGED ? frames >> 1 : mq.M, frames);
   const int T = q.T, M = q.M;
   const uint32_t own16 = q.own16;
   q.forward_begin();
+  if constexpr (RAGGED) {
+    if (T == 1) {  // one frame: this role alone, the fused kernel's sequence of phases (tight layout: alpha' from the history)
+      q.template forward_frame<false>(1);
+      q.forward_store_row(1);
+      const float tot = q.forward_total(0.0);
+      q.template backward_begin<false>(__builtin_amdgcn_rcpf(tot));
+      q.template backward_frame<false>(0, 1);
+      return;
+    }
+  }
   // ---- first phase: frames 1..M (rows 0..M-1 of the alpha' history leave under the walks, row M here)
   for (int t = 1; t <= M; ++t) q.template forward_frame<false>(t);
   q.forward_store_row(M);
@@ -62,9 +81,9 @@ __device__ __forceinline__ void mitm_forward(const DenParams &p, const MitmParam
 // =========================================================================================================
 // ROLE B: frames T-1..M with normalisers of its own and no gamma; then den_tied_kernel's backward frame.
 // =========================================================================================================
-template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, int RESB>
-__device__ __forceinline__ void mitm_backward(const DenParams &p, const MitmParams &mq, int s) {
-  TiedSeq<JV, PV, ALPHA_LDS, ACCUM, 0, RESB, true> q(p, s, mq.M);
+template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, int RESB, bool RAGGED = false>
+__device__ __forceinline__ void mitm_backward(const DenParams &p, const MitmParams &mq, int s, int frames = 0) {
+  TiedSeq<JV, PV, ALPHA_LDS, ACCUM, 0, RESB, true> q(p, s, RAGGED ? frames >> 1 : mq.M, frames);
   const int T = q.T, M = q.M;
   const uint32_t own16 = q.own16;
   // B'_T = 1; B_T = B'_T + leaky sum_h pi(h) B'_T(h)
@@ -107,15 +126,23 @@ __device__ __forceinline__ void mitm_backward(const DenParams &p, const MitmPara
   if (!partner_ok && q.tid == 0) p.seq_ab[s] = __builtin_nanf("");
 }
 
-template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, int RESF, int RESB>
+template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, int RESF, int RESB, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void den_tied_mitm_kernel(const DenParams p, const MitmParams q) {
   const uint32_t ticket = take_ticket(q);
   const int s = (int)(ticket >> 1);
   if (s >= p.S) return;
-  if ((ticket & 1u) == 0u)
-    mitm_forward<JV, PV, ACCUM, RESF>(p, q, s);
-  else
-    mitm_backward<JV, PV, ALPHA_LDS, ACCUM, RESB>(p, q, s);
+  if constexpr (RAGGED) {
+    const int frames = ragged_frames(p.seq_frames(), s, p.T);  // (both roles: one load each, a scalar)
+    if ((ticket & 1u) == 0u)
+      mitm_forward<JV, PV, ACCUM, RESF, true>(p, q, s, frames);
+    else if (frames > 1)  // (a sequence of one frame is role F's alone; nobody waits for this workgroup)
+      mitm_backward<JV, PV, ALPHA_LDS, ACCUM, RESB, true>(p, q, s, frames);
+  } else {
+    if ((ticket & 1u) == 0u)
+      mitm_forward<JV, PV, ACCUM, RESF>(p, q, s);
+    else
+      mitm_backward<JV, PV, ALPHA_LDS, ACCUM, RESB>(p, q, s);
+  }
 }
 
 // resident chunks per role (the gamma frames of role F carry B_t and y_{t-1} next to the forward pass)
@@ -147,15 +174,15 @@ constexpr int mitm_res_bwd(int jv, int pv) {
   return jv == kJvSmall ? (pv == kPvSmall ? TC_MITM_RB : TC_MITM_RBP) : pv != kPvSmall ? 0 : jv == kJvMid ? 2 : TC_MITM_RB4;
 }
 
-template <int JV, int PV>
+template <int JV, int PV, bool RAGGED>
 int launch_mitm_jp(const DenParams &p, const MitmParams &q, int accumulate, size_t lds_bytes, hipStream_t stream) {
   constexpr int RF = mitm_res_fwd(JV, PV), RB = mitm_res_bwd(JV, PV);
   const bool al = p.L.alpha_in_lds;
   void (*k)(const DenParams, const MitmParams) = nullptr;
   if (accumulate)
-    k = al ? den_tied_mitm_kernel<JV, PV, true, true, RF, RB> : den_tied_mitm_kernel<JV, PV, false, true, RF, RB>;
+    k = al ? den_tied_mitm_kernel<JV, PV, true, true, RF, RB, RAGGED> : den_tied_mitm_kernel<JV, PV, false, true, RF, RB, RAGGED>;
   else
-    k = al ? den_tied_mitm_kernel<JV, PV, true, false, RF, RB> : den_tied_mitm_kernel<JV, PV, false, false, RF, RB>;
+    k = al ? den_tied_mitm_kernel<JV, PV, true, false, RF, RB, RAGGED> : den_tied_mitm_kernel<JV, PV, false, false, RF, RB, RAGGED>;
   TC_HIP_CHECK(allow_dynamic_lds((const void *)k, lds_bytes));
   hipLaunchKernelGGL(k, dim3(2 * p.S), dim3(kThreads), lds_bytes, stream, p, q);
   TC_HIP_CHECK(hipGetLastError());
@@ -166,7 +193,8 @@ int launch_mitm_jp(const DenParams &p, const MitmParams &q, int accumulate, size
 
 size_t mitm_sync_bytes(int S) { return (size_t)(16 + 8 * S + 255) & ~(size_t)255; }
 
-// Fits wherever the fused kernel fits with 16 more bytes of LDS, from two frames on.
+// Fits wherever the fused kernel fits with 16 more bytes of LDS, from two frames on (T: a ragged batch's longest; its
+// sequences of one frame are run by role F alone).
 bool mitm_fits(const DenLayout &L, int T) { return T >= 2 && (size_t)layout_lds_bytes(L, T) + 16u <= (size_t)kLdsLimitBytes; }
 
 int launch_den_tied_mitm(const DenParams &p, uint32_t *sync, int accumulate, hipStream_t stream) {
@@ -174,11 +202,11 @@ int launch_den_tied_mitm(const DenParams &p, uint32_t *sync, int accumulate, hip
   const size_t lds = (size_t)layout_lds_bytes(p.L, p.T) + 16u;
   MitmParams q;
   q.sync = sync;
-  q.M = p.T / 2;
+  q.M = p.T / 2;  // (a ragged batch: not read, every sequence meets at half its own length)
   q.aScr = (uint32_t)layout_lds_bytes(p.L, p.T);
   TC_HIP_CHECK(hipMemsetAsync(sync, 0, mitm_sync_bytes(p.S), stream));
   const int JV = p.L.JV, PV = p.L.PV;
-#define TC_CALL(J, V) launch_mitm_jp<J, V>(p, q, accumulate, lds, stream)
+#define TC_CALL(J, V) (p.seq_frames() ? launch_mitm_jp<J, V, true>(p, q, accumulate, lds, stream) : launch_mitm_jp<J, V, false>(p, q, accumulate, lds, stream))
   TC_TIED_DISPATCH(TC_CALL)
 #undef TC_CALL
   return TC_ERR_UNSUPPORTED;

@@ -728,11 +728,22 @@ __global__ __launch_bounds__(kThreads) void den_tied_planes_kernel(const DenPara
 // Two workgroups per sequence that meet in the middle (batches of at most half the CUs): den_tied_mitm.hip's scheme
 // =========================================================================================================
 // ROLE F: alpha forward over frames 1..M exactly as the fused kernel, the hand-over, then frames M+1..T with gamma_{t-1}
-template <bool ACCUM, int MAXP, bool SPLIT>
-__device__ __forceinline__ void planes_mitm_forward(const DenParams &p, const MitmParams &mq, int s) {
-  PlaneSeq<ACCUM, MAXP, SPLIT ? TC_PW_BUFFERS_FUSED : TC_PW_BUFFERS_PAIR, SPLIT> q(p, s, 0);
-  const int T = q.T, M = mq.M;
+// RAGGED (frames: the sequence's own frame count T_s): the meeting frame is T_s / 2; a sequence of ONE frame is this role's alone
+// (den_tied_mitm.hip says why it cannot meet) -- the fused kernel's sequence of phases -- and role B returns at once
+template <bool ACCUM, int MAXP, bool SPLIT, bool RAGGED = false>
+__device__ __forceinline__ void planes_mitm_forward(const DenParams &p, const MitmParams &mq, int s, int frames = 0) {
+  PlaneSeq<ACCUM, MAXP, SPLIT ? TC_PW_BUFFERS_FUSED : TC_PW_BUFFERS_PAIR, SPLIT> q(p, s, 0, frames);
+  const int T = q.T, M = RAGGED ? frames >> 1 : mq.M;
   q.forward_begin();
+  if constexpr (RAGGED) {
+    if (T == 1) {
+      q.template forward_frame<false>(1);
+      const float tot = q.forward_total();
+      q.template backward_begin<false>(__builtin_amdgcn_rcpf(tot));
+      q.template backward_frame<false>(0);
+      return;
+    }
+  }
   for (int t = 1; t <= M; ++t) q.template forward_frame<false>(t);
   publish(mq.sync + 4 + 2 * s, q.tid);
   const bool partner_ok = await(mq.sync + 4 + 2 * s + 1, q.tid, mq.aScr + 4u);
@@ -750,10 +761,10 @@ __device__ __forceinline__ void planes_mitm_forward(const DenParams &p, const Mi
 }
 
 // ROLE B: frames T-1..M with normalisers of its own and no gamma, the hand-over, then the fused kernel's backward frame
-template <bool ACCUM, int MAXP, bool SPLIT>
-__device__ __forceinline__ void planes_mitm_backward(const DenParams &p, const MitmParams &mq, int s) {
-  PlaneSeq<ACCUM, MAXP, SPLIT ? TC_PW_BUFFERS_FUSED : TC_PW_BUFFERS_PAIR, SPLIT> q(p, s, 1);
-  const int T = q.T, M = mq.M;
+template <bool ACCUM, int MAXP, bool SPLIT, bool RAGGED = false>
+__device__ __forceinline__ void planes_mitm_backward(const DenParams &p, const MitmParams &mq, int s, int frames = 0) {
+  PlaneSeq<ACCUM, MAXP, SPLIT ? TC_PW_BUFFERS_FUSED : TC_PW_BUFFERS_PAIR, SPLIT> q(p, s, 1, frames);
+  const int T = q.T, M = RAGGED ? frames >> 1 : mq.M;
   q.template backward_begin<true>(1.0f);  // B'_T = 1
   for (int t = T - 1; t >= M; --t) q.template backward_frame<true>(t);
   publish(mq.sync + 4 + 2 * s + 1, q.tid);
@@ -777,15 +788,23 @@ __device__ __forceinline__ void planes_mitm_backward(const DenParams &p, const M
   if (!partner_ok && q.tid == 0) p.seq_ab[s] = __builtin_nanf("");
 }
 
-template <bool ACCUM, int MAXP, bool SPLIT = false>
+template <bool ACCUM, int MAXP, bool SPLIT = false, bool RAGGED = false>
 __global__ __launch_bounds__(kThreads) void den_tied_planes_mitm_kernel(const DenParams p, const MitmParams q) {
   const uint32_t ticket = take_ticket(q);
   const int s = (int)(ticket >> 1);
   if (s >= p.S) return;
-  if ((ticket & 1u) == 0u)
-    planes_mitm_forward<ACCUM, MAXP, SPLIT>(p, q, s);
-  else
-    planes_mitm_backward<ACCUM, MAXP, SPLIT>(p, q, s);
+  if constexpr (RAGGED) {
+    const int frames = ragged_frames(p.seq_frames(), s, p.T);  // (both roles: one load each, a scalar)
+    if ((ticket & 1u) == 0u)
+      planes_mitm_forward<ACCUM, MAXP, SPLIT, true>(p, q, s, frames);
+    else if (frames > 1)  // (a sequence of one frame is role F's alone; nobody waits for this workgroup)
+      planes_mitm_backward<ACCUM, MAXP, SPLIT, true>(p, q, s, frames);
+  } else {
+    if ((ticket & 1u) == 0u)
+      planes_mitm_forward<ACCUM, MAXP, SPLIT>(p, q, s);
+    else
+      planes_mitm_backward<ACCUM, MAXP, SPLIT>(p, q, s);
+  }
 }
 
 }  // namespace
@@ -806,7 +825,14 @@ int launch_den_tied_planes_mitm(const DenParams &p, int accumulate, hipStream_t 
   q.aScr = (uint32_t)layout_lds_bytes(p.L, p.T);
   TC_HIP_CHECK(hipMemsetAsync(p.mitm_sync, 0, mitm_sync_bytes(p.S), stream));
   void (*k)(const DenParams, const MitmParams) = nullptr;
-  if (p.L.src_planes < p.L.JV)
+  if (p.seq_frames()) {  // ragged batch: the same three size classes, each sequence meeting at half its own frame count (q.M is not read)
+    if (p.L.src_planes < p.L.JV)
+      k = accumulate ? den_tied_planes_mitm_kernel<true, kJvPlanesSplit, true, true> : den_tied_planes_mitm_kernel<false, kJvPlanesSplit, true, true>;
+    else if (p.L.JV <= 6)
+      k = accumulate ? den_tied_planes_mitm_kernel<true, 6, false, true> : den_tied_planes_mitm_kernel<false, 6, false, true>;
+    else
+      k = accumulate ? den_tied_planes_mitm_kernel<true, kJvPlanes, false, true> : den_tied_planes_mitm_kernel<false, kJvPlanes, false, true>;
+  } else if (p.L.src_planes < p.L.JV)
     k = accumulate ? den_tied_planes_mitm_kernel<true, kJvPlanesSplit, true> : den_tied_planes_mitm_kernel<false, kJvPlanesSplit, true>;
   else if (p.L.JV <= 6)
     k = accumulate ? den_tied_planes_mitm_kernel<true, 6> : den_tied_planes_mitm_kernel<false, 6>;
