@@ -27,10 +27,11 @@ a256 = lambda x: (x + 255) & ~255
 # the stamp area is the 4 KB "scalar" block of the workspace (api.cpp: carve): the last block for batches
 # beyond 128 sequences of on-chip graphs
 assert S > 128, "batches of at most 128 sequences carry the second history behind the stamp area"
-# api.cpp carve(): history ((T + 2) rows when the two-sequence kernel fits the graph), four double[S], two float[S], 256 B
+# api.cpp carve(): history ((T + 2) rows when the two-sequence kernel fits the graph), the frame sums' [S][asum_stride(T)],
+# four double[S], two float[S], 256 B
 Hs = int(os.environ.get("TC_HS", 8192))
 rows = T + 2 if os.environ.get("TC_PAIR_ROOM", "1") == "1" else T + 1
-off = a256(rows * S * Hs * 4) + 4 * a256(S * 8) + 2 * a256(S * 4) + 256
+off = a256(rows * S * Hs * 4) + a256(S * ((T + 2 + 3) & ~3) * 4) + 4 * a256(S * 8) + 2 * a256(S * 4) + 256
 names = ["tail", "barrier1", "walk", "barrier2", "pass1+reduce"]
 for _ in range(2):
     rc = lib.tc_den_forward_backward(
@@ -47,3 +48,6 @@ for ph, name in enumerate(("forward", "backward")):
     print("  total        ", " ".join("%6.0f" % v for v in st[ph, :, :5].sum(axis=1)))
     print("  walk: resident", " ".join("%6.0f" % v for v in st[ph, :, 5]))
     print("  walk: streamed", " ".join("%6.0f" % v for v in st[ph, :, 6]))
+    print("  by wave generation (waves 0-3, 4-7, 8-11, 12-15):")
+    for i, nm in ((5, "resident"), (6, "streamed"), (2, "walk")):
+        print("    %-10s" % nm, " ".join("%7.0f" % st[ph, 4 * g:4 * g + 4, i].mean() for g in range(4)))

@@ -286,6 +286,15 @@ struct TiedSeq {
     stamps_reset();
   }
 
+  // Where a forward frame issues the store of the history row of frame t-1: from its per-state pass (true) or from under its
+  // arc walk (false), the same values to the same addresses.  A wave's vector-memory operations retire in order, so under
+  // the walk every streamed chunk requested behind the store waits for the store's acknowledgement, and the wave first
+  // re-reads the row from the gather buffer.  Measured, two libraries taking turns on one MI355X
+  // (profiles/store_placement/README.md): the fused kernel at C3 (256 sequences) 1.357 -> 1.337 ms from the pass, every turn
+  // below the parent's; the two-workgroup form at C2 (64 sequences) 0.640 -> 0.647 ms, every turn above it (why, is
+  // not established): its roles keep the walk's placement.
+  static constexpr bool kHistFromPass = !MITM;
+
   // frame t = 1..T   ([K] AlphaGeneralFrame(t) + AlphaDash(t))
   template <bool GAMMA>
   __device__ __forceinline__ void forward_frame(int t) {
@@ -305,16 +314,17 @@ struct TiedSeq {
     }
     float n_t = 1.f;
     if (GAMMA && t < T) n_t = vload_f32(bn + t);  // for c^_{t+1}
-    // The history row of frame t-1 is stored from here, not from the end of frame t-1: a CU issues a 1 KB
-    // store instruction only every ~60 cycles, so the 32 of a frame, issued back to back by 16 waves,
-    // held the frame's tail for ~1.9k cycles (profiles/r02_phase_stamps_before_spread.txt).  Under the walk
-    // the store path is idle: the four wave generations issue theirs after resident chunk 0, 1, 2, 3.
+    // The history row of frame t-1 is not stored from the end of frame t-1: a CU issues a 1 KB store instruction only
+    // every ~60 cycles, so the 32 of a frame, issued back to back by 16 waves that leave a barrier together, held the
+    // frame's tail for ~1.9k cycles (profiles/r02_phase_stamps_before_spread.txt).  The two-workgroup roles store it from
+    // here, under the walk: the four wave generations issue theirs after resident chunk 0, 1, 2, 3.  The fused kernel
+    // stores it from the per-state pass below (kHistFromPass).
     // (GAMMA frames: rows above the meeting frame have no reader.)
     age_prio_on(wave);
     bool stored = false;  // (nothing resident: the four wave generations store after streamed pair 0, 1, 2, 3)
     const RowCommit frc{aACC + 256u * (uint32_t)(K * wave), fsec, K};
     walk<kA0, RESF>(fres, q0, fbase, lane16, fnch, fmask, frc, [&](int i) {
-      if (!GAMMA && t > 1 && !stored && (RESF > 0 ? i == store_slot : (i == kWalkEnd || i == -1 - (wave >> 2)))) {
+      if (!kHistFromPass && !GAMMA && t > 1 && !stored && (RESF > 0 ? i == store_slot : (i == kWalkEnd || i == -1 - (wave >> 2)))) {
         stored = true;
         const rsrc_t hist_prev = make_rsrc(hist + (int64_t)(t - 1) * hist_step, 4u * Hs);
 #ifndef TC_ABL_NOHIST
@@ -342,12 +352,22 @@ struct TiedSeq {
         cpi[j] = bld4(r_pi, own16, j * kPlane);  // pi: first touched behind the reduction, which hides its L2 trip
       }
     const float gs = kGammaScale * chat;
+    // kHistFromPass: the history row of frame t-1 leaves from here, out of the registers this pass reads alpha'_{t-1} into.
+    // The waves arrive here as they finish their walks, so their stores do not queue as they would behind a barrier, and the
+    // next load the wave needs (frame t+1's first look-ahead chunk) is a reduction, the tail, a barrier and the resident
+    // chunks away.  The store is unconditional -- a vector-memory operation behind a condition costs the walk's counted
+    // waits --: frame 1 has no row to store (row 0 is forward_begin's) and stores through a descriptor of no bytes, which
+    // drops it.
+    const rsrc_t hist_prev = make_rsrc(hist + (int64_t)(t - 1) * hist_step, t > 1 ? 4u * Hs : 0u);
 #pragma unroll
     for (int j = 0; j < JV; ++j) {
       v4[j] = mk4(0.f);
       if (plane_on(j)) {
         const f4 F = own_rows(vrow, j);
         const f4 al = lds4(kA0 + own16 + j * kPlane);  // alpha'_{t-1} of the owned states
+#ifndef TC_ABL_NOHIST
+        if (kHistFromPass && !GAMMA) bst4(hist_prev, own16 + j * kPlane, al);
+#endif
         v4[j] = f4{fwd_state<GAMMA>(fs[j].x, ws[j].x, F.x, al.x, bt[j].x, gs, dpart), fwd_state<GAMMA>(fs[j].y, ws[j].y, F.y, al.y, bt[j].y, gs, dpart),
                    fwd_state<GAMMA>(fs[j].z, ws[j].z, F.z, al.z, bt[j].z, gs, dpart), fwd_state<GAMMA>(fs[j].w, ws[j].w, F.w, al.w, bt[j].w, gs, dpart)};
         part += hsum(v4[j]);
@@ -565,12 +585,18 @@ struct TiedSeq {
     // a row held the backward tail for ~1k cycles: profiles/r02_phase_stamps.txt, tail of waves 0-3 vs 12-15).
     // It waits, thread-private, in the exp(y) buffer that went dead with frame t+1's per-state pass and that
     // this thread overwrites only after its walk.
+    // (This row stays under the walk in every kernel.  Without the hook's stores the C3 launch is 0.06 ms shorter
+    // (-DTC_ABL_NOWALKSTORE), but no other place measured kept any of that: the top of the frame, for all waves +0.01 ms, for
+    // the first one or two wave generations +-0.003; the end of the per-state pass +0.004 ms.  And the streamed part of the
+    // walk is not longer for the wave generations that store late, as it was in the forward walk.
+    // profiles/store_placement/README.md)
     age_prio_on(wave);
     bool dstored = false;
     const RowCommit brc{aACC + 256u * (uint32_t)(K * wave), bsec, K};
     // (PURE: the history row of B_{t+1}, still in this thread's registers, leaves the same way; row T went out in
     // backward_begin, the last pure frame's row goes out in backward_store_row)
     walk<kA0, RESB>(bres, q0, bbase, lane16, bnch, bmask, brc, [&](int i) {
+#ifndef TC_ABL_NOWALKSTORE  /* (ablation: what the stores under the backward walk cost; TC_ABL_NODERIV leaves them in) */
       if ((PURE ? t < T - 1 : kDeferDeriv && t < t_top - 1) && !dstored &&
           (RESB > 0 ? i == bstore_slot : (i == kWalkEnd || i == -1 - (wave >> 2)))) {
         dstored = true;
@@ -587,6 +613,7 @@ struct TiedSeq {
           xent_zero_row(t + 1);
         }
       }
+#endif
     } TC_WALK_PASS);
     __builtin_amdgcn_s_setprio(0);
     if (ALPHA_LDS) {
