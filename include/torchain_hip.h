@@ -138,9 +138,10 @@ int32_t tc_supervision_is_e2e(const tc_supervision *supervision);
  * path (tc_den_graph_stats) is refused: TC_ERR_UNSUPPORTED from every entry, before anything is launched.  A handle made
  * here is ragged also when all its lengths are equal; tc_supervision_create_e2e's handles are untouched.
  * tc_supervision_frames: the num_sequences lengths (all equal to tc_supervision_num_frame for any other handle) into host
- * memory.  tc_supervision_is_ragged: 1 for a handle of tc_supervision_create_e2e_ragged, else 0.
+ * memory.  tc_supervision_is_ragged: 1 for a handle of tc_supervision_create_e2e_ragged or tc_supervision_create_ragged,
+ * else 0.
  * tc_debug_counter("ragged_steps") counts the objective calls made on a ragged handle.
- * Regular (merged-FST) supervisions have one frames_per_sequence, as [K] Supervision has: no ragged form. */
+ * Regular supervisions of unequal lengths: tc_supervision_create_ragged below. */
 int tc_supervision_create_e2e_ragged(tc_supervision **out, float weight, int32_t num_sequences,
                                      const int32_t *frames_per_sequence, int32_t label_dim,
                                      const int32_t *seq_state_begin, const int32_t *start, const int32_t *arc_begin,
@@ -148,6 +149,27 @@ int tc_supervision_create_e2e_ragged(tc_supervision **out, float weight, int32_t
                                      const float *final_weight);
 int tc_supervision_frames(const tc_supervision *supervision, int32_t *frames_host);
 int32_t tc_supervision_is_ragged(const tc_supervision *supervision);
+
+/* Regular (time-unfolded) supervisions of UNEQUAL sequence lengths: one epsilon-free acceptor per sequence, the acceptors
+ * concatenated the way tc_supervision_create_e2e_ragged takes its input (sequence s owns states [seq_state_begin[s],
+ * seq_state_begin[s+1]); arc_begin has seq_state_begin[S] + 1 entries starting at 0, positions in the concatenated arc
+ * arrays; arc_nextstate is local to the sequence; ilabel = pdf_id + 1; tropical costs, final_weight = +inf: not final).
+ * Each sequence is what tc_supervision_create accepts with num_sequences = 1 and frames_per_sequence[s] frames: state 0 its
+ * start, states numbered in time order, every path exactly frames_per_sequence[s] arcs long, final costs on the last level
+ * only.  Nothing is merged, split or re-weighted: a sequence's tables are those tc_supervision_create builds for it alone,
+ * and the numerator gives, for every sequence of the batch, the bits it gives on that sequence alone.
+ * The handle is a ragged one in every respect stated above for tc_supervision_create_e2e_ragged -- T = the longest length,
+ * padding, +0, the objective's weight, the denominator's forms, the refusal of graphs on the streamed path -- also when all
+ * its lengths are equal, and tc_supervision_is_e2e is 0.  tc_supervision_stats works on it: "frames" is the longest length,
+ * the sizes are the batch's maxima, and they choose between the resident and the level-windowed kernel as for
+ * tc_supervision_create.
+ * TC_ERR_INVALID_ARGUMENT: a length below 1.  TC_ERR_BAD_FST: a sequence whose paths are not all exactly its own number
+ * of arcs long, a label outside 1 .. label_dim, a next state out of range, states out of time order.  TC_ERR_UNSUPPORTED:
+ * num_sequences * the longest length above 2^26, or a log-alpha history (8 bytes per state of the batch) above 4 GiB. */
+int tc_supervision_create_ragged(tc_supervision **out, float weight, int32_t num_sequences,
+                                 const int32_t *frames_per_sequence, int32_t label_dim,
+                                 const int32_t *seq_state_begin, const int32_t *arc_begin, const int32_t *arc_ilabel,
+                                 const float *arc_weight, const int32_t *arc_nextstate, const float *final_weight);
 
 /* Merges the supervision FSTs of a minibatch's examples into the one acceptor tc_supervision_create takes: what the
  * reference reaches natively through kaldi::nnet3::MergeChainExamples -> [K] chain::AppendSupervision
@@ -676,7 +698,8 @@ int tc_debug_set(const char *key, int value);
  * "num_windowed_launches" = regular numerator launches that took the level-windowed kernel (counted in "num_launches" too);
  * "channel_last_steps" = tc_chain_step_strided calls taken in TC_LAYOUT_CHANNEL_LAST (their row gathers and scatters, and
  * tc_rows_gather / tc_rows_scatter, count as "layout_launches"); "ragged_steps" = objective calls made on a ragged
- * supervision (tc_supervision_create_e2e_ragged; their padding kernels are not counted as "layout_launches");
+ * supervision (tc_supervision_create_e2e_ragged, tc_supervision_create_ragged; their padding kernels are not counted as
+ * "layout_launches");
  * "ragged_two_cu_launches" = denominator launches of a ragged batch that took two workgroups per sequence, each sequence
  * meeting at half its own length (tied graphs, 8 sequences up to half the device's CUs, a derivative asked for, neither
  * "no_mitm" nor "no_phase_split" set; counted in "den_launches" too).

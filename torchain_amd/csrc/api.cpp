@@ -215,7 +215,10 @@ int fill_num_params(tc_supervision *sup, int device, hipStream_t stream, const f
   {
     std::lock_guard<std::mutex> lock(sup->mu);
     p->t = sup->dev[device];
-    if (!sup->frames.empty()) p->seq_frames = sup->frames_dev[device];  // (in the same pool slot, uploaded with the tables)
+    if (!sup->frames.empty()) {  // (in the same pool slot, uploaded with the tables)
+      p->seq_frames = sup->frames_dev[device];
+      if (!sup->e2e) p->seq_level_off = sup->level_off_dev[device];
+    }
   }
   p->y = y;
   p->y_stride = y_stride;

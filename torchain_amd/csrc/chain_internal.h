@@ -338,6 +338,10 @@ struct NumTables {
   // and the widest level / the most arcs leaving one level / the most unique entries of one frame over all sequences
   std::vector<int32_t> frame_uniq;    // [S][T + 1] sequence-local unique id where each frame's entries begin
   int32_t max_level_states = 0, max_level_arcs = 0, max_frame_uniq = 0;
+  // S + 1 prefix sums of T_s + 2: where sequence s's entries of level_begin start (its frame_uniq entries start at
+  // seq_level_off[s] - s).  q * (T + 2) for a uniform handle, whose kernels compute that themselves; a ragged handle
+  // (tc_supervision_create_ragged) uploads it.
+  std::vector<int32_t> seq_level_off;
 };
 
 // LDS of the two regular numerator kernels (launch_num, tc_supervision_stats).  Resident (num_kernels.hip): log-alpha and
@@ -439,9 +443,12 @@ struct NumParams {
   // t*S + s): xent[...] = xent_row_w[row] * (xent_scale * v).  seq_xent keeps summing the unweighted xent_scale * v, and
   // deriv is not weighted here.  Null: no factor.
   const float *xent_row_w = nullptr;
-  // ragged end-to-end supervision: [S] frames of each sequence (device, in the supervision's pool slot); T above is the
-  // longest -- the tensors' and the scratch's T.  Null: uniform.  (The last member, as DenParams::seq_frames.)
+  // ragged supervision: [S] frames of each sequence (device, in the supervision's pool slot); T above is the
+  // longest -- the tensors' and the scratch's T.  Null: uniform.  (Behind every older member, as DenParams::seq_frames: the
+  // uniform kernels' argument offsets stay what they were.)
   const int32_t *seq_frames = nullptr;
+  // ragged regular supervision: NumTables::seq_level_off on the device ([S + 1]); null otherwise
+  const int32_t *seq_level_off = nullptr;
 };
 
 }  // namespace tc
@@ -452,13 +459,15 @@ struct tc_supervision {
   bool e2e = false;  // tc_supervision_create_e2e: `e2e_tab` holds the tables, `tab` is empty
   tc::NumTables tab;
   tc::E2eTables e2e_tab;
-  // tc_supervision_create_e2e_ragged: the sequences' lengths (S entries, T above is the longest); empty: uniform
+  // tc_supervision_create_ragged / tc_supervision_create_e2e_ragged: the sequences' lengths (S entries, T above is the
+  // longest); empty: uniform
   std::vector<int32_t> frames;
   int64_t total_frames = 0;        // their sum (S * T for a uniform handle)
   std::vector<size_t> blob_off;    // offsets of the tables inside a pool slot
   std::mutex mu;
   std::map<int, tc::NumDev> dev;
   std::map<int, const int32_t *> frames_dev;  // ragged: the lengths in the device's pool slot, behind the tables
+  std::map<int, const int32_t *> level_off_dev;  // ragged regular: NumTables::seq_level_off, in the same slot
 };
 
 namespace tc {

@@ -27,7 +27,10 @@ namespace tc {
 // for 150 frames whatever the batch; from LDS the chain is a fraction of that.
 // (the arithmetic itself is in num_device.h, shared with the level-windowed kernel)
 // E: element type of y / xent_out when they are the caller's (B, C, T) tensors (NumParams::elem; 2-D: float32)
-template <bool STAGE, typename E = float>
+// RAGGED (a ragged supervision, NumParams::seq_frames): the sequence walks its own T_s frames, its level bounds start at
+// seq_level_off[q]; p.T stays the T of the tensors (num_load_y, num_scatter_one) and of the LDS layout.  No padding row of
+// y, deriv, xent or xent_out is touched: the tables hold the sequence's own frames only.
+template <bool STAGE, typename E = float, bool RAGGED = false>
 __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   double *log_alpha = reinterpret_cast<double *>(lds_raw);
@@ -46,11 +49,12 @@ __global__ __launch_bounds__(128) void num_fwd_bwd_kernel(const NumParams p) {
 
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int T = p.T;
+  // (a scalar: the frame loops and their barriers are the workgroup's)
+  const int T = RAGGED ? ragged_frames(p.seq_frames, q, p.T) : p.T;
   const int sb = p.t.seq_state_off[q], nst = p.t.seq_state_off[q + 1] - sb;
   const int ab = p.t.seq_arc_off[q], narc = p.t.seq_arc_off[q + 1] - ab;
   const int ub = p.t.seq_uniq_off[q], nu = p.t.seq_uniq_off[q + 1] - ub;
-  const int *g_level = p.t.level_begin + (int64_t)q * (T + 2);
+  const int *g_level = p.t.level_begin + (RAGGED ? (int64_t)__builtin_amdgcn_readfirstlane(p.seq_level_off[q]) : (int64_t)q * (T + 2));
   const int *g_out_begin = p.t.out_begin + sb + q;
   const int *g_in_begin = p.t.in_begin + sb + q;
   const int *g_in_arc = p.t.in_arc + ab;
@@ -169,12 +173,21 @@ int launch_num_scatter(const NumParams &p, hipStream_t stream) {
 }
 
 namespace {
-template <bool STAGE, typename E>
+template <bool STAGE, typename E, bool RAGGED>
 int launch_num_fwd_bwd(const NumParams &p, size_t lds, hipStream_t stream) {
-  TC_HIP_CHECK(allow_dynamic_lds((const void *)num_fwd_bwd_kernel<STAGE, E>, lds));
-  hipLaunchKernelGGL((num_fwd_bwd_kernel<STAGE, E>), dim3(p.S), dim3(128), lds, stream, p);
+  TC_HIP_CHECK(allow_dynamic_lds((const void *)num_fwd_bwd_kernel<STAGE, E, RAGGED>, lds));
+  hipLaunchKernelGGL((num_fwd_bwd_kernel<STAGE, E, RAGGED>), dim3(p.S), dim3(128), lds, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
+}
+
+template <bool STAGE, typename E>
+int launch_num_fwd_bwd(const NumParams &p, size_t lds, hipStream_t stream) {
+  if (p.seq_frames) {  // a ragged supervision: its own level offsets come with its lengths
+    if (!p.seq_level_off) return TC_ERR_INVALID_ARGUMENT;
+    return launch_num_fwd_bwd<STAGE, E, true>(p, lds, stream);
+  }
+  return launch_num_fwd_bwd<STAGE, E, false>(p, lds, stream);
 }
 
 template <bool STAGE>
@@ -192,7 +205,8 @@ int launch_num(const NumParams &p, hipStream_t stream) {
   const size_t lds = (size_t)p.lds_states * 16 + (size_t)p.lds_uniq * 4 + (size_t)p.lds_arcs * 4;
   // a sequence that does not fit one workgroup's LDS: a window of levels instead (num_windowed_kernels.hip)
   if (lds > (size_t)kLdsLimitBytes || debug_flag(kDbgForceNumWindowed)) return launch_num_windowed(p, stream);
-  // with the sequence's tables staged in LDS when that keeps a workgroup within a quarter of a CU's LDS
+  // with the sequence's tables staged in LDS when that keeps a workgroup within a quarter of a CU's LDS (a ragged batch:
+  // p.T is its longest sequence, as the maxima in p.lds_* are the batch's)
   const size_t staged = lds + ((size_t)2 * (p.lds_states + 2) + (size_t)5 * p.lds_arcs + (size_t)(p.T + 2)) * 4;
   if (staged <= (size_t)kLdsLimitBytes / 4) return launch_num_fwd_bwd<true>(p, staged, stream);
   return launch_num_fwd_bwd<false>(p, lds, stream);

@@ -29,7 +29,10 @@ namespace tc {
 constexpr int kWinThreads = 256;
 
 // E: element type of y / xent_out when they are the caller's (B, C, T) tensors (NumParams::elem; 2-D: float32)
-template <typename E = float>
+// RAGGED (a ragged supervision, NumParams::seq_frames): the sequence walks its own T_s frames; its level bounds start at
+// seq_level_off[q] and its frame_uniq entries at seq_level_off[q] - q (one entry fewer per sequence); p.T stays the T of the
+// tensors.  No padding row is touched.
+template <typename E = float, bool RAGGED = false>
 __global__ __launch_bounds__(kWinThreads) void num_windowed_kernel(const NumParams p) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   double *alpha_w = reinterpret_cast<double *>(lds_raw);  // [2][win_states]
@@ -39,12 +42,13 @@ __global__ __launch_bounds__(kWinThreads) void num_windowed_kernel(const NumPara
   __shared__ double tot_sh;
 
   const int q = blockIdx.x, tid = threadIdx.x;
-  const int T = p.T, W = p.win_states;
+  const int T = RAGGED ? ragged_frames(p.seq_frames, q, p.T) : p.T, W = p.win_states;  // (T: a scalar, as the barriers need)
+  const int64_t lo = RAGGED ? (int64_t)__builtin_amdgcn_readfirstlane(p.seq_level_off[q]) : (int64_t)q * (T + 2);
   const int sb = p.t.seq_state_off[q];
   const int ab = p.t.seq_arc_off[q];
   const int ub = p.t.seq_uniq_off[q], nu = p.t.seq_uniq_off[q + 1] - ub;
-  const int *level = p.t.level_begin + (int64_t)q * (T + 2);
-  const int *frame_uniq = p.t.frame_uniq + (int64_t)q * (T + 1);
+  const int *level = p.t.level_begin + lo;
+  const int *frame_uniq = p.t.frame_uniq + (RAGGED ? lo - q : (int64_t)q * (T + 1));
   const int *out_begin = p.t.out_begin + sb + q;
   const int *in_begin = p.t.in_begin + sb + q;
   const int *in_arc = p.t.in_arc + ab;
@@ -123,12 +127,21 @@ __global__ __launch_bounds__(kWinThreads) void num_windowed_kernel(const NumPara
 }
 
 namespace {
-template <typename E>
+template <typename E, bool RAGGED>
 int launch_windowed(const NumParams &p, size_t lds, hipStream_t stream) {
-  TC_HIP_CHECK(allow_dynamic_lds((const void *)num_windowed_kernel<E>, lds));
-  hipLaunchKernelGGL((num_windowed_kernel<E>), dim3(p.S), dim3(kWinThreads), lds, stream, p);
+  TC_HIP_CHECK(allow_dynamic_lds((const void *)num_windowed_kernel<E, RAGGED>, lds));
+  hipLaunchKernelGGL((num_windowed_kernel<E, RAGGED>), dim3(p.S), dim3(kWinThreads), lds, stream, p);
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
+}
+
+template <typename E>
+int launch_windowed(const NumParams &p, size_t lds, hipStream_t stream) {
+  if (p.seq_frames) {  // a ragged supervision: its own level offsets come with its lengths
+    if (!p.seq_level_off) return TC_ERR_INVALID_ARGUMENT;
+    return launch_windowed<E, true>(p, lds, stream);
+  }
+  return launch_windowed<E, false>(p, lds, stream);
 }
 }  // namespace
 

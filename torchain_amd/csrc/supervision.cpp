@@ -2,7 +2,8 @@
 // egs.outputs[0].supervision (src/my_lib_example.cpp:71-76) and Kaldi's NumeratorComputation walks
 // the merged FST serially on the CPU.  Here the merged acceptor is split once, on the host, into its
 // num_sequences independent per-sequence acceptors so that the HIP kernel can run one wavefront per
-// sequence; the split is exact (see split comment below).
+// sequence; the split is exact (see split comment below).  tc_supervision_create_ragged takes the per-sequence acceptors
+// themselves, each of its own length; both entries build a sequence's tables in append_sequence.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -135,6 +136,140 @@ int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream) {
 
 }  // namespace tc
 
+namespace {
+
+// Scratch of the unique-(frame, pdf) pass, kept across the sequences of one handle.
+struct SeqScratch {
+  std::vector<int32_t> map_this_frame, touched, ucount;
+};
+
+// One sequence's tables, appended to `tb`: the arcs by local source state, the in-arc lists, the unique (frame, pdf)
+// entries, frame_uniq, the level maxima and max_*.  Both create entries build every sequence here.  The sequence has
+// `nloc` local states in time order, local 0 its start; level[0 .. T + 1] are the local ids where its time levels begin
+// (level[T + 1] = nloc); final_logw[ls] = -final cost (-inf: not final).  Local state ls owns the arcs of state
+// state_of(ls) of the CSR (arc_begin / arc_ilabel / arc_weight / arc_next), none when that is negative; local_of maps an
+// arc's next state to its local id.
+template <class StateOf, class LocalOf>
+void append_sequence(NumTables &tb, int32_t T, int32_t label_dim, int32_t nloc, const int32_t *level, const float *final_logw,
+                     const int32_t *arc_begin, const int32_t *arc_ilabel, const float *arc_weight, const int32_t *arc_next,
+                     StateOf state_of, LocalOf local_of, SeqScratch &sc) {
+  std::vector<int32_t> &map_this_frame = sc.map_this_frame, &touched = sc.touched, &ucount = sc.ucount;
+  const int32_t abase = (int32_t)tb.arc_src.size();
+  tb.final_logw.insert(tb.final_logw.end(), final_logw, final_logw + nloc);
+  // level boundaries in local state ids (T + 2 entries)
+  const size_t lb = tb.level_begin.size();
+  tb.level_begin.insert(tb.level_begin.end(), level, level + T + 2);
+  // arcs, sorted by local source state; out_begin has nloc + 1 entries per sequence
+  for (int32_t ls = 0; ls < nloc; ++ls) {
+    const int32_t g = state_of(ls);
+    tb.out_begin.push_back((int32_t)tb.arc_src.size() - abase);
+    if (g < 0) continue;
+    for (int32_t a = arc_begin[g]; a < arc_begin[g + 1]; ++a) {
+      tb.arc_src.push_back(ls);
+      tb.arc_dst.push_back(local_of(arc_next[a]));
+      tb.arc_logw.push_back(-arc_weight[a]);
+      tb.arc_uniq.push_back(arc_ilabel[a] - 1);  // pdf for now; replaced by the uniq id below
+    }
+  }
+  tb.out_begin.push_back((int32_t)tb.arc_src.size() - abase);
+  const int32_t narc = (int32_t)tb.arc_src.size() - abase;
+  // in-arc lists (stable by arc id)
+  {
+    std::vector<int32_t> cnt(nloc + 1, 0);
+    for (int32_t a = 0; a < narc; ++a) cnt[tb.arc_dst[abase + a] + 1]++;
+    for (int32_t i = 0; i < nloc; ++i) cnt[i + 1] += cnt[i];
+    for (int32_t i = 0; i <= nloc; ++i) tb.in_begin.push_back(cnt[i]);
+    std::vector<int32_t> fillv(cnt.begin(), cnt.end() - 1);
+    const size_t ib = tb.in_arc.size();
+    tb.in_arc.resize(ib + narc);
+    for (int32_t a = 0; a < narc; ++a) tb.in_arc[ib + fillv[tb.arc_dst[abase + a]]++] = a;
+  }
+  // unique (frame, pdf) pairs, in first-occurrence order like [K] ComputeLookupIndexes
+  {
+    const int32_t ubase = (int32_t)tb.uniq_t.size();
+    // (counting sort by unique id: a list per id would be one heap allocation per (frame, pdf) pair -- tens of
+    // thousands per minibatch, most of this function's time when a fresh supervision arrives every step)
+    map_this_frame.assign(label_dim, -1);
+    touched.clear();
+    ucount.clear();
+    int32_t cur_t = 0;
+    int32_t t = 0;  // arcs are emitted in source-state order, so the frame only ever moves forward
+    for (int32_t a = 0; a < narc; ++a) {
+      const int32_t ls = tb.arc_src[abase + a];
+      while (t + 1 <= T && tb.level_begin[lb + t + 1] <= ls) ++t;
+      if (t != cur_t) {
+        for (int32_t p : touched) map_this_frame[p] = -1;
+        touched.clear();
+        cur_t = t;
+      }
+      const int32_t pdf = tb.arc_uniq[abase + a];
+      int32_t u = map_this_frame[pdf];
+      if (u < 0) {
+        u = (int32_t)ucount.size();
+        map_this_frame[pdf] = u;
+        touched.push_back(pdf);
+        tb.uniq_t.push_back(t);
+        tb.uniq_pdf.push_back(pdf);
+        ucount.push_back(0);
+      }
+      ucount[u]++;
+      tb.arc_uniq[abase + a] = u;
+    }
+    int32_t run = 0;
+    const size_t ub = tb.uniq_begin.size(), ua = tb.uniq_arc.size();
+    for (int32_t c : ucount) {
+      tb.uniq_begin.push_back(run);
+      run += c;
+    }
+    tb.uniq_arc.resize(ua + narc);
+    for (size_t u = 0; u < ucount.size(); ++u) ucount[u] = tb.uniq_begin[ub + u];  // fill positions
+    for (int32_t a = 0; a < narc; ++a) tb.uniq_arc[ua + ucount[tb.arc_uniq[abase + a]]++] = a;
+    tb.uniq_begin.push_back(run);
+    tb.seq_uniq_off.push_back((int32_t)tb.uniq_t.size());
+    tb.max_uniq = std::max(tb.max_uniq, (int32_t)tb.uniq_t.size() - ubase);
+    // where each frame's entries begin (the frame only moves forward, so they are one range per frame)
+    const int32_t nu = (int32_t)tb.uniq_t.size() - ubase;
+    const size_t fb = tb.frame_uniq.size();
+    tb.frame_uniq.resize(fb + T + 1, nu);
+    for (int32_t u = nu - 1; u >= 0; --u) tb.frame_uniq[fb + tb.uniq_t[ubase + u]] = u;
+    for (int32_t f = T - 1; f >= 0; --f)
+      if (tb.frame_uniq[fb + f] > tb.frame_uniq[fb + f + 1]) tb.frame_uniq[fb + f] = tb.frame_uniq[fb + f + 1];
+    for (int32_t f = 0; f < T; ++f)
+      tb.max_frame_uniq = std::max(tb.max_frame_uniq, tb.frame_uniq[fb + f + 1] - tb.frame_uniq[fb + f]);
+  }
+  // the widest level and the most arcs leaving one level (the level-windowed kernel's LDS: num_windowed_kernels.hip)
+  const int32_t *lv = &tb.level_begin[lb];
+  const int32_t *ob = &tb.out_begin[tb.out_begin.size() - (size_t)(nloc + 1)];  // this sequence's nloc + 1 entries
+  for (int32_t t = 0; t <= T; ++t) {
+    tb.max_level_states = std::max(tb.max_level_states, lv[t + 1] - lv[t]);
+    tb.max_level_arcs = std::max(tb.max_level_arcs, ob[lv[t + 1]] - ob[lv[t]]);
+  }
+  tb.seq_state_off.push_back((int32_t)tb.final_logw.size());
+  tb.seq_arc_off.push_back((int32_t)tb.arc_src.size());
+  tb.seq_level_off.push_back(tb.seq_level_off.back() + T + 2);
+  tb.max_states = std::max(tb.max_states, nloc);
+  tb.max_arcs = std::max(tb.max_arcs, narc);
+}
+
+void begin_tables(NumTables &tb, int32_t num_states, int32_t num_arcs, int32_t S, int64_t levels) {
+  tb.seq_state_off.push_back(0);
+  tb.seq_arc_off.push_back(0);
+  tb.seq_uniq_off.push_back(0);
+  tb.seq_level_off.push_back(0);
+  tb.arc_src.reserve(num_arcs);
+  tb.arc_dst.reserve(num_arcs);
+  tb.arc_logw.reserve(num_arcs);
+  tb.arc_uniq.reserve(num_arcs);
+  tb.in_arc.reserve(num_arcs);
+  tb.uniq_arc.reserve(num_arcs);
+  tb.final_logw.reserve((size_t)num_states + S);
+  tb.out_begin.reserve((size_t)num_states + 2 * S);
+  tb.in_begin.reserve((size_t)num_states + 2 * S);
+  tb.level_begin.reserve((size_t)levels);
+}
+
+}  // namespace
+
 extern "C" {
 
 int tc_supervision_create(tc_supervision **out, float weight, int32_t S, int32_t T, int32_t label_dim,
@@ -177,22 +312,12 @@ int tc_supervision_create(tc_supervision **out, float weight, int32_t S, int32_t
   sup->T = T;
   sup->P = label_dim;
   NumTables &tb = sup->tab;
-  tb.seq_state_off.push_back(0);
-  tb.seq_arc_off.push_back(0);
-  tb.seq_uniq_off.push_back(0);
+  begin_tables(tb, num_states, num_arcs, S, (int64_t)S * (T + 2));
   const float kInf = std::numeric_limits<float>::infinity();
   std::vector<float> boundary_final;  // final weights (tropical) of the states at time (q+1)*T for sequence q
-  std::vector<int32_t> map_this_frame, touched, ucount;  // scratch of the unique-(frame, pdf) pass
-  tb.arc_src.reserve(num_arcs);
-  tb.arc_dst.reserve(num_arcs);
-  tb.arc_logw.reserve(num_arcs);
-  tb.arc_uniq.reserve(num_arcs);
-  tb.in_arc.reserve(num_arcs);
-  tb.uniq_arc.reserve(num_arcs);
-  tb.final_logw.reserve((size_t)num_states + S);
-  tb.out_begin.reserve((size_t)num_states + 2 * S);
-  tb.in_begin.reserve((size_t)num_states + 2 * S);
-  tb.level_begin.reserve((size_t)S * (T + 2));
+  std::vector<float> seq_final;       // the sequence's final_logw, by local state
+  std::vector<int32_t> level;         // its T + 2 level boundaries
+  SeqScratch scratch;
 
   for (int32_t q = 0; q < S; ++q) {
     const int32_t b0 = time_begin[(size_t)q * T];           // first state at this sequence's start time
@@ -227,104 +352,92 @@ int tc_supervision_create(tc_supervision **out, float weight, int32_t S, int32_t
     }
     // local numbering: local 0 = start; global state g in (b1 .. e1) -> g - b1 + 1
     const int32_t nloc = 1 + (e1 - b1);
-    const int32_t sbase = (int32_t)tb.final_logw.size();
-    const int32_t abase = (int32_t)tb.arc_src.size();
     auto local = [&](int32_t g) { return g - b1 + 1; };
-    for (int32_t i = 0; i < nloc; ++i) tb.final_logw.push_back(-kInf);
-    for (int32_t s = e0; s < e1; ++s) tb.final_logw[sbase + local(s)] = -boundary_final[s - e0];
-    // level boundaries in local state ids (T + 2 entries)
-    tb.level_begin.push_back(0);
-    for (int32_t t = 1; t <= T; ++t) tb.level_begin.push_back(local(time_begin[(size_t)q * T + t]));
-    tb.level_begin.push_back(nloc);
-    // arcs, sorted by local source state; out_begin has nloc + 1 entries per sequence
-    for (int32_t ls = 0; ls < nloc; ++ls) {
+    seq_final.assign(nloc, -kInf);
+    for (int32_t s = e0; s < e1; ++s) seq_final[local(s)] = -boundary_final[s - e0];
+    level.clear();
+    level.push_back(0);
+    for (int32_t t = 1; t <= T; ++t) level.push_back(local(time_begin[(size_t)q * T + t]));
+    level.push_back(nloc);
+    // local state ls owns the arcs of global state b0 (the start) or b1 + ls - 1; end-time states own none: their arcs
+    // belong to the next sequence
+    auto state_of = [&](int32_t ls) {
       const int32_t g = (ls == 0) ? b0 : (b1 + ls - 1);
-      tb.out_begin.push_back((int32_t)tb.arc_src.size() - abase);
-      if (ls > 0 && g >= e0) continue;  // end-time states: their arcs belong to the next sequence
-      for (int32_t a = arc_begin[g]; a < arc_begin[g + 1]; ++a) {
-        tb.arc_src.push_back(ls);
-        tb.arc_dst.push_back(local(arc_next[a]));
-        tb.arc_logw.push_back(-arc_weight[a]);
-        tb.arc_uniq.push_back(arc_ilabel[a] - 1);  // pdf for now; replaced by the uniq id below
-      }
+      return (ls > 0 && g >= e0) ? -1 : g;
+    };
+    append_sequence(tb, T, label_dim, nloc, level.data(), seq_final.data(), arc_begin, arc_ilabel, arc_weight, arc_next,
+                    state_of, local, scratch);
+  }
+  *out = sup;
+  return TC_OK;
+}
+
+// One time-unfolded acceptor per sequence, each of its own length: every sequence goes to append_sequence as it is (no
+// merge, no split, no re-weighting).  frames / total_frames make the handle ragged for everything that reads them.
+int tc_supervision_create_ragged(tc_supervision **out, float weight, int32_t S, const int32_t *frames_per_sequence,
+                                 int32_t label_dim, const int32_t *seq_state_begin, const int32_t *arc_begin,
+                                 const int32_t *arc_ilabel, const float *arc_weight, const int32_t *arc_next,
+                                 const float *final_weight) {
+  if (!out) return TC_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  if (S <= 0 || label_dim <= 0 || !frames_per_sequence || !seq_state_begin || !arc_begin || !final_weight)
+    return TC_ERR_INVALID_ARGUMENT;
+  int32_t tmax = 0;
+  int64_t levels = 0;
+  for (int32_t s = 0; s < S; ++s) {
+    if (frames_per_sequence[s] < 1) return TC_ERR_INVALID_ARGUMENT;
+    tmax = std::max(tmax, frames_per_sequence[s]);
+    levels += (int64_t)frames_per_sequence[s] + 2;
+  }
+  if ((int64_t)S * tmax > ((int64_t)1 << 26)) return TC_ERR_UNSUPPORTED;  // the egs readers' bound on a minibatch
+  if (seq_state_begin[0] != 0 || arc_begin[0] != 0) return TC_ERR_BAD_FST;
+  for (int32_t s = 0; s < S; ++s)
+    if (seq_state_begin[s + 1] <= seq_state_begin[s]) return TC_ERR_BAD_FST;  // (a sequence has its start state)
+  const int32_t num_states = seq_state_begin[S];
+  // the log-alpha history, one double per state (stage_locked): refused by the count alone, before the states are read
+  if ((int64_t)num_states * 8 > kE2eMaxScratchBytes) return TC_ERR_UNSUPPORTED;
+  for (int32_t g = 0; g < num_states; ++g)
+    if (arc_begin[g + 1] < arc_begin[g]) return TC_ERR_BAD_FST;
+  const int32_t num_arcs = arc_begin[num_states];
+  if (num_arcs > 0 && (!arc_ilabel || !arc_weight || !arc_next)) return TC_ERR_INVALID_ARGUMENT;
+
+  std::vector<std::vector<int32_t>> levels_of(S);
+  std::vector<int32_t> times;
+  for (int32_t s = 0; s < S; ++s) {
+    const int32_t sb = seq_state_begin[s], n = seq_state_begin[s + 1] - sb, T = frames_per_sequence[s];
+    for (int32_t a = arc_begin[sb]; a < arc_begin[sb + n]; ++a) {
+      if (arc_next[a] < 0 || arc_next[a] >= n) return TC_ERR_BAD_FST;
+      if (arc_ilabel[a] < 1 || arc_ilabel[a] > label_dim) return TC_ERR_BAD_FST;  // [K] pdf_id range assert
     }
-    tb.out_begin.push_back((int32_t)tb.arc_src.size() - abase);
-    const int32_t narc = (int32_t)tb.arc_src.size() - abase;
-    // in-arc lists (stable by arc id)
-    {
-      std::vector<int32_t> cnt(nloc + 1, 0);
-      for (int32_t a = 0; a < narc; ++a) cnt[tb.arc_dst[abase + a] + 1]++;
-      for (int32_t i = 0; i < nloc; ++i) cnt[i + 1] += cnt[i];
-      for (int32_t i = 0; i <= nloc; ++i) tb.in_begin.push_back(cnt[i]);
-      std::vector<int32_t> fillv(cnt.begin(), cnt.end() - 1);
-      const size_t ib = tb.in_arc.size();
-      tb.in_arc.resize(ib + narc);
-      for (int32_t a = 0; a < narc; ++a) tb.in_arc[ib + fillv[tb.arc_dst[abase + a]]++] = a;
-    }
-    // unique (frame, pdf) pairs, in first-occurrence order like [K] ComputeLookupIndexes
-    {
-      const int32_t ubase = (int32_t)tb.uniq_t.size();
-      // (counting sort by unique id: a list per id would be one heap allocation per (frame, pdf) pair -- tens of
-      // thousands per minibatch, most of this function's time when a fresh supervision arrives every step)
-      map_this_frame.assign(label_dim, -1);
-      touched.clear();
-      ucount.clear();
-      int32_t cur_t = 0;
-      int32_t t = 0;  // arcs are emitted in source-state order, so the frame only ever moves forward
-      for (int32_t a = 0; a < narc; ++a) {
-        const int32_t ls = tb.arc_src[abase + a];
-        while (t + 1 <= T && tb.level_begin[(size_t)q * (T + 2) + t + 1] <= ls) ++t;
-        if (t != cur_t) {
-          for (int32_t p : touched) map_this_frame[p] = -1;
-          touched.clear();
-          cur_t = t;
-        }
-        const int32_t pdf = tb.arc_uniq[abase + a];
-        int32_t u = map_this_frame[pdf];
-        if (u < 0) {
-          u = (int32_t)ucount.size();
-          map_this_frame[pdf] = u;
-          touched.push_back(pdf);
-          tb.uniq_t.push_back(t);
-          tb.uniq_pdf.push_back(pdf);
-          ucount.push_back(0);
-        }
-        ucount[u]++;
-        tb.arc_uniq[abase + a] = u;
-      }
-      int32_t run = 0;
-      const size_t ub = tb.uniq_begin.size(), ua = tb.uniq_arc.size();
-      for (int32_t c : ucount) {
-        tb.uniq_begin.push_back(run);
-        run += c;
-      }
-      tb.uniq_arc.resize(ua + narc);
-      for (size_t u = 0; u < ucount.size(); ++u) ucount[u] = tb.uniq_begin[ub + u];  // fill positions
-      for (int32_t a = 0; a < narc; ++a) tb.uniq_arc[ua + ucount[tb.arc_uniq[abase + a]]++] = a;
-      tb.uniq_begin.push_back(run);
-      tb.seq_uniq_off.push_back((int32_t)tb.uniq_t.size());
-      tb.max_uniq = std::max(tb.max_uniq, (int32_t)tb.uniq_t.size() - ubase);
-      // where each frame's entries begin (the frame only moves forward, so they are one range per frame)
-      const int32_t nu = (int32_t)tb.uniq_t.size() - ubase;
-      const size_t fb = tb.frame_uniq.size();
-      tb.frame_uniq.resize(fb + T + 1, nu);
-      for (int32_t u = nu - 1; u >= 0; --u) tb.frame_uniq[fb + tb.uniq_t[ubase + u]] = u;
-      for (int32_t f = T - 1; f >= 0; --f)
-        if (tb.frame_uniq[fb + f] > tb.frame_uniq[fb + f + 1]) tb.frame_uniq[fb + f] = tb.frame_uniq[fb + f + 1];
-      for (int32_t f = 0; f < T; ++f)
-        tb.max_frame_uniq = std::max(tb.max_frame_uniq, tb.frame_uniq[fb + f + 1] - tb.frame_uniq[fb + f]);
-    }
-    // the widest level and the most arcs leaving one level (the level-windowed kernel's LDS: num_windowed_kernels.hip)
-    const int32_t *lv = &tb.level_begin[(size_t)q * (T + 2)];
-    const int32_t *ob = &tb.out_begin[tb.out_begin.size() - (size_t)(nloc + 1)];  // this sequence's nloc + 1 entries
-    for (int32_t t = 0; t <= T; ++t) {
-      tb.max_level_states = std::max(tb.max_level_states, lv[t + 1] - lv[t]);
-      tb.max_level_arcs = std::max(tb.max_level_arcs, ob[lv[t + 1]] - ob[lv[t]]);
-    }
-    tb.seq_state_off.push_back((int32_t)tb.final_logw.size());
-    tb.seq_arc_off.push_back((int32_t)tb.arc_src.size());
-    tb.max_states = std::max(tb.max_states, nloc);
-    tb.max_arcs = std::max(tb.max_arcs, narc);
+    // (arc_begin's entries are positions in the concatenated arc arrays; next states are local to the sequence)
+    if (state_times(n, arc_begin + sb, arc_ilabel, arc_next, final_weight + sb, &times) != T) return TC_ERR_BAD_FST;
+    for (int32_t i = 1; i < n; ++i)
+      if (times[i] < times[i - 1]) return TC_ERR_BAD_FST;  // states must be numbered in time order
+    if (times[n - 1] > T) return TC_ERR_BAD_FST;           // a path that goes on beyond the final states' level
+    std::vector<int32_t> &level = levels_of[s];
+    level.assign((size_t)T + 2, n);
+    for (int32_t i = n - 1; i >= 0; --i) level[times[i]] = i;
+    for (int32_t t = T; t >= 0; --t)
+      if (level[t] > level[t + 1]) level[t] = level[t + 1];
+  }
+
+  tc_supervision *sup = new tc_supervision();
+  sup->weight = weight;
+  sup->S = S;
+  sup->T = tmax;
+  sup->P = label_dim;
+  sup->frames.assign(frames_per_sequence, frames_per_sequence + S);
+  for (int32_t s = 0; s < S; ++s) sup->total_frames += frames_per_sequence[s];
+  NumTables &tb = sup->tab;
+  begin_tables(tb, num_states, num_arcs, S, levels);
+  std::vector<float> seq_final;
+  SeqScratch scratch;
+  for (int32_t s = 0; s < S; ++s) {
+    const int32_t sb = seq_state_begin[s], n = seq_state_begin[s + 1] - sb;
+    seq_final.resize(n);
+    for (int32_t i = 0; i < n; ++i) seq_final[i] = -final_weight[sb + i];  // (+inf: not final -> -inf)
+    append_sequence(tb, frames_per_sequence[s], label_dim, n, levels_of[s].data(), seq_final.data(), arc_begin, arc_ilabel,
+                    arc_weight, arc_next, [&](int32_t ls) { return sb + ls; }, [](int32_t next) { return next; }, scratch);
   }
   *out = sup;
   return TC_OK;
@@ -388,8 +501,12 @@ static int stage_locked(tc_supervision *sup, int device) {
       {tb.uniq_begin.data(), tb.uniq_begin.size() * 4},       {tb.uniq_arc.data(), tb.uniq_arc.size() * 4},
       {tb.arc_logw.data(), tb.arc_logw.size() * 4},           {tb.final_logw.data(), tb.final_logw.size() * 4},
       {tb.frame_uniq.data(), tb.frame_uniq.size() * 4},
+      // a ragged handle (tc_supervision_create_ragged): where each sequence's levels begin, and the lengths, travel with
+      // the tables (as stage_e2e_locked's lengths do)
+      {tb.seq_level_off.data(), tb.seq_level_off.size() * 4}, {sup->frames.data(), sup->frames.size() * 4},
   };
-  const int nparts = (int)(sizeof(parts) / sizeof(parts[0]));
+  const bool ragged = !sup->frames.empty();
+  const int nparts = (int)(sizeof(parts) / sizeof(parts[0])) - (ragged ? 0 : 2);
   size_t total = 0;
   sup->blob_off.clear();
   for (int i = 0; i < nparts; ++i) {
@@ -430,6 +547,10 @@ static int stage_locked(tc_supervision *sup, int device) {
   d.stage = (float *)(blob + stage_off);
   d.alpha_hist = (double *)(blob + hist_off);
   sup->dev[device] = d;
+  if (ragged) {
+    sup->level_off_dev[device] = P(17);
+    sup->frames_dev[device] = P(18);
+  }
   return TC_OK;
 }
 

@@ -500,7 +500,10 @@ def append_supervisions_numpy(sups):
 
 def append_supervisions(sups):
     """[K] AppendSupervision (see ``append_supervisions_numpy``) through the library's ``tc_supervision_append``: the
-    reference merges natively too (``src/my_lib_example_rand.cpp:160``).  Host memory only."""
+    reference merges natively too (``src/my_lib_example_rand.cpp:160``).  Host memory only.
+
+    Pieces of unequal ``frames_per_sequence`` are refused, as [K] refuses them: a merged supervision has one length.  Whole
+    utterances of unequal lengths go into one minibatch without a merge, through ``io.Supervision.from_sequences``."""
     import ctypes as C
 
     from ._lib import lib

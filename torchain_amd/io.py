@@ -210,6 +210,70 @@ class Supervision:
               "tc_supervision_create_e2e")
         return cls(handle)
 
+    @classmethod
+    def from_fsts(cls, weight, frames_per_sequence, label_dim, fsts):
+        """Regular supervisions of unequal lengths (a "ragged" minibatch of whole utterances): one time-unfolded acceptor
+        per sequence, as alignments and lattices give them.  ``fsts`` is a list of per-sequence
+        ``(arc_begin, ilabel, arc_weight, nextstate, final)`` in CSR form -- each what ``from_fst`` takes with
+        ``num_sequences = 1``: state 0 the start, states in time order, every path exactly that sequence's number of arcs
+        long, ``ilabel`` = pdf_id + 1, tropical costs, ``final`` = inf for a state that is not final.
+        ``frames_per_sequence``: one int per sequence.
+
+        ``n_frame`` and ``shape`` use the longest length ``Tmax``, as for ``from_e2e_fsts`` with a list of lengths: every
+        tensor keeps its ``(B, C, Tmax)`` / ``(Tmax * B, C)`` shape, frames ``t >= frames[s]`` of sequence ``s`` are padding
+        that influences nothing, and every gradient is exactly zero there.  For every sequence the numerator computes the
+        bits it computes on that sequence alone."""
+        fsts = list(fsts)
+        if not fsts:
+            raise ValueError("from_fsts: no FSTs")
+        lengths = np.asarray(frames_per_sequence)
+        if lengths.shape != (len(fsts),) or lengths.dtype.kind not in "iu":
+            raise ValueError("from_fsts: frames_per_sequence must be one int per sequence")
+        lengths = _i32(lengths)
+        seq_begin, ab, il, aw, nx, fin = [0], [np.zeros(1, np.int32)], [], [], [], []
+        arcs = 0
+        for arc_begin, ilabel, arc_weight, nextstate, final in fsts:
+            arc_begin = np.asarray(arc_begin, dtype=np.int64)
+            final = np.asarray(final, dtype=np.float32).ravel()
+            if arc_begin.shape != (len(final) + 1,) or arc_begin[0] != 0:
+                raise ValueError("from_fsts: arc_begin must have len(final) + 1 entries starting at 0")
+            if any(np.asarray(x).size != arc_begin[-1] for x in (ilabel, arc_weight, nextstate)):
+                raise ValueError("from_fsts: sequence %d: ilabel, arc_weight and nextstate must have arc_begin[-1] "
+                                 "entries" % (len(seq_begin) - 1))
+            seq_begin.append(seq_begin[-1] + len(final))
+            ab.append((arc_begin[1:] + arcs).astype(np.int32))
+            arcs += int(arc_begin[-1])
+            il.append(np.asarray(ilabel, dtype=np.int32).ravel())
+            aw.append(np.asarray(arc_weight, dtype=np.float32).ravel())
+            nx.append(np.asarray(nextstate, dtype=np.int32).ravel())
+            fin.append(final)
+        sb = _i32(seq_begin)
+        ab, il, nx = _i32(np.concatenate(ab)), _i32(np.concatenate(il)), _i32(np.concatenate(nx))
+        aw, fin = _f32(np.concatenate(aw)), _f32(np.concatenate(fin))
+        handle = C.c_void_p()
+        check(lib.tc_supervision_create_ragged(C.byref(handle), float(weight), len(fsts), _p(lengths), int(label_dim),
+                                               _p(sb), _p(ab), _p(il), _p(aw), _p(nx), _p(fin)),
+              "tc_supervision_create_ragged")
+        return cls(handle)
+
+    @classmethod
+    def from_sequences(cls, sups):
+        """A ragged minibatch from single-sequence regular supervisions (``torchain_amd.synth.SupFst`` with
+        ``num_sequences == 1``: what the egs readers return for one eg), each of its own ``frames_per_sequence``.  They must
+        share ``weight`` and ``label_dim``."""
+        sups = list(sups)
+        if not sups:
+            raise ValueError("from_sequences: no supervisions")
+        for i, s in enumerate(sups):
+            if isinstance(s, _egs.E2eSup):
+                raise ValueError("from_sequences: supervision %d is an end-to-end one (from_e2e_fsts takes their lengths)" % i)
+            if int(s.num_sequences) != 1:
+                raise ValueError("from_sequences: supervision %d has %d sequences, not 1" % (i, s.num_sequences))
+            if float(s.weight) != float(sups[0].weight) or int(s.label_dim) != int(sups[0].label_dim):
+                raise ValueError("from_sequences: supervision %d differs from the first in weight or label_dim" % i)
+        return cls.from_fsts(sups[0].weight, [int(s.frames_per_sequence) for s in sups], sups[0].label_dim,
+                             [(s.arc_begin, s.ilabel, s.arc_weight, s.nextstate, s.final) for s in sups])
+
     @property
     def is_e2e(self):
         """True for an end-to-end supervision (``from_e2e_fsts``)."""
@@ -217,12 +281,14 @@ class Supervision:
 
     @property
     def is_ragged(self):
-        """True for an end-to-end supervision made with one length per sequence."""
+        """True for a supervision made with one length per sequence (``from_fsts``, ``from_sequences``, ``from_e2e_fsts``
+        with a list of lengths), also when the lengths are all equal."""
         return bool(lib.tc_supervision_is_ragged(self.ptr))
 
     @property
     def frames(self):
-        """The sequences' lengths (numpy int32, ``n_batch`` entries; all ``n_frame`` unless ``is_ragged``)."""
+        """The sequences' lengths (numpy int32, ``n_batch`` entries; all ``n_frame`` unless ``is_ragged``, regular and
+        end-to-end supervisions alike)."""
         out = np.zeros(self.n_batch, dtype=np.int32)
         check(lib.tc_supervision_frames(self.ptr, _p(out)), "tc_supervision_frames")
         return out
