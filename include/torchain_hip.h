@@ -565,6 +565,36 @@ int tc_num_forward_backward(tc_supervision *supervision, const float *nnet_outpu
                             double *logprob_dev, void *workspace, int64_t workspace_bytes, int device,
                             void *stream);
 
+/* The single most likely path of every sequence of a supervision under the network's outputs: the frame-level pdf
+ * alignment ([K] gets it from a CPU decoder, one utterance at a time; a flat-start recipe builds its regular chain model
+ * from it, and frame accuracies are counted against it).  Regular and end-to-end handles, uniform and ragged.
+ *   nnet_output : layout_bct == 0: the 2-D float32 matrix (T*S, P), row t*S + s, rows row_stride floats apart (dtype must
+ *                 be TC_DTYPE_F32); layout_bct != 0: the contiguous (S, P, T) tensor of `dtype` (TC_DTYPE_*; row_stride is
+ *                 not read).  num_rows == S * T and num_cols == P of the handle, T the longest sequence's.
+ *   pdf_dev     : device int32[S * T]; entry s * T + t is the pdf (0-based: ilabel - 1) of frame t of sequence s, -1 in
+ *                 the padding frames t >= T_s of a ragged handle
+ *   score_dev   : device double[S]: the path's log score, the sum of y_t(pdf_t) - arc cost along the path minus the final
+ *                 cost.  The supervision's weight does not enter.
+ * A sequence with no path of exactly T_s arcs to a final state gets score -inf and -1 in all its frames; the other
+ * sequences are unaffected.  Nothing at frames >= T_s is read.  Among paths of exactly equal score one is returned, the
+ * same one at every call.
+ * Arithmetic: the numerator's forward recursion with max in place of the log-sum -- each y + (-cost) is one float32 sum,
+ * everything else is double -- so the score is within T_s * 2^-23 * max(|y| + |cost|) of the path's float64 score.
+ * One launch (num_best_path_kernels.hip): one workgroup per sequence walks the frames with two adjacent levels (regular)
+ * or two score vectors (end-to-end) in LDS and leaves every state's score in the supervision's pool slot -- the history
+ * the numerator kernels use, which is scratch: a later objective call on the handle gives the bits it gives without
+ * this call -- then one wavefront traces back from the best final state.  A regular supervision needs
+ * 16 * L + 4 * U + 2048 <= 163840 bytes of LDS, L the widest time level's states (rounded up to 2) and U the most unique
+ * (frame, pdf) entries of one frame (rounded up to 4): about 8000 states a level when each has a pdf of its own, where
+ * the level-windowed numerator needs 32 * L + 4 * U + 4 * (arcs leaving a level); beyond that TC_ERR_UNSUPPORTED.  End-to-end supervisions: the limits of
+ * tc_supervision_create_e2e.
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null pointer, num_rows or num_cols that are not the handle's, an
+ * unknown dtype, a 2-D call with a 16-bit dtype or row_stride < num_cols.  Asynchronous on `stream`; no workspace, and
+ * nothing is allocated once the supervision is staged.  tc_debug_counter("best_path_launches") counts the launches. */
+int tc_supervision_best_path(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
+                             int64_t num_rows, int32_t num_cols, int64_t row_stride, int32_t *pdf_dev, double *score_dev,
+                             int device, void *stream);
+
 /* The cross-entropy objective Kaldi's chain trainer reports next to the chain objective ([K]
  * nnet-chain-training.cc: TraceMatMat(xent_output, xent_deriv, kTrans), xent_deriv = w * numerator posteriors);
  * the reference leaves it as a TODO (torchain/functions.py:88-89).  objf_dev: device double[1].  Needs
@@ -702,7 +732,8 @@ int tc_debug_set(const char *key, int value);
  * "layout_launches");
  * "ragged_two_cu_launches" = denominator launches of a ragged batch that took two workgroups per sequence, each sequence
  * meeting at half its own length (tied graphs, 8 sequences up to half the device's CUs, a derivative asked for, neither
- * "no_mitm" nor "no_phase_split" set; counted in "den_launches" too).
+ * "no_mitm" nor "no_phase_split" set; counted in "den_launches" too);
+ * "best_path_launches" = tc_supervision_best_path calls that launched their kernel (not counted in "num_launches").
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -191,6 +191,8 @@ def _load():
     L.tc_xent_objf.argtypes = [vp, i64, i32, i64, vp, i64, vp, vp, i64, C.c_int, vp]
     L.tc_num_forward_backward.restype = C.c_int
     L.tc_num_forward_backward.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, vp, i64, C.c_int, vp]
+    L.tc_supervision_best_path.restype = C.c_int
+    L.tc_supervision_best_path.argtypes = [vp, vp, C.c_int, C.c_int, i64, i32, i64, vp, vp, C.c_int, vp]
     return L
 
 

@@ -480,6 +480,31 @@ int tc_num_forward_backward(tc_supervision *sup, const float *y, int64_t rows, i
   return supervision_mark_use(sup, device, stream);
 }
 
+int tc_supervision_best_path(tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows, int32_t cols,
+                             int64_t y_stride, int32_t *pdf_dev, double *score_dev, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!sup || !y || !pdf_dev || !score_dev) return TC_ERR_INVALID_ARGUMENT;
+  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && dtype != TC_DTYPE_F32) return TC_ERR_INVALID_ARGUMENT;  // (2-D tensors are float32, as NumParams::y)
+  if ((int64_t)sup->S * sup->T != rows || sup->P != cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  hipStream_t stream = (hipStream_t)stream_v;
+  NumParams p;
+  // (a (B, C, T) tensor has no row stride: fill_num_params is given the dense one)
+  int rc = fill_num_params(sup, device, stream, (const float *)y, rows, cols, layout_bct ? (int64_t)cols : y_stride, nullptr,
+                           0, nullptr, 0, nullptr, &p);
+  if (rc != TC_OK) return rc;
+  p.y_bct = layout_bct ? 1 : 0;
+  p.elem = dtype;
+  p.best_pdf = pdf_dev;
+  p.best_score = score_dev;
+  rc = launch_num_best_path(p, stream);
+  if (rc != TC_OK) return rc;
+  return supervision_mark_use(sup, device, stream);
+}
+
 }  // extern "C"
 
 // deriv_scale = 1: the reference's outputs.  deriv_scale = -1: what its backward returns (tc_chain_objf_and_grad).

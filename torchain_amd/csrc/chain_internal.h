@@ -449,6 +449,10 @@ struct NumParams {
   const int32_t *seq_frames = nullptr;
   // ragged regular supervision: NumTables::seq_level_off on the device ([S + 1]); null otherwise
   const int32_t *seq_level_off = nullptr;
+  // tc_supervision_best_path (num_best_path_kernels.hip): [S][T] the best path's pdf per frame (-1 in the padding and for a
+  // sequence without a path), [S] its log score.  Null for every other launch.  (At the end, as the two above.)
+  int32_t *best_pdf = nullptr;
+  double *best_score = nullptr;
 };
 
 }  // namespace tc
@@ -532,6 +536,7 @@ int launch_num_scatter(const NumParams &p, hipStream_t stream);
 int launch_num_windowed(const NumParams &p, hipStream_t stream);     // num_windowed_kernels.hip (via launch_num)
 int launch_num_e2e(const NumParams &p, hipStream_t stream);          // num_e2e_kernels.hip (via launch_num)
 int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via launch_num_scatter)
+int launch_num_best_path(const NumParams &p, hipStream_t stream);    // num_best_path_kernels.hip (regular and end-to-end)
 size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs);
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
@@ -625,7 +630,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -654,3 +654,15 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
 
 
 _ChainLoss = _ChainStep  # (the name the reference's module exports, torchain/functions.py)
+
+
+def best_path(input, supervision):
+    """The frame-level pdf alignment of ``supervision`` under ``input``, in the style of ``chain_loss``: ``(pdfs, scores)``,
+    int32 ``(B, Tmax)`` (``-1`` in padding frames) and float64 ``(B,)``, on the input's device
+    (``io.Supervision.best_path``, ``tc_supervision_best_path``).  ``input`` is what ``chain_loss`` takes; 2-D float32 and
+    dense ``(B, C, T)`` float32 / bfloat16 / float16 go to the kernel as they are, any other view through ``.contiguous()``
+    -- this is not a hot path.  Autograd is not involved."""
+    if not isinstance(supervision, io.Supervision):
+        raise TypeError("best_path takes an io.Supervision, got %s" % type(supervision).__name__)
+    with torch.no_grad():
+        return supervision.best_path(input)

@@ -320,6 +320,45 @@ class Supervision:
         d["kernel"] = {0: "resident", 1: "windowed"}.get(d["route"], "unsupported")
         return d
 
+    def best_path(self, nnet_output):
+        """The single most likely path of every sequence under ``nnet_output``: the frame-level pdf alignment
+        (``tc_supervision_best_path``), for regular and end-to-end handles, uniform and ragged.  Returns ``(pdfs, scores)``
+        on the input's device: ``pdfs`` int32 ``(B, Tmax)``, the 0-based pdf of every frame and ``-1`` in a ragged handle's
+        padding frames; ``scores`` float64 ``(B,)``, the path's log score (sum of ``y_t(pdf_t) - arc cost``, minus the final
+        cost; the supervision's ``weight`` does not enter).  A sequence without a path of exactly its number of frames gets
+        ``-inf`` and ``-1`` in all its frames.
+
+        ``nnet_output`` is what ``chain_loss`` takes: ``(B, C, T)`` or ``(T*B, C)``.  2-D float32 with unit column stride and
+        contiguous ``(B, C, T)`` in float32, bfloat16 or float16 are read where they lie; any other view or dtype goes through
+        ``.contiguous()`` (and ``.float()``) first -- alignment is not a hot path.  No autograd: the input is detached, the
+        outputs carry no graph.  Asynchronous on the current stream; the history in the handle's pool slot is scratch, so
+        a ``chain_loss`` on the handle is not affected."""
+        x = nnet_output.detach()
+        if not x.is_cuda:
+            raise ValueError("best_path: nnet_output must be a CUDA tensor (only the HIP implementation is available)")
+        S, T, P = self.n_batch, self.n_frame, self.n_pdf
+        want = (S, P, T) if x.dim() == 3 else (S * T, P)
+        if x.dim() not in (2, 3) or tuple(x.shape) != want:
+            raise ValueError("best_path: nnet output of shape %s does not match the supervision (%s expected)"
+                             % (tuple(x.shape), want))
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dtype not in dtypes or (x.dim() == 2 and x.dtype != torch.float32):
+            x = x.float()
+        if x.dim() == 3 and not x.is_contiguous():
+            x = x.contiguous()
+        if x.dim() == 2 and (x.stride(1) != 1 or x.stride(0) < P):
+            x = x.contiguous()
+        device = x.device
+        pdfs = torch.empty((S, T), dtype=torch.int32, device=device)
+        scores = torch.empty((S,), dtype=torch.float64, device=device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            check(lib.tc_supervision_best_path(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
+                                               x.stride(0) if x.dim() == 2 else 0, C.c_void_p(pdfs.data_ptr()),
+                                               C.c_void_p(scores.data_ptr()), device.index, stream),
+                  "tc_supervision_best_path")
+        return pdfs, scores
+
     def __del__(self, _free=lib.tc_supervision_free):
         ptr = getattr(self, "ptr", None)
         if ptr:
