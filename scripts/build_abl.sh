@@ -18,4 +18,4 @@ for f in $all; do
   fi
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../scratch_abl/lib_$name.so den_graph.o den_layout.o schedule_general.o schedule_owner.o supervision.o supervision_merge.o supervision_e2e.o egs_reader.o rand_reader.o self_test.o tuning_cache.o api.o $objs num_kernels.o num_windowed_kernels.o num_e2e_kernels.o layout_kernels.o layout_rows_kernels.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../scratch_abl/lib_$name.so den_graph.o den_layout.o schedule_general.o schedule_owner.o supervision.o supervision_merge.o supervision_e2e.o egs_reader.o rand_reader.o self_test.o tuning_cache.o api.o $objs num_kernels.o num_windowed_kernels.o num_e2e_kernels.o num_best_path_kernels.o layout_kernels.o layout_rows_kernels.o

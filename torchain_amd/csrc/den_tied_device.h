@@ -74,6 +74,33 @@ __device__ __forceinline__ void bst4_aux(rsrc_t r, uint32_t voff, f4 v) {
                                          r, (int)voff, 0, AUX);
 }
 
+// A global row straight into LDS (gfx950: buffer_load_dwordx4 ... offen lds): no destination registers, 1 KiB per wave
+// instruction, lane l's 16 bytes land at lds_wave + 16 * l -- `lds_wave`, the byte address of lane 0's slot, is wave-uniform
+// and goes through M0.  The compiler owns M0 (the row commits below set it in their own statement), so it is saved and put
+// back here.  Rules of use:
+//   * the statement is invisible to the compiler's wait counting: the reader waits with dma_wait<N>() below, N = the number
+//     of vector-memory operations the wave is known to have issued behind the DMA on every path;
+//   * nothing orders the landing against a ds_read of the same bytes but that wait (and, for other waves' reads, a
+//     barrier): an earlier read of the slot must have RETURNED before the DMA is issued (lgkmcnt);
+//   * lanes beyond the descriptor's bytes land zeros; the offset stays in the VGPR (see bst4 below), the instruction's
+//     immediate offset would move the LDS address as well;
+//   * s_nop 4: the wait states of a descriptor word or an M0 written just before the statement.
+__device__ __forceinline__ void dma4_to_lds(rsrc_t r, uint32_t voff, uint32_t lds_wave) {
+  uint32_t keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(r), "s"(lds_wave)
+               : "memory");
+}
+// waits until at most N of the wave's vector-memory operations are outstanding (they retire in order)
+template <int N>
+__device__ __forceinline__ void dma_wait() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit count");
+  asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
+}
+// every LDS operation of the wave has returned
+__device__ __forceinline__ void lds_wait_all() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
+
 __device__ __forceinline__ f4 mk4(float x) { return f4{x, x, x, x}; }
 __device__ __forceinline__ float hsum(f4 v) { return (v.x + v.y) + (v.z + v.w); }
 // exp(clamp(y, -30, 30)) ([K] later Kaldi: ApplyExpLimited; equal to the 22fbdd ApplyExp() for |y| < 30) with the

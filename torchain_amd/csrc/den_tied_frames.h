@@ -106,7 +106,7 @@ struct TiedSeq {
   const uint32_t aACC;   // row sums [row][lane]: K per wave, then the secondary rows
   const uint32_t vrow;   // this thread's slot of its wave's row 0
   const uint32_t aGM;    // gamma_t, u32 fixed point
-  const uint32_t aAL;    // alpha'_{t+1} of the owned states (backward, roomy layout)
+  const uint32_t aAL;    // alpha'_{t+1} of the owned states (backward, roomy layout; kHistByDma: alpha'_t, landed by DMA)
   const uint32_t aRed, aAsum;  // reduction scratch; alpha-sum of every frame
   const uint32_t tab_bytes, row_bytes;
   // leaky * pi of the owned states is re-read with the other per-state tables every frame (an L2 hit)
@@ -144,7 +144,7 @@ struct TiedSeq {
   Chunk6 bres[RESB > 0 ? RESB : 1];
   f4 v4[JV];         // alpha_t (un-dashed) of the owned states
   f4 bt[JV];         // GAMMA frames: B_t of the owned states
-  f4 areg[JV];
+  f4 areg[JV];       // backward: alpha'_t of the owned states (kHistByDma: alpha'_{t+1}, the frame above's)
   f4 ycur[PV], ynext[PV];
   f4 bown[JV];  // beta_{t+1} / B_{t+1} of the owned states (the LDS gather source holds Y instead)
 #ifdef TC_PHASE_STAMPS
@@ -517,7 +517,12 @@ struct TiedSeq {
           const float b = b_T + bsum;
           bown[j] = f4{h0 < H ? b : 0.f, h0 + 1 < H ? b : 0.f, h0 + 2 < H ? b : 0.f, h0 + 3 < H ? b : 0.f};
           if (PURE) bst4(bT, own16 + j * kPlane, bown[j]);  // B_T for the partner's gamma_{T-1}
-          if (!PURE && ALPHA_LDS) lds4_st(aAL + own16 + j * kPlane, bld4(hist_up, own16, j * kPlane));
+          if (!PURE && ALPHA_LDS) {
+            if (kHistByDma)
+              areg[j] = bld4(hist_up, own16, j * kPlane);  // (row T-1 follows by DMA, below)
+            else
+              lds4_st(aAL + own16 + j * kPlane, bld4(hist_up, own16, j * kPlane));
+          }
         }
       }
 #pragma unroll
@@ -540,7 +545,38 @@ struct TiedSeq {
         }
     }
     bstore_slot = RESB >= 4 ? wave >> 2 : RESB >= 2 ? wave >> 3 : 0;
+    if (!PURE && kHistByDma) hist_dma(T - 1);  // (last: nothing this prologue waits for queues behind it)
     stamps_reset();
+  }
+
+  // How a backward gamma frame of the fused kernel (roomy layout) gets alpha'_t of the owned states, which its per-state pass
+  // needs as `al` and the next frame's as `aup`.  false (the two-workgroup roles, the tight layout, -DTC_NO_HIST_DMA): frame t
+  // loads row t into areg under its walk, and its tail parks areg in aAL for frame t-1.  true: row t comes into aAL by DMA
+  // (dma4_to_lds), requested from frame t+1's per-state pass; frame t reads `al` from aAL and `aup` from areg, which keeps
+  // that `al` for frame t-1.  The same values reach the same arithmetic in the same order.  What it removes: the row's
+  // loads from the top of the walk, where every streamed chunk (an L2 hit) queued behind a row from HBM, and the tail's 32
+  // ds_write_b128 (areg is live across the walk in both forms).  profiles/hist_dma/README.md
+#ifdef TC_NO_HIST_DMA
+  static constexpr bool kHistByDma = false;
+#else
+  static constexpr bool kHistByDma = !MITM && ALPHA_LDS;
+#endif
+  // vector-memory operations every path issues between a frame's DMAs and the next per-state pass: the look-ahead chunk
+  // and the y row at the top of the frame (what else lies between -- the walk hook's stores, streamed chunks -- may be absent)
+#ifdef TC_ABL_NOY2
+  static constexpr int kDmaBehind = 3;
+#else
+  static constexpr int kDmaBehind = 3 + PV;
+#endif
+
+  // history row t of the owned states into aAL, each lane's float4 where that lane reads it; t < 0: no row, and the request
+  // goes through a descriptor of no bytes (unconditional, as the forward frame's store is).  The caller's own reads of
+  // aAL have returned.
+  __device__ __forceinline__ void hist_dma(int t) {
+    const rsrc_t row = make_rsrc(hist + (int64_t)(t > 0 ? t : 0) * hist_step, t >= 0 ? 4u * Hs : 0u);
+#pragma unroll
+    for (int j = 0; j < JV; ++j)
+      if (plane_on(j)) dma4_to_lds(row, own16 + j * kPlane, aAL + 1024u * (uint32_t)wave + j * kPlane);
   }
 
 #ifdef TC_NO_BWD_DEFER
@@ -574,10 +610,14 @@ struct TiedSeq {
 #else
       for (int v = 0; v < PV; ++v) ynext[v] = row_ld(yrow, own16 + v * kPlane, p.y_vec);
 #endif
-      if (!PURE) {
+      if (!PURE && !kHistByDma) {  // (kHistByDma: the row is in aAL, or on its way there)
         const rsrc_t hist_t = make_rsrc(hist + (int64_t)t * hist_step, 4u * Hs);
 #pragma unroll
+#ifdef TC_ABL_NOHISTLOAD
+        for (int j = 0; j < JV; ++j) areg[j] = mk4(1e-4f) * (float)(t + 1);  // (ablation: what the history row's load under the walk costs)
+#else
         for (int j = 0; j < JV; ++j) areg[j] = plane_on(j) ? bld4(hist_t, own16, j * kPlane) : mk4(0.f);
+#endif
       }
     }
     // beta'_t(h) * asum_t = sum over out-arcs of w * Y(dst): the same walk as forward, no atomics
@@ -646,6 +686,11 @@ struct TiedSeq {
       // alpha'_{t+1}: parked by this thread (roomy layout) or re-read from the history (tight layout)
       if (!PURE && !ALPHA_LDS) aup_n = bld4(make_rsrc(hist + (int64_t)(t + 1) * hist_step, 4u * Hs), own16, j * kPlane);
     };
+    // kHistByDma: row t has landed in aAL once the DMAs that frame t+1 issued have retired.  A wave's vector-memory
+    // operations retire in order and every path has issued kDmaBehind (3 + PV) behind them, so vmcnt(3 + PV) covers the
+    // DMAs; it is a counted wait because the youngest operations may be the walk hook's derivative and cross-entropy
+    // stores (2 PV of them), whose acknowledgements vmcnt(0) would wait for.  In front of this pass's table requests.
+    if (!PURE && kHistByDma) dma_wait<kDmaBehind>();
     if (kAhead) request(0);
 #pragma unroll
     for (int j = 0; j < JV; ++j) {
@@ -658,8 +703,10 @@ struct TiedSeq {
         const f4 aup_g = aup_n;
         if (kAhead && j + 1 < planes) request(j + 1);
         f4 a = own_rows(vrow, j);
-        const f4 al = areg[j];  // alpha'_t of the owned states
-        const f4 aup = (!PURE && ALPHA_LDS) ? lds4(aAL + own16 + j * kPlane) : aup_g;
+        // alpha'_t of the owned states, and alpha'_{t+1} (kHistByDma: the frame above's `al`)
+        const f4 al = (!PURE && kHistByDma) ? lds4(aAL + own16 + j * kPlane) : areg[j];
+        const f4 aup = (!PURE && kHistByDma) ? areg[j] : (!PURE && ALPHA_LDS) ? lds4(aAL + own16 + j * kPlane) : aup_g;
+        if (!PURE && kHistByDma) areg[j] = al;
         a.x = bwd_state<PURE>(pb_cur, fs.x, ws.x, bown[j].x, al.x, aup.x, cp.x, a.x, inv_as, asum_up);
         a.y = bwd_state<PURE>(pb_cur, fs.y, ws.y, bown[j].y, al.y, aup.y, cp.y, a.y, inv_as, asum_up);
         a.z = bwd_state<PURE>(pb_cur, fs.z, ws.z, bown[j].z, al.z, aup.z, cp.z, a.z, inv_as, asum_up);
@@ -671,6 +718,17 @@ struct TiedSeq {
         if (PURE) part_u += hsum(a);
         if (!PURE && t == 0) part_ab += hsum(al * b4[j]);
       }
+    }
+    if (!PURE && kHistByDma) {
+      // Row t-1 for the next frame, into the 16 bytes this lane has just read.  The last of the pass's vector-memory requests,
+      // so that no table load queues behind a row from HBM; the next load the wave needs is a reduction, the tail, a barrier
+      // and the resident chunks away.  The DMA is not ordered against a ds_read: the wave's reads have returned first (the
+      // reduction below would wait for its LDS operations a few instructions on in any case).  Measured at C3
+      // (profiles/hist_dma/README.md): from here -0.017 ms against the parent's frame; each plane's request right behind that
+      // plane's read, in front of the next plane's table loads, +0.165 ms; from the end of the tail, where the 16 waves leave a
+      // barrier together, +0.034 ms.
+      lds_wait_all();
+      hist_dma(t - 1);
     }
     float inv_n = 1.f;
     if (PURE) {
@@ -715,6 +773,7 @@ struct TiedSeq {
           p.seq_ab[s] = ab;
           p.seq_gsum[s] = gsum;
         }
+        if (kHistByDma) dma_wait<0>();  // (the workgroup's LDS is not given back under a request that writes it)
         return true;
       }
     }
@@ -740,7 +799,9 @@ struct TiedSeq {
           lds4_st_at(own16, kA0 + j * kPlane, yv);
         else
           lds4_st(kA0 + own16 + j * kPlane, yv);
-        if (!PURE && ALPHA_LDS) lds4_st(aAL + own16 + j * kPlane, areg[j]);
+#ifndef TC_ABL_NOPARK  /* (ablation: what parking alpha'_t for the next frame costs the tail) */
+        if (!PURE && ALPHA_LDS && !kHistByDma) lds4_st(aAL + own16 + j * kPlane, areg[j]);
+#endif
       }
 #pragma unroll
     for (int v = 0; v < PV; ++v) ycur[v] = ynext[v];
