@@ -527,6 +527,51 @@ int tc_chain_step_strided(tc_den_graph *graph, tc_supervision *supervision, cons
                           float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
                           void *stream);
 
+/* tc_chain_step_strided with the sequences' own objectives reported, and with a minibatch that survives a failed sequence.
+ * The reference (and Kaldi, whose egs are filtered offline) gives up the whole minibatch when its objective is not finite:
+ * objf = -10 * weight, every gradient reset (src/my_lib_chain.cpp:104-136 -> [K] ComputeChainObjfAndDeriv).  A ragged
+ * minibatch built from whole utterances meets such sequences -- an end-to-end FST with no path of exactly T_s arcs, a NaN
+ * or inf in one sequence's activations -- and its caller cannot tell which one it was.
+ *   seq_results_dev  : nullable; device double[num_sequences][6], 8-byte aligned, one row per sequence:
+ *                      {num_logprob, den_logprob, sum_y2, xent_sum, frames, status}.  The two log-probabilities are the
+ *                      unweighted ones (the sequence's objective is weight * (num_logprob - den_logprob)); xent_sum is the
+ *                      sequence's share of xent_objf_dev, scaled as that is, 0 without the xent branch; frames is its own
+ *                      T_s; status is a bit set, 0 for ok: 1 numerator non-finite (no path: -inf; forward and backward
+ *                      totals that disagree: NaN; a non-finite cross-entropy sum, which is made of the numerator's
+ *                      posteriors), 2 denominator non-finite (its log-probability or sum y^2: a NaN or inf among the
+ *                      sequence's activations), 4 an alpha-beta check value non-finite (only when grad != NULL).
+ *                      Written whatever isolate_failures says; every other output is then tc_chain_step_strided's, bit
+ *                      for bit.
+ *   isolate_failures : != 0: a sequence FAILED when its status is not 0 -- no tolerance is involved.  Then
+ *                      results_dev3 = {objf, l2_term, weight}, loss_dev1 and xent_objf_dev are formed from the surviving
+ *                      sequences alone, summed in the order of the unmasked call (a failed sequence's term is an exact
+ *                      +0.0): weight = supervision weight * (the survivors' frames), loss = -objf / weight, and Kaldi's
+ *                      alpha-beta check |sum - S| > 2 is held against the survivors' sums and their count.  Every
+ *                      gradient element of a failed sequence, in grad and in xent_grad, is +0 in every layout and dtype,
+ *                      as a ragged minibatch's padding is: no l2 term, no penalty, no deriv_weights product -- a failed
+ *                      sequence is a sequence of no frames.  The other sequences' elements are the bits of the call
+ *                      without the switch.
+ *                      Nothing failed: every output is that call's, bit for bit.  Every sequence failed, or the
+ *                      survivors miss the alpha-beta check: the whole minibatch takes the failure route exactly as without
+ *                      the switch (status still tells the sequences apart).
+ *                      Whether a non-finite sequence can make its NEIGHBOURS non-finite (they are then reported as
+ *                      failed too, by the same rule) depends on the denominator kernel: DESIGN.md 4.13 lists the families.
+ *   how              : a sibling of the scalar epilogue forms the statuses and both sets of sums and leaves each
+ *                      sequence's surviving frames beside the failure flag in the workspace; with isolate_failures the
+ *                      ragged minibatches' padding pass runs on those, last of all (one more launch per gradient for a
+ *                      uniform supervision, none for a ragged one).  The denominator and numerator kernels are untouched.
+ *   grad == NULL     : the evaluation step with the same scalars; nothing else is written.
+ * isolate_failures == 0 and seq_results_dev == NULL: tc_chain_step_strided, launch for launch.  Same workspace.  No host
+ * synchronisation, nothing allocated; safe under stream capture.  The split entries (tc_chain_objf_and_deriv,
+ * tc_chain_objf_and_grad, tc_den_forward_backward*) do not take the switch. */
+int tc_chain_step_per_sequence(tc_den_graph *graph, tc_supervision *supervision, const void *input, const void *xent_input,
+                               int layout, int64_t row_stride, int64_t batch_stride, int64_t frame_stride,
+                               float l2_regularize, float leaky_hmm_coefficient, float xent_regularize, int kaldi_way,
+                               void *grad, void *xent_grad, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
+                               const float *deriv_weights, float out_of_range_regularize, int dtype, void *workspace,
+                               int64_t workspace_bytes, int device, void *stream, int isolate_failures,
+                               double *seq_results_dev);
+
 /* The benchmarked unit: [K] DenominatorComputation::Forward() + Backward(deriv_weight, deriv)
  * (direct use in the reference: src/chain-supervision-test.hpp:403-414).
  *   logprob_dev   : device double[1], sum over sequences of the denominator log-prob

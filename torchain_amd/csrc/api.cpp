@@ -34,6 +34,7 @@ struct Workspace {
   double *den_lp, *num_lp, *y2, *xent_lp;
   float *ab, *gs;
   int32_t *fail;
+  int32_t *alive_frames;  // per sequence, its own frames or 0 for a failed one: the isolating step (tc_chain_step_per_sequence)
   double *scalar;
   size_t total;
 };
@@ -83,6 +84,7 @@ Workspace carve(char *base, int Hs, int S, int T, int big_P = 0, int big_H = 0, 
   w.ab = (float *)take((size_t)S * 4);
   w.gs = (float *)take((size_t)S * 4);
   w.fail = (int32_t *)take(256);
+  w.alive_frames = (int32_t *)take((size_t)S * 4);
   w.scalar = (double *)take(4096);  // also the stamp area of diagnostic builds
   // streamed path: exp(y) of every frame, transposed once and used by both passes, when that is at most 1 GB
   // (else one frame at a time, recomputed by the backward pass: 2-7 % slower, measured; the cap keeps the workspace
@@ -524,6 +526,10 @@ struct ObjfStep {  // what only the one-call step passes: all unset for the two 
   bool xent_sums_ready = false;  // (the numerator-only pass of kaldi_way == 0 has left the sequences' xent sums)
   // the step moves deriv / xent on (emit_gradients) and zeroes a ragged minibatch's padding in the caller's tensors itself
   bool outputs_move_on = false;
+  // tc_chain_step_per_sequence: the sequences' own values ([S][6] doubles, nullable) and whether a failed sequence is masked
+  // out of the sums; either one selects the per-sequence finalize (alive_frames is then written to the workspace)
+  double *seq_results = nullptr;
+  bool isolate = false;
 };
 
 static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int64_t rows, int32_t cols,
@@ -630,9 +636,15 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   }
   rc = supervision_mark_use(sup, device, stream);
   if (rc != TC_OK) return rc;
-  rc = launch_finalize(w.den_lp, w.num_lp, w.y2, w.ab, w.gs, sup->S, sup->T, wgt, l2_regularize, deriv != nullptr,
-                       results_dev3, w.fail, stream, (np.seq_xent || o.xent_sums_ready) && o.xent_objf_dev ? w.xent_lp : nullptr,
-                       o.xent_objf_dev, o.loss_dev1, ragged ? sup->total_frames : 0);
+  const double *xent_sums = (np.seq_xent || o.xent_sums_ready) && o.xent_objf_dev ? w.xent_lp : nullptr;
+  if (o.isolate || o.seq_results)
+    rc = launch_finalize_per_sequence(w.den_lp, w.num_lp, w.y2, w.ab, w.gs, sup->S, sup->T, wgt, l2_regularize, deriv != nullptr,
+                                      results_dev3, w.fail, stream, xent_sums, o.xent_objf_dev, o.loss_dev1,
+                                      ragged ? sup->total_frames : 0, ragged ? np.seq_frames : nullptr, o.isolate ? 1 : 0,
+                                      o.seq_results, w.alive_frames);
+  else
+    rc = launch_finalize(w.den_lp, w.num_lp, w.y2, w.ab, w.gs, sup->S, sup->T, wgt, l2_regularize, deriv != nullptr,
+                         results_dev3, w.fail, stream, xent_sums, o.xent_objf_dev, o.loss_dev1, ragged ? sup->total_frames : 0);
   if (rc != TC_OK) return rc;
   // (a (B, C, T) xent tensor is rows * cols contiguous floats: cleared as such)
   rc = launch_zero_on_fail(w.fail, deriv, deriv_stride, xent, o.xent_bct ? (int64_t)cols : xent_stride, y, y_stride,
@@ -801,8 +813,9 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
                              float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
                              float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
                              float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
-                             void *stream_v) {
+                             void *stream_v, int isolate_failures = 0, double *seq_results_dev = nullptr) {
   if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)seq_results_dev & 7) != 0) return TC_ERR_INVALID_ARGUMENT;
   const bool cl = layout == TC_LAYOUT_CHANNEL_LAST;
   const int three_d = layout != TC_LAYOUT_ROWS;
   if (((uintptr_t)deriv_weights & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
@@ -898,23 +911,35 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   o.bct_dtype = dtype;
   o.xent_row_w = row_w;
   o.outputs_move_on = true;
+  o.isolate = isolate_failures != 0;
+  o.seq_results = seq_results_dev;
   rc = chain_objf(g, sup, io.y, rows, P, io.y_stride, results_dev3, io.gr, P, io.xg, P, l2_regularize, leaky, dscale, xscale,
                   w.chain, (int64_t)w.chain_bytes, device, stream_v, o);
   if (rc != TC_OK || eval_only) return rc;
   rc = emit_gradients(io, layout, dtype, input, row_stride, sb, st, grad, xent_grad, w.y2d, S, T, P, pen_c2, row_w, device,
                       stream_v);
-  if (rc != TC_OK || sup->frames.empty()) return rc;
+  if (rc != TC_OK || (sup->frames.empty() && !o.isolate)) return rc;
   // A ragged minibatch: the objective wrote no padding row, the last passes moved whatever lay there; +0 into the padding
   // of the caller's gradients, each where its layout puts element (sequence, frame, channel).  (The (B, C, T) xent gradient
   // was cleared on the way in and has entries only at the numerator's posteriors.)
+  const bool bct = layout == TC_LAYOUT_BCT;
+  const int eb = half ? 2 : 4;
+  const int64_t zb = bct || cl ? (int64_t)T * P : (int64_t)P, zt = bct ? 1 : (cl ? (int64_t)P : (int64_t)S * P), zc = bct ? T : 1;
+  if (o.isolate) {
+    // The isolating step: a failed sequence is a sequence of no frames.  The finalize left every sequence's surviving frames
+    // in the workspace (its own length, 0 when it failed; the handle's lengths when the whole minibatch took the failure
+    // route), so the one launch covers padding and failed sequences -- whose rows hold whatever the kernels made of a
+    // non-finite recursion, the (B, C, T) xent gradient's included.
+    const int32_t *alive = carve((char *)w.chain, hist_states(g), S, T, big_p(g), big_h(g), big_g(g), big_hb(g), split_room(g, S), pair_room(g), planes_room(g)).alive_frames;
+    rc = launch_zero_failed(grad, eb, zb, zt, zc, S, T, P, alive, stream);
+    if (rc == TC_OK && xent_grad && use_xent) rc = launch_zero_failed(xent_grad, eb, zb, zt, zc, S, T, P, alive, stream);
+    return rc;
+  }
   const int32_t *frames_dev = nullptr;
   {
     std::lock_guard<std::mutex> lock(sup->mu);
     frames_dev = sup->frames_dev[device];
   }
-  const bool bct = layout == TC_LAYOUT_BCT;
-  const int eb = half ? 2 : 4;
-  const int64_t zb = bct || cl ? (int64_t)T * P : (int64_t)P, zt = bct ? 1 : (cl ? (int64_t)P : (int64_t)S * P), zc = bct ? T : 1;
   rc = launch_zero_padding(grad, eb, zb, zt, zc, S, T, P, frames_dev, stream);
   if (rc == TC_OK && xent_grad && use_xent && !bct) rc = launch_zero_padding(xent_grad, eb, zb, zt, zc, S, T, P, frames_dev, stream);
   return rc;
@@ -965,16 +990,17 @@ int64_t tc_chain_step_strided_workspace_bytes(const tc_den_graph *g, int32_t S, 
   return tc_chain_step_typed_workspace_bytes(g, S, T, layout != TC_LAYOUT_ROWS, with_xent, dtype);
 }
 
-int tc_chain_step_strided(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
-                          int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize, float leaky,
-                          float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
-                          float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
-                          float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
-                          void *stream_v) {
+int tc_chain_step_per_sequence(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
+                               int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize, float leaky,
+                               float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
+                               float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                               float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                               void *stream_v, int isolate_failures, double *seq_results_dev) {
   if (layout == TC_LAYOUT_ROWS || layout == TC_LAYOUT_BCT)
     return chain_step_layout(g, sup, input_v, xent_input_v, layout, row_stride, 0, 0, l2_regularize, leaky, xent_regularize,
                              kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev, deriv_weights,
-                             out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v);
+                             out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v, isolate_failures,
+                             seq_results_dev);
   if (layout != TC_LAYOUT_CHANNEL_LAST || !sup) return TC_ERR_INVALID_ARGUMENT;
   if (!channel_last_strides_ok(sup->S, sup->T, sup->P, batch_stride, frame_stride)) return TC_ERR_INVALID_ARGUMENT;
   // (element offsets are multiples of the element size: a base that is not breaks every access)
@@ -983,7 +1009,20 @@ int tc_chain_step_strided(tc_den_graph *g, tc_supervision *sup, const void *inpu
     return TC_ERR_INVALID_ARGUMENT;
   return chain_step_layout(g, sup, input_v, xent_input_v, layout, 0, batch_stride, frame_stride, l2_regularize, leaky,
                            xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev,
-                           deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v);
+                           deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v,
+                           isolate_failures, seq_results_dev);
+}
+
+int tc_chain_step_strided(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
+                          int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize, float leaky,
+                          float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
+                          float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                          float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                          void *stream_v) {
+  return tc_chain_step_per_sequence(g, sup, input_v, xent_input_v, layout, row_stride, batch_stride, frame_stride, l2_regularize,
+                                    leaky, xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1,
+                                    xent_objf_dev, deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes,
+                                    device, stream_v, 0, nullptr);
 }
 
 int tc_rows_gather(const void *in, int dtype, int32_t B, int32_t Cn, int32_t T, int64_t batch_stride, int64_t frame_stride,

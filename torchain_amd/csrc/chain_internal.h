@@ -557,6 +557,22 @@ int launch_finalize(const double *den_lp, const double *num_lp, const double *y2
                     int S, int T, float sup_weight, float l2, int have_deriv, float *results, int32_t *fail_flag,
                     hipStream_t stream, const double *xent_lp = nullptr, double *xent_total = nullptr,
                     float *loss_out = nullptr, int64_t total_frames = 0);
+// The finalize of tc_chain_step_per_sequence (a sibling kernel: finalize_kernel keeps its instruction stream).  Forms each
+// sequence's status (1: numerator, 2: denominator, 4: alpha-beta check non-finite), writes seq_results ([S][6] doubles:
+// num_lp, den_lp, y2, xent sum, frames, status; nullable) and alive_frames ([S]: the sequence's own frames, or 0 when it is
+// masked out).  isolate: the sums run over the sequences of status 0, in finalize_kernel's order, a masked term being an
+// exact +0.0, and the alpha-beta sums are held against their count.  When nothing failed, everything failed or the
+// survivors miss that check, the unmasked sums give finalize_kernel's outputs bit for bit and alive_frames holds every
+// sequence's own length.  seq_frames: a ragged minibatch's lengths (null: T each).
+int launch_finalize_per_sequence(const double *den_lp, const double *num_lp, const double *y2, const float *ab, const float *gs,
+                                 int S, int T, float sup_weight, float l2, int have_deriv, float *results, int32_t *fail_flag,
+                                 hipStream_t stream, const double *xent_lp, double *xent_total, float *loss_out,
+                                 int64_t total_frames, const int32_t *seq_frames, int isolate, double *seq_results,
+                                 int32_t *alive_frames);
+// ... its zeroing: +0 into frames >= alive_frames[b] of sequence b, as launch_zero_padding but from frame 0 where
+// alive_frames[b] is 0 (a failed sequence is a sequence of no frames)
+int launch_zero_failed(void *out, int elem_bytes, int64_t sb, int64_t st, int64_t sc, int B, int T, int cols,
+                       const int32_t *alive_frames, hipStream_t stream);
 // Ragged minibatches: +0 into the elements of frames >= seq_frames[b] of an output tensor whose element (b, t, c) lies at
 // b*sb + t*st + c*sc (element strides; elem_bytes 4 or 2) -- every layout and dtype of the entries; costs what the padding
 // costs.  (layout_rows_kernels.hip)

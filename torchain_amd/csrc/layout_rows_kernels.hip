@@ -203,7 +203,45 @@ __global__ __launch_bounds__(kRowsThreads) void zero_padding_kernel(Bits *out, i
   }
 }
 
+// The isolating step: zero_padding_kernel on the frames that survive, alive_frames[b] in 0 .. T -- 0 for a failed sequence,
+// all of whose rows go (ragged_frames holds a length to 1 .. T; a sibling, so that zero_padding_kernel stays as it is).
+template <typename Bits>
+__global__ __launch_bounds__(kRowsThreads) void zero_failed_kernel(Bits *out, int64_t sb, int64_t st, int64_t sc, int B, int T,
+                                                                   int cols, const int32_t *__restrict__ alive_frames) {
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int f0 = __builtin_amdgcn_readfirstlane(alive_frames[b]);
+    const int first = f0 < 0 ? 0 : (f0 > T ? T : f0), pad = T - first;
+    if (pad <= 0) continue;
+    const int64_t n = (int64_t)pad * cols;
+    Bits *const base = out + (int64_t)b * sb;
+    for (int64_t i = (int64_t)blockIdx.x * kRowsThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowsThreads) {
+      int64_t f, c;
+      if (st < sc) {
+        c = i / pad;
+        f = i - c * pad;
+      } else {
+        f = i / cols;
+        c = i - f * cols;
+      }
+      base[(first + f) * st + c * sc] = Bits(0);
+    }
+  }
+}
+
 }  // namespace
+
+int launch_zero_failed(void *out, int elem_bytes, int64_t sb, int64_t st, int64_t sc, int B, int T, int cols,
+                       const int32_t *alive_frames, hipStream_t stream) {
+  if (!out || !alive_frames || B <= 0 || T <= 0 || cols <= 0 || (elem_bytes != 4 && elem_bytes != 2)) return TC_ERR_INVALID_ARGUMENT;
+  const int64_t per_seq = ((int64_t)T * cols + kRowsThreads - 1) / kRowsThreads;
+  const dim3 blocks((unsigned)std::min<int64_t>(per_seq, 64), (unsigned)std::min(B, 65535)), threads(kRowsThreads);
+  if (elem_bytes == 4)
+    hipLaunchKernelGGL(zero_failed_kernel<uint32_t>, blocks, threads, 0, stream, static_cast<uint32_t *>(out), sb, st, sc, B, T, cols, alive_frames);
+  else
+    hipLaunchKernelGGL(zero_failed_kernel<uint16_t>, blocks, threads, 0, stream, static_cast<uint16_t *>(out), sb, st, sc, B, T, cols, alive_frames);
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
 
 int launch_zero_padding(void *out, int elem_bytes, int64_t sb, int64_t st, int64_t sc, int B, int T, int cols,
                         const int32_t *seq_frames, hipStream_t stream) {

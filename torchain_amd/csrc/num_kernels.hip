@@ -289,6 +289,167 @@ int launch_finalize(const double *den_lp, const double *num_lp, const double *y2
   return TC_OK;
 }
 
+// ---- the scalar epilogue of tc_chain_step_per_sequence ------------------------------------------------------------
+// finalize_kernel's sums twice, in its order (thread i takes sequences i, i + 256, ...; thread 0 adds the 256 partials):
+// over every sequence, and over the sequences whose own scalars are all finite, a masked term being an exact +0.0.
+// epilogue_scalars is finalize_kernel's arithmetic on one set of sums; `count` and `frames` are what the alpha-beta sums
+// and the weight are held against (S and the minibatch's frames; the survivors' and theirs).
+namespace {
+struct EpilogueOut {
+  float objf, l2_term, weight;
+  int fail;
+};
+
+__device__ __forceinline__ EpilogueOut epilogue_scalars(double D, double N, double Q, double A, double G, double count,
+                                                        float weight, float sup_weight, float l2, int have_deriv) {
+  EpilogueOut e;
+  const float num_logprob_weighted = (float)(N * (double)sup_weight);
+  const float den_logprob = (float)D;
+  float objf = num_logprob_weighted - sup_weight * den_logprob;
+  bool ok = true;
+  if (have_deriv) {
+    if (fabs(A - count) > 2.0 || !(A - A == 0.0)) ok = false;
+    if (fabs(G - count) > 2.0 || !(G - G == 0.0)) ok = false;
+  }
+  e.fail = 0;
+  if (!(objf - objf == 0.0f) || !ok) {
+    objf = -10.0f * weight;
+    e.fail = 1;
+  }
+  e.l2_term = 0.f;
+  if (l2 != 0.0f) e.l2_term = (float)(-0.5 * (double)(sup_weight * l2) * (double)(float)Q);
+  e.objf = objf;
+  e.weight = weight;
+  return e;
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void finalize_per_sequence_kernel(
+    const double *den_lp, const double *num_lp, const double *y2, const float *ab, const float *gs, int S, int T,
+    float sup_weight, float l2, int have_deriv, float *results, int32_t *fail_flag, const double *xent_lp, double *xent_total,
+    float *loss_out, int64_t total_frames, const int32_t *seq_frames, int isolate, double *seq_results, int32_t *alive_frames) {
+  __shared__ double sh[12][256];  // all: d n q a g x; alive: the same six
+  __shared__ int sh_cnt[256];
+  __shared__ long long sh_frames[256];
+  __shared__ int sh_masked;
+  const int tid = threadIdx.x;
+  double d = 0, n = 0, q = 0, a = 0, g = 0, x = 0, md = 0, mn = 0, mq = 0, ma = 0, mg = 0, mx = 0;
+  int cnt = 0;
+  long long frames = 0;
+  for (int s = tid; s < S; s += 256) {
+    const double ds = den_lp[s], ns = num_lp ? num_lp[s] : 0.0, qs = y2[s];
+    const double as = have_deriv ? (double)ab[s] : 0.0, gsv = have_deriv ? (double)gs[s] : 0.0;
+    const double xs = xent_lp ? xent_lp[s] : 0.0;
+    int own = T;
+    if (seq_frames) {
+      own = seq_frames[s];
+      own = own < 1 ? 1 : (own > T ? T : own);
+    }
+    // (the sequence's cross-entropy sum is formed from the numerator's posteriors: non-finite with them)
+    int status = 0;
+    if (!(ns - ns == 0.0) || !(xs - xs == 0.0)) status |= 1;
+    if (!(ds - ds == 0.0) || !(qs - qs == 0.0)) status |= 2;
+    if (!(as - as == 0.0) || !(gsv - gsv == 0.0)) status |= 4;
+    const bool alive = status == 0;
+    d += ds;
+    n += ns;
+    q += qs;
+    a += as;
+    g += gsv;
+    x += xs;
+    md += alive ? ds : 0.0;
+    mn += alive ? ns : 0.0;
+    mq += alive ? qs : 0.0;
+    ma += alive ? as : 0.0;
+    mg += alive ? gsv : 0.0;
+    mx += alive ? xs : 0.0;
+    cnt += alive ? 1 : 0;
+    frames += alive ? own : 0;
+    if (seq_results) {
+      double *r = seq_results + (int64_t)s * 6;
+      r[0] = ns;
+      r[1] = ds;
+      r[2] = qs;
+      r[3] = xs;
+      r[4] = (double)own;
+      r[5] = (double)status;
+    }
+    alive_frames[s] = alive ? own : 0;
+  }
+  sh[0][tid] = d;
+  sh[1][tid] = n;
+  sh[2][tid] = q;
+  sh[3][tid] = a;
+  sh[4][tid] = g;
+  sh[5][tid] = x;
+  sh[6][tid] = md;
+  sh[7][tid] = mn;
+  sh[8][tid] = mq;
+  sh[9][tid] = ma;
+  sh[10][tid] = mg;
+  sh[11][tid] = mx;
+  sh_cnt[tid] = cnt;
+  sh_frames[tid] = frames;
+  __syncthreads();
+  if (tid == 0) {
+    double t[12];
+    for (int k = 0; k < 12; ++k) t[k] = 0;
+    int alive_n = 0;
+    long long alive_f = 0;
+    for (int i = 0; i < 256; ++i) {
+      for (int k = 0; k < 12; ++k) t[k] += sh[k][i];
+      alive_n += sh_cnt[i];
+      alive_f += sh_frames[i];
+    }
+    // finalize_kernel's weight and outputs, from the sums over every sequence
+    const float weight_all = total_frames > 0 ? sup_weight * (float)total_frames : sup_weight * (float)S * (float)T;
+    EpilogueOut e = epilogue_scalars(t[0], t[1], t[2], t[3], t[4], (double)S, weight_all, sup_weight, l2, have_deriv);
+    double X = t[5];
+    int masked = 0;
+    if (isolate && alive_n > 0 && alive_n < S) {
+      // the survivors: their sums, their count, their frames (the weight in the form of the minibatch's own)
+      const float weight_m = total_frames > 0 ? sup_weight * (float)alive_f : sup_weight * (float)alive_n * (float)T;
+      const EpilogueOut m = epilogue_scalars(t[6], t[7], t[8], t[9], t[10], (double)alive_n, weight_m, sup_weight, l2, have_deriv);
+      if (!m.fail) {  // (else the whole minibatch takes the failure route, as without the switch)
+        e = m;
+        X = t[11];
+        masked = 1;
+      }
+    }
+    sh_masked = masked;
+    results[0] = e.objf;
+    results[1] = e.l2_term;
+    results[2] = e.weight;
+    *fail_flag = e.fail;
+    if (xent_total) *xent_total = e.fail ? 0.0 : X;
+    if (loss_out) loss_out[0] = -e.objf / e.weight;
+  }
+  __syncthreads();
+  if (!sh_masked) {  // nothing is masked out: every sequence keeps its own frames
+    for (int s = tid; s < S; s += 256) {
+      int own = T;
+      if (seq_frames) {
+        own = seq_frames[s];
+        own = own < 1 ? 1 : (own > T ? T : own);
+      }
+      alive_frames[s] = own;
+    }
+  }
+}
+
+int launch_finalize_per_sequence(const double *den_lp, const double *num_lp, const double *y2, const float *ab, const float *gs,
+                                 int S, int T, float sup_weight, float l2, int have_deriv, float *results, int32_t *fail_flag,
+                                 hipStream_t stream, const double *xent_lp, double *xent_total, float *loss_out,
+                                 int64_t total_frames, const int32_t *seq_frames, int isolate, double *seq_results,
+                                 int32_t *alive_frames) {
+  if (!alive_frames) return TC_ERR_INVALID_ARGUMENT;
+  hipLaunchKernelGGL(finalize_per_sequence_kernel, dim3(1), dim3(256), 0, stream, den_lp, num_lp, y2, ab, gs, S, T, sup_weight,
+                     l2, have_deriv, results, fail_flag, xent_lp, xent_total, loss_out, total_frames, seq_frames, isolate,
+                     seq_results, alive_frames);
+  TC_HIP_CHECK(hipGetLastError());
+  return TC_OK;
+}
+
 // Resets the derivative outputs when the finalize step flagged a numerical failure (rare path; exits
 // after one uniform load otherwise).  [K] zeroes both derivatives and only then adds the l2 term, so
 // deriv becomes -l2_scale*y and xent_deriv 0.

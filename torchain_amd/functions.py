@@ -39,6 +39,13 @@ Same names, argument meaning, defaults and quirks as the reference:
   scattered by the library, one pass each.  Values: bit for bit those of the call on ``input.contiguous()`` (float16: up to
   the sign of an exactly zero gradient element, where the view gives the float32 gradient's ``.to(float16)``).  ``xent_input``
   must be a view with the same strides (or absent); any other combination is made contiguous first (``plan_step_inputs``).
+* ``per_sequence=True`` (keyword-only, through ``**options``): ``ChainResults.per_sequence`` holds every sequence's own
+  ``num_logprob``, ``den_logprob``, ``objf``, ``frames``, ``xent_sum``, ``sum_y2`` and ``status`` (0 ok; bit 1 numerator, 2
+  denominator, 4 alpha-beta check non-finite), read lazily like ``data``; ``ChainResults.failed`` the indices whose status is
+  not 0.  Nothing else changes.  ``on_failure="sequence"`` (default ``"minibatch"``, the reference's behaviour) implies it and
+  isolates a failed sequence: the objective, weight, l2 term, loss and cross-entropy objective are the survivors' and the failed
+  sequence's gradient rows are ``+0`` like a ragged minibatch's padding; with nothing failed every output is bit for bit the
+  default call's (``tc_chain_step_per_sequence``).
 """
 import ctypes as C
 import inspect
@@ -74,6 +81,12 @@ class ChainResults:
         self._xent_scale = 1.0
         self._xent_host = None
         self._defer_host_copy = False  # set by chain_loss_data_parallel: the one D2H follows the all-reduce
+        # ``chain_loss(..., per_sequence=True)``: the sequences' own values, float64 (S, 6) on the device as the library
+        # wrote them (tc_chain_step_per_sequence), read when ``per_sequence`` is first looked at; local to the rank
+        self._seq_dev = None
+        self._seq_ready = None
+        self._seq_weight = 1.0
+        self._seq_host = None
 
     @property
     def data(self):
@@ -92,6 +105,23 @@ class ChainResults:
             self._stale = True
         if self._xent_dev is not None:
             self._xent_host = None
+        self._seq_host = None
+
+    @property
+    def per_sequence(self):
+        """The sequences' own values (``PerSequence``), or None unless ``chain_loss`` was asked for them.  Lazy: one D2H of
+        ``S * 48`` bytes behind the step when first read; ``invalidate()`` makes the next read copy again."""
+        if self._seq_host is None and self._seq_dev is not None:
+            if self._seq_ready is not None:
+                torch.cuda.current_stream(self._seq_dev.device).wait_event(self._seq_ready)
+            self._seq_host = PerSequence(self._seq_dev.cpu(), self._seq_weight)
+        return self._seq_host
+
+    @property
+    def failed(self):
+        """Indices of the sequences whose status is not 0 (an int64 tensor), or None without ``per_sequence``."""
+        seq = self.per_sequence
+        return None if seq is None else torch.nonzero(seq.status, as_tuple=False).flatten()
 
     @data.setter
     def data(self, value):
@@ -127,6 +157,28 @@ class ChainResults:
     def xent_loss(self):
         """-xent_objf / weight, the per-frame cross-entropy Kaldi logs as 'output-xent'; None without a xent branch."""
         return None if self.xent_objf is None else -self.xent_objf / float(self.data[2])
+
+
+class PerSequence:
+    """One minibatch's sequences, each for itself: float64 CPU tensors of ``S`` entries ``num_logprob`` and ``den_logprob``
+    (unweighted), ``objf`` = weight * (num - den), ``frames`` (the sequence's own ``T_s``), ``xent_sum`` (its share of
+    ``xent_objf``, as the library scales it: times ``-xent_regularize``; 0 without a xent branch) and ``sum_y2`` (the l2
+    term's sum), and the int64 tensor ``status``: 0 ok, bit 1 numerator, 2 denominator, 4 alpha-beta check non-finite."""
+
+    STATUS_NUMERATOR, STATUS_DENOMINATOR, STATUS_ALPHA_BETA = 1, 2, 4
+
+    def __init__(self, rows, weight):
+        rows = rows.double().reshape(-1, 6)
+        self.weight = float(weight)
+        self.num_logprob, self.den_logprob, self.sum_y2, self.xent_sum, self.frames = (rows[:, i].clone() for i in range(5))
+        self.status = rows[:, 5].to(torch.int64)
+        self.objf = self.weight * (self.num_logprob - self.den_logprob)
+
+    def __len__(self):
+        return int(self.status.numel())
+
+    def __repr__(self):
+        return "PerSequence(sequences=%d, failed=%s)" % (len(self), torch.nonzero(self.status).flatten().tolist())
 
 
 _workspaces = {}  # (device, stream) -> workspace, most recently used last
@@ -271,6 +323,23 @@ def _options(options, who="chain_loss"):
     return _out_of_range(c)
 
 
+ON_FAILURE = ("minibatch", "sequence")
+
+
+def _failure_options(options):
+    """``per_sequence`` and ``on_failure`` taken out of ``**options`` and checked: ``(report, isolate)``.  ``on_failure`` is
+    ``"minibatch"`` (the reference's route: one failed sequence fails them all) or ``"sequence"`` (isolation, which implies the
+    report); anything else is a ``ValueError``, before any library call."""
+    per_sequence = options.pop("per_sequence", False)
+    on_failure = options.pop("on_failure", "minibatch")
+    if not isinstance(on_failure, str) or on_failure not in ON_FAILURE:
+        raise ValueError("on_failure must be 'minibatch' or 'sequence', got %r" % (on_failure,))
+    if not isinstance(per_sequence, (bool, int)):
+        raise ValueError("per_sequence must be a bool, got %r" % (per_sequence,))
+    isolate = on_failure == "sequence"
+    return bool(per_sequence) or isolate, isolate
+
+
 def _penalized(g, y, c):
     """The library's penalised gradient with torch ops in the library's order (``tc_chain_step_penalized``): ``g + t`` where
     ``p != 0`` and ``g`` itself elsewhere, ``t = fl32(2c) * p``, ``p`` the part of ``y`` beyond ``+-OUTPUT_LIMIT`` (0 for NaN and
@@ -323,10 +392,11 @@ class _ChainStep(Function):
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
                 l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
-                out_of_range_regularize=0.0):
+                out_of_range_regularize=0.0, per_sequence=False, isolate=False):
         out, grad, xgrad = _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
                                      leaky_hmm_coefficient, xent_regularize, kaldi_way, want_grad=True,
-                                     deriv_weights=deriv_weights, out_of_range_regularize=out_of_range_regularize)
+                                     deriv_weights=deriv_weights, out_of_range_regularize=out_of_range_regularize,
+                                     per_sequence=per_sequence, isolate=isolate)
         ctx.grads = (grad, xgrad)
         if results._defer_host_copy:
             return input.new_zeros(1)
@@ -334,12 +404,15 @@ class _ChainStep(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return (ctx.grads[0], ctx.grads[1], None, None, None, None, None, None, None, None, None)
+        return (ctx.grads[0], ctx.grads[1]) + (None,) * 11
 
 
 def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-              xent_regularize, kaldi_way, want_grad, deriv_weights=None, out_of_range_regularize=0.0):
-    """One ``tc_chain_step_strided``, in the layout ``classify_layout`` finds (a time-major view as the 2-D rows it is;
+              xent_regularize, kaldi_way, want_grad, deriv_weights=None, out_of_range_regularize=0.0, per_sequence=False,
+              isolate=False):
+    """``per_sequence`` / ``isolate`` (``_failure_options``): the same step through ``tc_chain_step_per_sequence``, which also
+    fills the sequences' own values, allocated next to ``out``.  Otherwise:
+    One ``tc_chain_step_strided``, in the layout ``classify_layout`` finds (a time-major view as the 2-D rows it is;
     gradients of channel-last views come back as views of dense tensors).  ``want_grad=False`` is the evaluation step
     (``grad == NULL``): forward recursions only, no gradient tensors -- [K] ``ComputeChainObjfAndDeriv`` with ``nnet_output_deriv == NULL``; ``deriv_weights``
     (checked by ``_deriv_weights``) are then not passed on, and ``out_of_range_regularize`` (checked by ``_out_of_range``)
@@ -399,8 +472,14 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         tail = (_ptr(ws), ws.numel(), device.index, C.c_void_p(cur.cuda_stream))
         # (float32, NULL weights and no penalty: tc_chain_step itself; bfloat16 / float16 are widened on the way in and
         # their gradients rounded once on the way out)
-        check(lib.tc_chain_step_strided(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail),
-              "tc_chain_step_strided")
+        seq = None
+        if per_sequence or isolate:
+            seq = torch.empty((S, 6), dtype=torch.float64, device=device)
+            check(lib.tc_chain_step_per_sequence(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail, int(bool(isolate)),
+                                                 _ptr(seq)), "tc_chain_step_per_sequence")
+        else:
+            check(lib.tc_chain_step_strided(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail),
+                  "tc_chain_step_strided")
         results._dev = out[:3]
         results._stale = True
         results._ready = None
@@ -409,6 +488,10 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         else:
             results._ready = torch.cuda.Event()
             results._ready.record(cur)
+        results._seq_dev, results._seq_ready, results._seq_host = seq, results._ready, None
+        if seq is not None:
+            results._seq_weight = (supervision.weight if isinstance(supervision, io.Supervision)
+                                   else float(lib.tc_supervision_weight(sup_ptr)))
         if use_xent:
             results._xent_dev = out[4:6].view(torch.float64)
             results._xent_ready = results._ready
@@ -619,9 +702,11 @@ def _step_inputs(input, xent_input, want_grad):
 def chain_loss(input, den_graph, supervision,
                l2_regularize=0.0, leaky_hmm_coefficient=1e-5,
                xent_regularize=0.0, xent_input=None, kaldi_way=False, *, deriv_weights=None, **options):
-    """``options``: ``out_of_range_regularize=0.0``, keyword-only (the module docstring; ``_options``)."""
+    """``options``, keyword-only (the module docstring): ``out_of_range_regularize=0.0`` (``_options``), ``per_sequence=False``
+    and ``on_failure="minibatch"`` (``_failure_options``)."""
+    per_sequence, isolate = _failure_options(options)
     return _chain_loss_into(ChainResults(), input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                            xent_regularize, xent_input, kaldi_way, deriv_weights, _options(options))
+                            xent_regularize, xent_input, kaldi_way, deriv_weights, _options(options), per_sequence, isolate)
 
 
 # What introspection reports stays the reference's signature (torchain/functions.py:128-130), the drop-in surface callers
@@ -632,7 +717,7 @@ chain_loss.__signature__ = inspect.signature(chain_loss).replace(
 
 
 def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                     xent_input, kaldi_way, deriv_weights=None, out_of_range_regularize=0.0):
+                     xent_input, kaldi_way, deriv_weights=None, out_of_range_regularize=0.0, per_sequence=False, isolate=False):
     """``chain_loss`` with the ``ChainResults`` given (parallel.chain_loss_data_parallel passes one that defers the
     host copy of the three floats until after its all-reduce): check the options, plan, one call."""
     deriv_weights = _deriv_weights(deriv_weights, _rows_of(input))
@@ -641,13 +726,13 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
     x, xe = _step_inputs(input, xent_input, want_grad)
     if want_grad:
         loss = _ChainStep.apply(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                                kaldi_way, deriv_weights, c)
+                                kaldi_way, deriv_weights, c, per_sequence, isolate)
         return loss, results
     # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the forward
     # recursions only; deriv_weights and the penalty are checked above and not used.  The reference has no such check
     # (functions.py:74,82) and pays for a training step.
     out, _, _ = _run_step(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                          kaldi_way, want_grad=False)
+                          kaldi_way, want_grad=False, per_sequence=per_sequence, isolate=isolate)
     # (the loss of an up-cast dtype the step does not take keeps that dtype)
     like = x if input.dtype in _STEP_DTYPES else input
     return (like.new_zeros(1) if results._defer_host_copy else out[3:4].to(like.dtype)), results
