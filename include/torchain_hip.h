@@ -640,6 +640,48 @@ int tc_supervision_best_path(tc_supervision *supervision, const void *nnet_outpu
                              int64_t num_rows, int32_t num_cols, int64_t row_stride, int32_t *pdf_dev, double *score_dev,
                              int device, void *stream);
 
+/* The single strongest path through the DENOMINATOR graph under the network's outputs: a phone-LM-constrained free decoding
+ * of every sequence of a minibatch (the numerator's counterpart is tc_supervision_best_path above; [K] has neither on the
+ * GPU).  The score of a path of states h_0 .. h_T joined by arcs a_1 .. a_T is
+ *     log pi(h_0) + sum_{t = 1 .. T} ( log w(a_t) + y_{t-1}(pdf(a_t)) )
+ * with pi the graph's initial probabilities (tc_den_graph_initial_probs: the ones the denominator uses; a state with
+ * pi == 0 starts no path) and every state final at cost 0, as in [K]'s denominator computation.  y is taken as it is, not
+ * clamped.  The leaky-HMM coefficient does not enter: it smooths a sum and is not a path.
+ *   S, nnet_output, dtype, layout_bct, num_rows, num_cols, row_stride : as tc_supervision_best_path's -- the 2-D float32
+ *                 matrix (T*S, P), row t*S + s, rows row_stride floats apart, or (layout_bct != 0) the contiguous (S, P, T)
+ *                 tensor of `dtype`; num_rows == S * max_frames, num_cols == the graph's pdfs.
+ *   seq_frames_dev : device int32[S], the sequences' lengths T_s (held to 1 .. max_frames), or NULL: max_frames each.
+ *                 Nothing at frames t >= T_s is read.
+ *   pdf_dev     : device int32[S * T], entry s * T + t the 0-based pdf of frame t, -1 in the padding frames t >= T_s
+ *   state_dev   : NULL, or device int32[S * (T + 1)], entry s * (T + 1) + t the state h_t of the FST, -1 for t > T_s
+ *   score_dev   : device double[S]
+ * Arithmetic: log w and log pi are float64 logarithms rounded to float32 once on the host; log w + y is one float32 sum; the
+ * running score is float32, one add and one max per arc.  A returned score is therefore within T_s * 2^-23 * M of the
+ * float64 score of the path that is returned, M the largest running |score| along that path, and no returned score is
+ * lower than the float64 optimum by more than the same bound.  Among paths of exactly equal score one is returned: the
+ * same one at every call, whatever the sequence's place in the batch and whatever the other sequences are (the lowest last
+ * state, then at every frame the in-arc that comes first in the graph's arc list).
+ * A sequence with a NaN or +-inf anywhere in the rows of its valid frames (any pdf) gets score NaN and -1 in all its
+ * slots; one without a path of T_s arcs gets -inf and -1s; the other sequences keep their bits.
+ * One launch (den_best_path_kernels.hip), one workgroup per sequence: a (max, +) forward pass over a CSR by destination
+ * state of the FST's own arcs (built from the graph on the first call per device, in device memory of its own: the
+ * tables of the training step are not touched, and a step on the graph gives the same bits before and after), every
+ * state's score to the workspace, then a traceback by one wavefront that finds each maximum again bit for bit from those
+ * scores -- no back-pointers.  Workspace: (T + 1) * Hs * 4 bytes per sequence, Hs the graph's states rounded up to 4 (the
+ * whole rounded up to 256), 16-byte aligned.  The previous frame's scores are kept in LDS while 8 * Hs + 1024 <= 163840
+ * (20352 states); larger graphs read them from the history row just written ("den_best_path_streamed_launches" counts
+ * those launches, tc_debug_set("force_den_best_path_streamed", 1) sends every graph that way).  Graphs of every size.
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null pointer, S or max_frames <= 0, num_rows != S * max_frames,
+ * num_cols that are not the graph's, an unknown dtype, a 2-D call with a 16-bit dtype or row_stride < num_cols, lengths
+ * that are not 4-byte aligned.  TC_ERR_WORKSPACE: a workspace that is null, too small or not 16-byte aligned.
+ * Asynchronous on `stream`; nothing is allocated after the graph's first call on the device.
+ * tc_debug_counter("den_best_path_launches") counts the launches; "den_launches" does not move. */
+int64_t tc_den_best_path_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T);
+int tc_den_best_path(tc_den_graph *g, int32_t S, const void *nnet_output, int dtype, int layout_bct, int64_t num_rows,
+                     int32_t num_cols, int64_t row_stride, const int32_t *seq_frames_dev /* nullable: T each */,
+                     int32_t max_frames, int32_t *pdf_dev /* [S * T] */, int32_t *state_dev /* nullable, [S * (T + 1)] */,
+                     double *score_dev /* [S] */, void *workspace, int64_t workspace_bytes, int device, void *stream);
+
 /* The cross-entropy objective Kaldi's chain trainer reports next to the chain objective ([K]
  * nnet-chain-training.cc: TraceMatMat(xent_output, xent_deriv, kTrans), xent_deriv = w * numerator posteriors);
  * the reference leaves it as a TODO (torchain/functions.py:88-89).  objf_dev: device double[1].  Needs
@@ -755,6 +797,8 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *   "force_num_windowed" (1: regular supervisions that fit the resident numerator kernel take the level-windowed one,
  *                     which otherwise serves those that do not fit; same bits.  Read at every numerator launch and by
  *                     tc_supervision_stats)
+ *   "force_den_best_path_streamed" (1: tc_den_best_path reads the previous frame's scores from the workspace for every
+ *                     graph, as it does for those beyond its LDS form; same bits.  Read at every such call)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -778,7 +822,9 @@ int tc_debug_set(const char *key, int value);
  * "ragged_two_cu_launches" = denominator launches of a ragged batch that took two workgroups per sequence, each sequence
  * meeting at half its own length (tied graphs, 8 sequences up to half the device's CUs, a derivative asked for, neither
  * "no_mitm" nor "no_phase_split" set; counted in "den_launches" too);
- * "best_path_launches" = tc_supervision_best_path calls that launched their kernel (not counted in "num_launches").
+ * "best_path_launches" = tc_supervision_best_path calls that launched their kernel (not counted in "num_launches");
+ * "den_best_path_launches" = tc_den_best_path calls that launched their kernel (not counted in "den_launches"), and
+ * "den_best_path_streamed_launches" those of them that read the previous frame's scores from the workspace.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

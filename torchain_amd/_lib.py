@@ -195,6 +195,10 @@ def _load():
     L.tc_num_forward_backward.argtypes = [vp, vp, i64, i32, i64, vp, i64, vp, vp, i64, C.c_int, vp]
     L.tc_supervision_best_path.restype = C.c_int
     L.tc_supervision_best_path.argtypes = [vp, vp, C.c_int, C.c_int, i64, i32, i64, vp, vp, C.c_int, vp]
+    L.tc_den_best_path_workspace_bytes.restype = i64
+    L.tc_den_best_path_workspace_bytes.argtypes = [vp, i32, i32]
+    L.tc_den_best_path.restype = C.c_int
+    L.tc_den_best_path.argtypes = [vp, i32, vp, C.c_int, C.c_int, i64, i32, i64, vp, i32, vp, vp, vp, vp, i64, C.c_int, vp]
     return L
 
 

@@ -507,6 +507,47 @@ int tc_supervision_best_path(tc_supervision *sup, const void *y, int dtype, int 
   return supervision_mark_use(sup, device, stream);
 }
 
+int64_t tc_den_best_path_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {
+  if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
+  return den_best_workspace_bytes(g->H, S, T);
+}
+
+int tc_den_best_path(tc_den_graph *g, int32_t S, const void *y, int dtype, int layout_bct, int64_t rows, int32_t cols,
+                     int64_t y_stride, const int32_t *seq_frames_dev, int32_t max_frames, int32_t *pdf_dev,
+                     int32_t *state_dev, double *score_dev, void *workspace, int64_t workspace_bytes, int device,
+                     void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!g || !y || !pdf_dev || !score_dev || S <= 0 || max_frames <= 0) return TC_ERR_INVALID_ARGUMENT;
+  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && dtype != TC_DTYPE_F32) return TC_ERR_INVALID_ARGUMENT;  // (2-D tensors are float32)
+  if (rows != (int64_t)S * max_frames || cols != g->P) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)seq_frames_dev & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
+  if (!workspace || den_best_workspace_bytes(g->H, S, max_frames) > workspace_bytes || !aligned16(workspace))
+    return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  DenBestParams p;
+  const int rc = den_best_tables(g, device, &p.t);
+  if (rc != TC_OK) return rc;
+  p.y = (const float *)y;
+  p.y_stride = layout_bct ? (int64_t)cols : y_stride;
+  p.y_bct = layout_bct ? 1 : 0;
+  p.elem = dtype;
+  p.S = S;
+  p.T = max_frames;
+  p.H = g->H;
+  p.P = g->P;
+  p.Hs = (int)den_best_row_floats(g->H);
+  p.seq_frames = seq_frames_dev;
+  p.hist = (float *)workspace;
+  p.pdf_out = pdf_dev;
+  p.state_out = state_dev;
+  p.score_out = score_dev;
+  p.resident = den_best_resident(g->H) && !debug_flag(kDbgForceDenBestStreamed);
+  return launch_den_best_path(p, (hipStream_t)stream_v);
+}
+
 }  // extern "C"
 
 // deriv_scale = 1: the reference's outputs.  deriv_scale = -1: what its backward returns (tc_chain_objf_and_grad).

@@ -173,6 +173,39 @@ struct DenGraphDev {
   float tune_ms[2] = {0.f, 0.f};  // what the decision was made on: fused, two-sequence (ms for kTuneFrames frames)
 };
 
+// The best path through the graph (tc_den_best_path, den_best_path_kernels.hip): the FST's own states and arcs -- not the
+// work graph, not layout positions -- as a CSR by destination state.  in_begin[h] .. in_begin[h + 1] are the in-arcs of
+// state h in the order of the graph's arc list; log w and log pi are float64 logarithms rounded to float32 (log 0 = -inf).
+struct DenBestArc {
+  int32_t src, pdf;
+  float logw;
+};
+struct DenBestDev {
+  const int32_t *in_begin = nullptr;  // [H + 1]
+  const DenBestArc *arcs = nullptr;   // [A]
+  const float *logpi = nullptr;       // [H]
+  void *blob = nullptr;
+};
+struct DenBestParams {
+  DenBestDev t;
+  const float *y;      // the 2-D float32 matrix, or the (S, P, T) tensor of `elem` (y_bct)
+  int64_t y_stride;
+  int y_bct, elem;
+  int S, T, H, P, Hs;  // T: the longest sequence's frames; Hs: H rounded up to 4, a history row's floats
+  const int32_t *seq_frames;  // [S] device, null: T each
+  float *hist;         // [S][T + 1][Hs]: every state's score after t frames (the workspace)
+  int32_t *pdf_out;    // [S][T]
+  int32_t *state_out;  // [S][T + 1], nullable
+  double *score_out;   // [S]
+  int resident;        // the previous frame's scores in LDS (den_best_resident), else read from the history row
+};
+constexpr int kDenBestSmallLds = 1024;  // what the kernel keeps in LDS beside the two score vectors, rounded up
+inline int64_t den_best_row_floats(int H) { return ((int64_t)H + 3) & ~(int64_t)3; }
+inline bool den_best_resident(int H) { return 2 * 4 * den_best_row_floats(H) + kDenBestSmallLds <= (int64_t)160 * 1024; }
+inline int64_t den_best_workspace_bytes(int H, int S, int T) {
+  return (((int64_t)S * (T + 1) * den_best_row_floats(H) * 4) + 255) & ~(int64_t)255;
+}
+
 // LDS layout of the fused kernel, in floats: [P | A | ACC | GAMMA | ALPHA? | red | asum].  exp(y)
 // (P) starts at offset 0 and its region has the compile-time size PV * 4096 of the kernel
 // instantiation, so the gather source A (alpha' forward, beta backward) has a compile-time base.
@@ -314,6 +347,9 @@ struct tc_den_graph {
   std::mutex mu;
   std::map<int, tc::DenGraphDev> dev;
   std::map<int, int> preset_variant;  // device -> kernel choice fixed by the caller (tc_den_graph_set_variant)
+  // tc_den_best_path's tables (den_best_path_kernels.hip), in a blob of their own per device: made on that call's first
+  // use (den_best_tables, under `mu`), so `dev` and what the training step reads are what they are without it
+  std::map<int, tc::DenBestDev> best_dev;
 };
 
 // ---- numerator -----------------------------------------------------------------------------------
@@ -537,6 +573,8 @@ int launch_num_windowed(const NumParams &p, hipStream_t stream);     // num_wind
 int launch_num_e2e(const NumParams &p, hipStream_t stream);          // num_e2e_kernels.hip (via launch_num)
 int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via launch_num_scatter)
 int launch_num_best_path(const NumParams &p, hipStream_t stream);    // num_best_path_kernels.hip (regular and end-to-end)
+int launch_den_best_path(const DenBestParams &p, hipStream_t stream);  // den_best_path_kernels.hip
+int den_best_tables(tc_den_graph *g, int device, DenBestDev *out);   // den_graph.cpp: made and uploaded on first use
 size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs);
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
@@ -637,7 +675,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -646,7 +684,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

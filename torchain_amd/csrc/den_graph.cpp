@@ -426,7 +426,7 @@ extern "C" {
 int tc_debug_set(const char *key, int value) {
   static const char *const names[kDbgCount] = {"force_general", "force_streamed", "no_split", "no_pdf_banks",
                                                "no_bank_search", "sched_trace", "no_phase_split", "no_num_overlap", "no_pair",
-                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed"};
+                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed"};
   if (!key) return TC_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < kDbgCount; ++i)
     if (!strcmp(key, names[i])) {
@@ -466,7 +466,7 @@ int64_t tc_debug_counter(const char *key) {
   if (key && !strcmp(key, "pool_device_allocs")) return pool_counter(0);
   if (key && !strcmp(key, "pool_reuses")) return pool_counter(1);
   static const char *const names[kCntCount] = {"den_launches", "den_backward_launches", "num_launches", "num_backward_launches", "layout_launches",
-                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches"};
+                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches"};
   for (int i = 0; key && i < kCntCount; ++i)
     if (!strcmp(key, names[i])) return g_launches[i].load(std::memory_order_relaxed);
   return -1;
@@ -654,6 +654,14 @@ void tc_den_graph_free(tc_den_graph *g) {
         (void)hipFree(kv.second.blob);
         (void)hipSetDevice(cur);
       }
+    }
+  }
+  for (auto &kv : g->best_dev) {
+    int cur = 0;
+    if (kv.second.blob && hipGetDevice(&cur) == hipSuccess) {
+      (void)hipSetDevice(kv.first);
+      (void)hipFree(kv.second.blob);
+      (void)hipSetDevice(cur);
     }
   }
   delete g;
@@ -1076,6 +1084,60 @@ static int upload_den_graph(tc_den_graph *g, int device) {
   g->dev[device] = d;
   return TC_OK;
 }
+
+}  // extern "C"
+
+// tc_den_best_path's tables: the FST's arcs as a CSR by destination state, in the order of the arc list within a state,
+// with log w and log pi taken in double and rounded to float.  Built and uploaded on the first call per device, into a
+// blob of their own; g->dev is neither read nor written.
+int tc::den_best_tables(tc_den_graph *g, int device, DenBestDev *out) {
+  std::lock_guard<std::mutex> lock(g->mu);
+  auto it = g->best_dev.find(device);
+  if (it != g->best_dev.end()) {
+    *out = it->second;
+    return TC_OK;
+  }
+  const int H = g->H;
+  const int64_t A = g->A;
+  std::vector<int32_t> in_begin(H + 1, 0);
+  for (int64_t a = 0; a < A; ++a) ++in_begin[g->arc_dst[a] + 1];
+  for (int h = 0; h < H; ++h) in_begin[h + 1] += in_begin[h];
+  std::vector<DenBestArc> arcs((size_t)std::max<int64_t>(A, 1), DenBestArc{0, 0, -INFINITY});
+  {
+    std::vector<int32_t> fill(in_begin.begin(), in_begin.end() - 1);
+    for (int64_t a = 0; a < A; ++a)
+      arcs[fill[g->arc_dst[a]]++] = DenBestArc{g->arc_src[a], g->arc_pdf[a], (float)std::log((double)g->arc_prob[a])};
+  }
+  std::vector<float> logpi(H);
+  for (int h = 0; h < H; ++h) logpi[h] = g->initial_probs[h] > 0.f ? (float)std::log((double)g->initial_probs[h]) : -INFINITY;
+  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t off_arcs = align(in_begin.size() * 4), off_pi = off_arcs + align(arcs.size() * sizeof(DenBestArc));
+  const size_t total = off_pi + align(logpi.size() * 4);
+  int prev = 0;
+  TC_HIP_CHECK(hipGetDevice(&prev));
+  TC_HIP_CHECK(hipSetDevice(device));
+  char *blob = nullptr;
+  hipError_t e = hipMalloc((void **)&blob, total);
+  if (e == hipSuccess) e = hipMemcpy(blob, in_begin.data(), in_begin.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(blob + off_arcs, arcs.data(), arcs.size() * sizeof(DenBestArc), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(blob + off_pi, logpi.data(), logpi.size() * 4, hipMemcpyHostToDevice);
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (blob) (void)hipFree(blob);
+    g_last_hip_error = (int)e;
+    return TC_ERR_HIP;
+  }
+  DenBestDev d;
+  d.in_begin = (const int32_t *)blob;
+  d.arcs = (const DenBestArc *)(blob + off_arcs);
+  d.logpi = (const float *)(blob + off_pi);
+  d.blob = blob;
+  g->best_dev[device] = d;
+  *out = d;
+  return TC_OK;
+}
+
+extern "C" {
 
 const char *tc_strerror(int code) {
   switch (code) {

@@ -751,3 +751,18 @@ def best_path(input, supervision):
         raise TypeError("best_path takes an io.Supervision, got %s" % type(supervision).__name__)
     with torch.no_grad():
         return supervision.best_path(input)
+
+
+def den_best_path(input, den_graph, frames=None, return_states=False, max_workspace_bytes=1 << 30, workspace=None, out=None,
+                  n_batch=None):
+    """The single strongest path through ``den_graph`` under ``input`` -- a free decoding constrained by the phone LM alone --
+    in the style of ``best_path``: ``(pdfs, scores)``, int32 ``(B, Tmax)`` (``-1`` in padding frames) and float64 ``(B,)``,
+    and with ``return_states`` the FST's states, int32 ``(B, Tmax + 1)`` (``io.DenominatorGraph.best_path``,
+    ``tc_den_best_path``).  ``input`` is a dense ``(B, C, T)`` float32 / bfloat16 / float16 tensor or 2-D float32 (then
+    ``frames`` or ``n_batch`` tells ``B``); ``frames`` the sequences' lengths, ``Supervision.frames`` of a ragged handle as it
+    is.  Autograd is not involved."""
+    if not isinstance(den_graph, io.DenominatorGraph):
+        raise TypeError("den_best_path takes an io.DenominatorGraph, got %s" % type(den_graph).__name__)
+    with torch.no_grad():
+        return den_graph.best_path(input, frames=frames, return_states=return_states, max_workspace_bytes=max_workspace_bytes,
+                                   workspace=workspace, out=out, n_batch=n_batch)

@@ -131,6 +131,109 @@ class DenominatorGraph:
               "tc_den_graph_debug_walk")
         return out
 
+    def best_path(self, nnet_output, frames=None, return_states=False, max_workspace_bytes=1 << 30, workspace=None, out=None,
+                  n_batch=None):
+        """The single strongest path through this graph under ``nnet_output`` (``tc_den_best_path``): a phone-LM-constrained
+        free decoding of every sequence, the denominator's counterpart of ``Supervision.best_path``.  A path's score is
+        ``log pi(h_0) + sum_t (log w(a_t) + y_{t-1}(pdf(a_t)))`` with the graph's initial probabilities, every state final at
+        cost 0 and ``y`` as it is (no clamp, no leaky-HMM coefficient).  Returns ``(pdfs, scores)`` or, with
+        ``return_states``, ``(pdfs, scores, states)`` on the input's device: ``pdfs`` int32 ``(B, Tmax)``, 0-based, ``scores``
+        float64 ``(B,)``, ``states`` int32 ``(B, Tmax + 1)`` (the FST's states); ``-1`` in padding slots.  A sequence with a
+        NaN or an infinity in its valid frames gets score NaN and ``-1`` everywhere.
+
+        ``nnet_output`` is contiguous ``(B, C, T)`` float32 / bfloat16 / float16 or 2-D float32 ``(T*B, C)`` with unit column
+        stride (row ``t*B + b``); a 2-D input needs ``frames`` or ``n_batch`` to tell ``B``.  ``frames``: a list, array or
+        int tensor of ``B`` lengths in ``1 .. Tmax`` (``Supervision.frames`` of a ragged handle as it is); ``None``: ``Tmax``
+        each.  Shapes, dtypes and lengths are checked here, before any library call.
+
+        The call keeps every state's score of every frame, ``(Tmax + 1) * 4 * (states rounded up to 4)`` bytes a sequence.
+        When that exceeds ``max_workspace_bytes`` for the whole batch (or the size of ``workspace``, a CUDA uint8 tensor to
+        reuse instead of allocating one), consecutive groups of sequences run one after the other, as few as fit, on the same
+        stream into the same outputs: the bits are those of one call.  (A group of a 2-D input is gathered into a matrix of
+        its own first.)  ``out``: preallocated ``(pdfs, scores)`` or ``(pdfs, scores, states)``.  Asynchronous on the current
+        stream; no autograd."""
+        x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("best_path: nnet_output must be a CUDA tensor (only the HIP implementation is available)")
+        P = self.n_pdf
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dim() == 3:
+            B, T = int(x.shape[0]), int(x.shape[2])
+            if int(x.shape[1]) != P or B < 1 or T < 1:
+                raise ValueError("best_path: nnet output of shape %s is not (B, %d, T)" % (tuple(x.shape), P))
+            if x.dtype not in dtypes:
+                raise TypeError("best_path: a (B, C, T) output must be float32, bfloat16 or float16, got %s" % x.dtype)
+            if n_batch is not None and int(n_batch) != B:
+                raise ValueError("best_path: n_batch = %d, but the output has %d sequences" % (int(n_batch), B))
+        elif x.dim() == 2:
+            if x.dtype != torch.float32:
+                raise TypeError("best_path: a 2-D output must be float32, got %s" % x.dtype)
+            if frames is None and n_batch is None:
+                raise ValueError("best_path: a 2-D output needs `frames` or `n_batch` to tell the number of sequences")
+            B = int(n_batch) if n_batch is not None else len(frames)
+            if int(x.shape[1]) != P or B < 1 or x.shape[0] < B or x.shape[0] % B != 0:
+                raise ValueError("best_path: nnet output of shape %s is not (T * %d, %d)" % (tuple(x.shape), B, P))
+            T = int(x.shape[0]) // B
+        else:
+            raise ValueError("best_path: nnet output must be (B, C, T) or (T*B, C), got shape %s" % (tuple(x.shape),))
+        lengths = None
+        if frames is not None:
+            lengths = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+            if lengths.ndim != 1 or lengths.dtype.kind not in "iu":
+                raise TypeError("best_path: frames must be a list or an int tensor of lengths")
+            if len(lengths) != B:
+                raise ValueError("best_path: %d lengths for %d sequences" % (len(lengths), B))
+            if lengths.min() < 1 or lengths.max() > T:
+                raise ValueError("best_path: every length must be in 1 .. %d, got %d .. %d" % (T, lengths.min(), lengths.max()))
+        device = x.device
+        if x.dim() == 3 and not x.is_contiguous():
+            x = x.contiguous()
+        if x.dim() == 2 and (x.stride(1) != 1 or x.stride(0) < P):
+            x = x.contiguous()
+        if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8
+                                      or workspace.device != device or not workspace.is_contiguous()):
+            raise ValueError("best_path: workspace must be a contiguous uint8 tensor on the output's device")
+        shapes = [((B, T), torch.int32), ((B,), torch.float64)] + ([((B, T + 1), torch.int32)] if return_states else [])
+        if out is not None:
+            if len(out) != len(shapes):
+                raise ValueError("best_path: out must hold %d tensors" % len(shapes))
+            for o, (shape, dt) in zip(out, shapes):
+                if tuple(o.shape) != shape or o.dtype != dt or o.device != device or not o.is_contiguous():
+                    raise ValueError("best_path: an out tensor is not a contiguous %s %s on %s" % (dt, shape, device))
+            outs = list(out)
+        else:
+            outs = [torch.empty(shape, dtype=dt, device=device) for shape, dt in shapes]
+        need = lambda n: int(lib.tc_den_best_path_workspace_bytes(self.ptr, n, T))  # noqa: E731  (host arithmetic only)
+        cap = int(max_workspace_bytes) if workspace is None else min(int(max_workspace_bytes), workspace.numel())
+        group = B
+        if need(B) > cap:
+            group = max(1, min(B, cap // need(1)))
+            while group > 1 and need(group) > cap:
+                group -= 1
+            if need(group) > cap:
+                raise ValueError("best_path: one sequence needs %d bytes of workspace, %d are allowed" % (need(1), cap))
+        ws = workspace if workspace is not None else torch.empty(need(group), dtype=torch.uint8, device=device)
+        fr = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            for s0 in range(0, B, group):
+                n = min(group, B - s0)
+                if x.dim() == 3:
+                    xg, stride = x[s0:s0 + n], 0
+                elif n == B:
+                    xg, stride = x, x.stride(0)
+                else:  # rows t*B + s0 .. t*B + s0 + n - 1 of every frame, as a matrix of the group's own
+                    rs = x.stride(0)
+                    xg = torch.as_strided(x, (T, n, P), (B * rs, rs, 1), x.storage_offset() + s0 * rs).reshape(T * n, P)
+                    stride = xg.stride(0)  # (a group of one sequence stays a view, rows B * rs apart)
+                check(lib.tc_den_best_path(self.ptr, n, C.c_void_p(xg.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), n * T, P,
+                                           stride, None if fr is None else C.c_void_p(fr[s0:s0 + n].data_ptr()), T,
+                                           C.c_void_p(outs[0][s0:s0 + n].data_ptr()),
+                                           C.c_void_p(outs[2][s0:s0 + n].data_ptr()) if return_states else None,
+                                           C.c_void_p(outs[1][s0:s0 + n].data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                           device.index, stream), "tc_den_best_path")
+        return tuple(outs)
+
 
 class Supervision:
     """Reference ``io.py:20-31``: wraps a supervision handle and exposes ``n_pdf``, ``n_batch``,
