@@ -572,6 +572,53 @@ int tc_chain_step_per_sequence(tc_den_graph *graph, tc_supervision *supervision,
                                int64_t workspace_bytes, int device, void *stream, int isolate_failures,
                                double *seq_results_dev);
 
+/* tc_chain_step_per_sequence with the cross-entropy head's log-softmax folded in.
+ * Kaldi's chain recipes end the cross-entropy head in a log-softmax (the "output-xent" layer).  The trainer takes
+ * xent_objf = sum(xent_output * xent_deriv) on its LOG-PROBABILITIES and back-propagates xent_regularize * xent_deriv (after
+ * MulRowsVec by deriv_weights) THROUGH that log-softmax ([K] nnet-chain-training.cc).  The reference has no log-softmax in
+ * training: its head ends in a plain Conv1d, torchain/functions.py:88-89 carries a "TODO: compute xent loss like kaldi?",
+ * and only forward.py:67 applies log_softmax, at inference.  Without the switch the step mirrors the reference: xent_grad is
+ * V = -xent_regularize * deriv_weights[row] * weight * gamma_num, the gradient of an objective linear in xent_input.
+ *   xent_log_softmax : != 0, with the xent branch active (xent_input given, xent_regularize != 0), x = xent_input, row =
+ *                      one (sequence, frame), c = channel, everything in float32 from the widened input:
+ *                        mx = max_c x[row, c],  ls = log(sum_c exp(x[row, c] - mx))            (lse = mx + ls)
+ *                        (float32 exponentials, their sum carried in double and its logarithm rounded once)
+ *                        xent_grad[row, c] = V[row, c] - (sum_c' V[row, c']) * exp((x[row, c] - mx) - ls)
+ *                      rounded once for 16-bit tensors; the gradient is dense.  A row of V without a non-zero entry -- a
+ *                      ragged minibatch's padding, a frame of deriv_weights == 0, a failed sequence of isolate_failures,
+ *                      the whole minibatch on the soft-failure route -- is +0, chosen by a select: a NaN in x there does
+ *                      not reach the gradient.
+ *                      xent_objf_dev = (-xent_regularize) * sum_rows sum_c weight * gamma_num * ((x - mx) - ls), the
+ *                      subtractions made in double, summed in double in the order of the call without the switch; the
+ *                      xent_sum of seq_results_dev and the survivors' sum of isolate_failures carry the same term.  The
+ *                      objective ignores deriv_weights, as without the switch.
+ *                      A NaN or +-inf in a live row of xent_input makes every element of that row's gradient and the
+ *                      row's objective term non-finite (a sequence's xent_sum with it, and its status bit 1); other rows
+ *                      keep their bits.
+ *                      results_dev3, loss_dev1, grad and every value formed from `input` do not change by a bit.
+ *                      kaldi_way == 0 with the switch: TC_ERR_INVALID_ARGUMENT (the whole objective is then run again on
+ *                      xent_input, which is another question).  Without the xent branch the switch does nothing.
+ *   how              : two launches of xent_softmax_kernels.hip.  The row statistics (mx, ls), 2 floats a row in the
+ *                      workspace, are formed in front of the objective from xent_input where the step reads it (float32
+ *                      rows, the widened / gathered float32 scratch, or the caller's (B, C, T) tensor of `dtype`); the
+ *                      numerator kernels subtract them in their cross-entropy sums.  The gradient pass runs behind the
+ *                      objective's soft-failure reset and in front of the last passes, in place on the float32 matrix the
+ *                      numerator wrote V to.  tc_debug_counter("xent_log_softmax_launches") counts both.
+ *   grad == NULL     : the evaluation step returns the same xent_objf_dev (statistics launch only) and writes no gradient.
+ * xent_log_softmax == 0: tc_chain_step_per_sequence, launch for launch, and its workspace suffices.
+ * Workspace: tc_chain_step_log_softmax_workspace_bytes = tc_chain_step_strided_workspace_bytes plus, with the xent branch,
+ * the row statistics (8 * num_sequences * frames_per_sequence bytes, rounded up to 256).  No host synchronisation, nothing
+ * allocated; safe under stream capture.  The split entries and the torch.library operator do not take the switch. */
+int64_t tc_chain_step_log_softmax_workspace_bytes(const tc_den_graph *graph, int32_t num_sequences,
+                                                  int32_t frames_per_sequence, int layout, int with_xent, int dtype);
+int tc_chain_step_log_softmax(tc_den_graph *graph, tc_supervision *supervision, const void *input, const void *xent_input,
+                              int layout, int64_t row_stride, int64_t batch_stride, int64_t frame_stride,
+                              float l2_regularize, float leaky_hmm_coefficient, float xent_regularize, int kaldi_way,
+                              void *grad, void *xent_grad, float *results_dev3, float *loss_dev1, double *xent_objf_dev,
+                              const float *deriv_weights, float out_of_range_regularize, int dtype, void *workspace,
+                              int64_t workspace_bytes, int device, void *stream, int isolate_failures,
+                              double *seq_results_dev, int xent_log_softmax);
+
 /* The benchmarked unit: [K] DenominatorComputation::Forward() + Backward(deriv_weight, deriv)
  * (direct use in the reference: src/chain-supervision-test.hpp:403-414).
  *   logprob_dev   : device double[1], sum over sequences of the denominator log-prob
@@ -824,7 +871,9 @@ int tc_debug_set(const char *key, int value);
  * "no_mitm" nor "no_phase_split" set; counted in "den_launches" too);
  * "best_path_launches" = tc_supervision_best_path calls that launched their kernel (not counted in "num_launches");
  * "den_best_path_launches" = tc_den_best_path calls that launched their kernel (not counted in "den_launches"), and
- * "den_best_path_streamed_launches" those of them that read the previous frame's scores from the workspace.
+ * "den_best_path_streamed_launches" those of them that read the previous frame's scores from the workspace;
+ * "xent_log_softmax_launches" = launches of tc_chain_step_log_softmax's two kernels (the row statistics and the gradient
+ * pass: 2 a training step, 1 an evaluation step that asks for xent_objf_dev, 0 with the switch off).
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

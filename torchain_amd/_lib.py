@@ -161,6 +161,10 @@ def _load():
                                         vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, C.c_int64, C.c_int, vp]
     L.tc_chain_step_per_sequence.restype = C.c_int
     L.tc_chain_step_per_sequence.argtypes = L.tc_chain_step_strided.argtypes + [C.c_int, vp]
+    L.tc_chain_step_log_softmax_workspace_bytes.restype = C.c_int64
+    L.tc_chain_step_log_softmax_workspace_bytes.argtypes = L.tc_chain_step_strided_workspace_bytes.argtypes
+    L.tc_chain_step_log_softmax.restype = C.c_int
+    L.tc_chain_step_log_softmax.argtypes = L.tc_chain_step_per_sequence.argtypes + [C.c_int]
     L.tc_rows_gather.restype = C.c_int
     L.tc_rows_gather.argtypes = [vp, C.c_int, i32, i32, i32, i64, i64, vp, i64, C.c_int, vp]
     L.tc_rows_scatter.restype = C.c_int

@@ -571,6 +571,9 @@ struct ObjfStep {  // what only the one-call step passes: all unset for the two 
   // out of the sums; either one selects the per-sequence finalize (alive_frames is then written to the workspace)
   double *seq_results = nullptr;
   bool isolate = false;
+  // tc_chain_step_log_softmax: the row statistics of xent_out ([rows][2], launch_xent_row_stats); the numerator's
+  // cross-entropy sums are then taken on the rows' log-softmax (NumParams::xent_lse)
+  const float *xent_lse = nullptr;
 };
 
 static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int64_t rows, int32_t cols,
@@ -611,6 +614,7 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
     np.xent_out_stride = o.xent_out_stride;
     np.xent_out_bct = o.xent_out_bct;
     np.seq_xent = w.xent_lp;
+    np.xent_lse = o.xent_lse;
   }
   np.xent_bct = o.xent_bct;  // (a (B, C, T) tensor the caller has cleared: only the posteriors' entries are written)
   np.xent_row_w = xent ? o.xent_row_w : nullptr;  // (tc_chain_step_weighted: the numerator is xent's only non-zero writer)
@@ -725,10 +729,11 @@ namespace {
 struct StepWorkspace {
   char *chain, *trace;
   float *y2d, *g2d, *x2d, *xg;
+  float *lse;  // tc_chain_step_log_softmax: xent_input's row statistics, [S * T][2] (behind everything the siblings carve)
   size_t chain_bytes, total;
 };
 StepWorkspace carve_step(char *base, const tc_den_graph *g, int S, int T, int P, bool three_d, bool xent,
-                         int dtype = TC_DTYPE_F32) {
+                         int dtype = TC_DTYPE_F32, bool log_softmax = false) {
   StepWorkspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -745,6 +750,7 @@ StepWorkspace carve_step(char *base, const tc_den_graph *g, int S, int T, int P,
   w.g2d = copies ? (float *)take(mat) : nullptr;
   w.x2d = copies && xent ? (float *)take(mat) : nullptr;
   w.xg = half && xent ? (float *)take(mat) : nullptr;
+  w.lse = log_softmax && xent ? (float *)take((size_t)S * T * 2 * sizeof(float)) : nullptr;
   w.total = off;
   return w;
 }
@@ -854,8 +860,12 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
                              float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
                              float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
                              float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
-                             void *stream_v, int isolate_failures = 0, double *seq_results_dev = nullptr) {
+                             void *stream_v, int isolate_failures = 0, double *seq_results_dev = nullptr,
+                             int xent_log_softmax = 0) {
   if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  // (with kaldi_way == 0 the whole objective is run again on xent_input: what a log-softmax in front of that means is
+  // another question)
+  if (xent_log_softmax && !kaldi_way) return TC_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)seq_results_dev & 7) != 0) return TC_ERR_INVALID_ARGUMENT;
   const bool cl = layout == TC_LAYOUT_CHANNEL_LAST;
   const int three_d = layout != TC_LAYOUT_ROWS;
@@ -889,7 +899,10 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   // kaldi_way == 0 runs the objective on xent_input.  pen_c2 == 0: none of this runs.
   const float pen_c2 = eval_only ? 0.0f : 2.0f * out_of_range_regularize;
   if (std::isinf(pen_c2)) return TC_ERR_INVALID_ARGUMENT;
-  const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype);
+  // Kaldi's log-softmax at the end of the cross-entropy head, folded in (xent_softmax_kernels.hip): without the xent branch
+  // the option does nothing
+  const bool lsm = xent_log_softmax != 0 && use_xent;
+  const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype, lsm);
   if (!workspace || (int64_t)w.total > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
   if (cl && !channel_last_strides_ok(S, T, P, sb, st)) return TC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(device);
@@ -915,6 +928,12 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   } else if (half) {
     rc = launch_widen_rows(dtype, input, row_stride, w.y2d, rows, P, stream);
     if (rc == TC_OK && use_xent) rc = launch_widen_rows(dtype, xent_input, row_stride, w.x2d, rows, P, stream);
+    if (rc != TC_OK) return rc;
+  }
+  // (the rows of xent_input where the objective finds them: an evaluation step without xent_objf_dev has no use for them)
+  if (lsm && (xent_objf_dev || !eval_only)) {
+    rc = launch_xent_row_stats(io.caller_bct ? dtype : TC_DTYPE_F32, io.xent_in, io.caller_bct, io.xent_stride, S, T, P, w.lse,
+                               stream);
     if (rc != TC_OK) return rc;
   }
 
@@ -954,12 +973,30 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   o.outputs_move_on = true;
   o.isolate = isolate_failures != 0;
   o.seq_results = seq_results_dev;
+  o.xent_lse = lsm ? w.lse : nullptr;
   rc = chain_objf(g, sup, io.y, rows, P, io.y_stride, results_dev3, io.gr, P, io.xg, P, l2_regularize, leaky, dscale, xscale,
                   w.chain, (int64_t)w.chain_bytes, device, stream_v, o);
   if (rc != TC_OK || eval_only) return rc;
+  const bool ragged = !sup->frames.empty();
+  const int32_t *frames_dev = nullptr, *alive = nullptr;
+  if (ragged) {
+    std::lock_guard<std::mutex> lock(sup->mu);
+    frames_dev = sup->frames_dev[device];
+  }
+  // (the isolating step: every sequence's surviving frames, left in the workspace by the finalize -- see below)
+  if (o.isolate)
+    alive = carve((char *)w.chain, hist_states(g), S, T, big_p(g), big_h(g), big_g(g), big_hb(g), split_room(g, S), pair_room(g), planes_room(g)).alive_frames;
+  // ---- the log-softmax's backward: the xent gradient V, final but for its move or rounding, becomes V - rowsum(V) *
+  // softmax(xent_input) in the float32 matrix the numerator wrote it to.  Behind chain_objf's soft-failure reset (rows of no
+  // mass become +0), over the rows the tail below does not zero: a sequence's own frames, none of a failed sequence.
+  if (lsm) {
+    rc = launch_xent_softmax_grad(io.caller_bct ? dtype : TC_DTYPE_F32, io.xent_in, io.caller_bct, io.xent_stride, io.xg, P, S, T,
+                                  P, w.lse, o.isolate ? alive : frames_dev, stream);
+    if (rc != TC_OK) return rc;
+  }
   rc = emit_gradients(io, layout, dtype, input, row_stride, sb, st, grad, xent_grad, w.y2d, S, T, P, pen_c2, row_w, device,
                       stream_v);
-  if (rc != TC_OK || (sup->frames.empty() && !o.isolate)) return rc;
+  if (rc != TC_OK || (!ragged && !o.isolate)) return rc;
   // A ragged minibatch: the objective wrote no padding row, the last passes moved whatever lay there; +0 into the padding
   // of the caller's gradients, each where its layout puts element (sequence, frame, channel).  (The (B, C, T) xent gradient
   // was cleared on the way in and has entries only at the numerator's posteriors.)
@@ -971,15 +1008,9 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
     // in the workspace (its own length, 0 when it failed; the handle's lengths when the whole minibatch took the failure
     // route), so the one launch covers padding and failed sequences -- whose rows hold whatever the kernels made of a
     // non-finite recursion, the (B, C, T) xent gradient's included.
-    const int32_t *alive = carve((char *)w.chain, hist_states(g), S, T, big_p(g), big_h(g), big_g(g), big_hb(g), split_room(g, S), pair_room(g), planes_room(g)).alive_frames;
     rc = launch_zero_failed(grad, eb, zb, zt, zc, S, T, P, alive, stream);
     if (rc == TC_OK && xent_grad && use_xent) rc = launch_zero_failed(xent_grad, eb, zb, zt, zc, S, T, P, alive, stream);
     return rc;
-  }
-  const int32_t *frames_dev = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(sup->mu);
-    frames_dev = sup->frames_dev[device];
   }
   rc = launch_zero_padding(grad, eb, zb, zt, zc, S, T, P, frames_dev, stream);
   if (rc == TC_OK && xent_grad && use_xent && !bct) rc = launch_zero_padding(xent_grad, eb, zb, zt, zc, S, T, P, frames_dev, stream);
@@ -1031,17 +1062,36 @@ int64_t tc_chain_step_strided_workspace_bytes(const tc_den_graph *g, int32_t S, 
   return tc_chain_step_typed_workspace_bytes(g, S, T, layout != TC_LAYOUT_ROWS, with_xent, dtype);
 }
 
+int64_t tc_chain_step_log_softmax_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T, int layout, int with_xent,
+                                                  int dtype) {
+  if (layout != TC_LAYOUT_ROWS && layout != TC_LAYOUT_BCT && layout != TC_LAYOUT_CHANNEL_LAST) return TC_ERR_INVALID_ARGUMENT;
+  if (!g || S <= 0 || T <= 0 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  return (int64_t)carve_step(nullptr, g, S, T, g->P, layout != TC_LAYOUT_ROWS, with_xent != 0, dtype, true).total;
+}
+
 int tc_chain_step_per_sequence(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
                                int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize, float leaky,
                                float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
                                float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
                                float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
                                void *stream_v, int isolate_failures, double *seq_results_dev) {
+  return tc_chain_step_log_softmax(g, sup, input_v, xent_input_v, layout, row_stride, batch_stride, frame_stride, l2_regularize,
+                                   leaky, xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1,
+                                   xent_objf_dev, deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes,
+                                   device, stream_v, isolate_failures, seq_results_dev, 0);
+}
+
+int tc_chain_step_log_softmax(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
+                              int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize, float leaky,
+                              float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
+                              float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                              float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                              void *stream_v, int isolate_failures, double *seq_results_dev, int xent_log_softmax) {
   if (layout == TC_LAYOUT_ROWS || layout == TC_LAYOUT_BCT)
     return chain_step_layout(g, sup, input_v, xent_input_v, layout, row_stride, 0, 0, l2_regularize, leaky, xent_regularize,
                              kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev, deriv_weights,
                              out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v, isolate_failures,
-                             seq_results_dev);
+                             seq_results_dev, xent_log_softmax);
   if (layout != TC_LAYOUT_CHANNEL_LAST || !sup) return TC_ERR_INVALID_ARGUMENT;
   if (!channel_last_strides_ok(sup->S, sup->T, sup->P, batch_stride, frame_stride)) return TC_ERR_INVALID_ARGUMENT;
   // (element offsets are multiples of the element size: a base that is not breaks every access)
@@ -1051,7 +1101,7 @@ int tc_chain_step_per_sequence(tc_den_graph *g, tc_supervision *sup, const void 
   return chain_step_layout(g, sup, input_v, xent_input_v, layout, 0, batch_stride, frame_stride, l2_regularize, leaky,
                            xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1, xent_objf_dev,
                            deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes, device, stream_v,
-                           isolate_failures, seq_results_dev);
+                           isolate_failures, seq_results_dev, xent_log_softmax);
 }
 
 int tc_chain_step_strided(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,

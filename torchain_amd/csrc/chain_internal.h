@@ -489,6 +489,10 @@ struct NumParams {
   // sequence without a path), [S] its log score.  Null for every other launch.  (At the end, as the two above.)
   int32_t *best_pdf = nullptr;
   double *best_score = nullptr;
+  // tc_chain_step_log_softmax (xent_softmax_kernels.hip): [rows][2] the row statistics (max, log(sum(exp(x - max)))) of
+  // xent_out's rows, row = t*S + s.  The cross-entropy objective's term becomes xent_scale * v * (x - max - log sum): the
+  // log-softmax of the row.  Null: the plain product.  (The last member: every older argument offset stays.)
+  const float *xent_lse = nullptr;
 };
 
 }  // namespace tc
@@ -669,6 +673,18 @@ int launch_rows_gather(int dtype, const void *x, int64_t sb, int64_t st, float *
 int launch_rows_scatter(int dtype, const float *in, int64_t in_stride, void *out, int64_t osb, int64_t ost, int B, int T,
                         int cols, const LastPass &lp, hipStream_t stream);
 
+// xent_softmax_kernels.hip (tc_chain_step_log_softmax): the cross-entropy head's log-softmax folded into the step.  x is
+// xent_input where the step's table puts it: float32 rows with unit channel stride (x_bct == 0: row t*S + s at
+// row * x_stride), or the caller's (B, C, T) tensor of `dtype` (x_bct != 0).  stats: [S*T][2] floats, row t*S + s.
+// launch_xent_row_stats leaves (max, log(sum(exp(x - max)))) of every row.  launch_xent_softmax_grad turns the xent
+// gradient V the numerator left in g (rows of g_stride, or a float32 (B, C, T) tensor) into V - rowsum(V) * softmax(x) in
+// place; a row without a non-zero entry of V becomes +0 by a select.  live_frames ([S], nullable): rows of frames >=
+// live_frames[s] are left alone (padding, and the failed sequences of the isolating step).
+int launch_xent_row_stats(int dtype, const void *x, int x_bct, int64_t x_stride, int S, int T, int P, float *stats,
+                          hipStream_t stream);
+int launch_xent_softmax_grad(int dtype, const void *x, int x_bct, int64_t x_stride, float *g, int64_t g_stride, int S, int T,
+                             int P, const float *stats, const int32_t *live_frames, hipStream_t stream);
+
 extern thread_local int g_last_hip_error;
 
 // Diagnostic switches (tc_debug_set in the public header): process-wide, read when a graph is built.  They
@@ -684,7 +700,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

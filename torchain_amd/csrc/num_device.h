@@ -73,6 +73,13 @@ __device__ __forceinline__ float num_posterior(const NumParams &p, const int *un
   return p.weight * sum;
 }
 
+// The cross-entropy output element x of frame-major row `row` as the objective takes it: x itself, or with the row
+// statistics of tc_chain_step_log_softmax (NumParams::xent_lse) the row's log-softmax x - max - log(sum(exp(x - max))), the
+// two float32 statistics subtracted in double one after the other (a row shifted by 1e4 keeps its digits).
+__device__ __forceinline__ double xent_log_prob(const NumParams &p, int64_t row, double x) {
+  return p.xent_lse ? (x - (double)p.xent_lse[2 * row]) - (double)p.xent_lse[2 * row + 1] : x;
+}
+
 // scatter of one unique entry `gu` of sequence q: [K] AddElements(weight, indexes, derivs); v = weight * posterior.  Each
 // (row, pdf) is owned by exactly one lane, so a plain read-modify-write.  Adds the entry's term of the sequence's
 // cross-entropy objective to xo.
@@ -90,10 +97,10 @@ __device__ __forceinline__ void num_scatter_one(const NumParams &p, int q, int g
   }
   // (the cross-entropy output: the caller's (B, C, T) tensor of element type E, or a float32 matrix)
   if (p.seq_xent)
-    xo += (double)(p.xent_scale * v) * (double)(std::is_same<E, float>::value
+    xo += (double)(p.xent_scale * v) * xent_log_prob(p, row, (double)(std::is_same<E, float>::value
                                                     ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
                                                 : p.xent_out_bct ? load_elem<E>(p.xent_out, bct)
-                                                                 : p.xent_out[row * p.xent_out_stride + pdf]);
+                                                                 : p.xent_out[row * p.xent_out_stride + pdf]));
 }
 
 // The entries of a sequence are dealt to kNumScatterLanes lanes (entry u to lane u mod 128) whatever the workgroup's size,

@@ -58,11 +58,14 @@ __device__ __forceinline__ double write_posterior(const NumParams &p, int q, int
     const float xv = p.xent_scale * v;
     p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_row_w ? p.xent_row_w[row] * xv : xv;
   }
-  if (p.seq_xent)
-    return (double)(p.xent_scale * v) * (double)(std::is_same<El, float>::value
-                                                     ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
-                                                     : p.xent_out_bct ? load_elem<El>(p.xent_out, bct)
-                                                                      : p.xent_out[row * p.xent_out_stride + pdf]);
+  if (p.seq_xent) {
+    const double x = (double)(std::is_same<El, float>::value
+                                  ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
+                                  : p.xent_out_bct ? load_elem<El>(p.xent_out, bct)
+                                                   : p.xent_out[row * p.xent_out_stride + pdf]);
+    // (tc_chain_step_log_softmax: the row's log-softmax, as num_device.h's xent_log_prob states it)
+    return (double)(p.xent_scale * v) * (p.xent_lse ? (x - (double)p.xent_lse[2 * row]) - (double)p.xent_lse[2 * row + 1] : x);
+  }
   return 0.0;
 }
 

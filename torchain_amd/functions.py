@@ -46,6 +46,17 @@ Same names, argument meaning, defaults and quirks as the reference:
   isolates a failed sequence: the objective, weight, l2 term, loss and cross-entropy objective are the survivors' and the failed
   sequence's gradient rows are ``+0`` like a ragged minibatch's padding; with nothing failed every output is bit for bit the
   default call's (``tc_chain_step_per_sequence``).
+* ``xent_log_softmax=True`` (keyword-only, through ``**options``; needs ``kaldi_way=True``): Kaldi's cross-entropy head ends
+  in a log-softmax, the objective ``sum(xent_output * xent_deriv)`` is taken on its log-probabilities and the derivative is
+  back-propagated through it.  The reference has none in training (``torchain/functions.py:88-89`` is a TODO, only
+  ``forward.py:67`` applies ``log_softmax``), so by default the gradient returned for ``xent_input`` is ``V = -xent_regularize
+  * w * gamma_num`` (times ``deriv_weights``), descent on an objective linear in ``xent_input``.  With the option the call
+  folds the log-softmax of the RAW ``xent_input`` in: the gradient becomes ``V - rowsum(V) * softmax(xent_input)`` row by row
+  (dense; a row without posteriors -- padding, ``deriv_weights == 0``, a failed sequence -- is ``+0`` whatever ``xent_input``
+  holds there) and ``results.xent_objf`` is taken on ``log_softmax(xent_input)``.  Everything formed from ``input`` keeps its
+  bits.  It replaces ``F.log_softmax(xe, dim=1)`` in front of the call, its backward and the activation that backward keeps
+  (``tc_chain_step_log_softmax``).  Not a bool, or ``kaldi_way=False`` with it: ``ValueError`` before any
+  library call.  Without the xent branch it does nothing.  ``torchain_amd/ops.py`` and the split entries do not take it.
 """
 import ctypes as C
 import inspect
@@ -340,6 +351,18 @@ def _failure_options(options):
     return bool(per_sequence) or isolate, isolate
 
 
+def _xent_options(options, kaldi_way):
+    """``xent_log_softmax`` taken out of ``**options`` and checked: a bool (default False).  With ``kaldi_way=False`` the
+    whole objective is run again on ``xent_input``, where a log-softmax is another question: that pair is a ``ValueError``, as
+    a value that is not a bool is -- before any library call."""
+    flag = options.pop("xent_log_softmax", False)
+    if not isinstance(flag, bool):
+        raise ValueError("xent_log_softmax must be a bool, got %r" % (flag,))
+    if flag and not kaldi_way:
+        raise ValueError("xent_log_softmax=True needs kaldi_way=True: with kaldi_way=False the objective is run on xent_input")
+    return flag
+
+
 def _penalized(g, y, c):
     """The library's penalised gradient with torch ops in the library's order (``tc_chain_step_penalized``): ``g + t`` where
     ``p != 0`` and ``g`` itself elsewhere, ``t = fl32(2c) * p``, ``p`` the part of ``y`` beyond ``+-OUTPUT_LIMIT`` (0 for NaN and
@@ -392,11 +415,11 @@ class _ChainStep(Function):
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
                 l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
-                out_of_range_regularize=0.0, per_sequence=False, isolate=False):
+                out_of_range_regularize=0.0, per_sequence=False, isolate=False, xent_log_softmax=False):
         out, grad, xgrad = _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
                                      leaky_hmm_coefficient, xent_regularize, kaldi_way, want_grad=True,
                                      deriv_weights=deriv_weights, out_of_range_regularize=out_of_range_regularize,
-                                     per_sequence=per_sequence, isolate=isolate)
+                                     per_sequence=per_sequence, isolate=isolate, xent_log_softmax=xent_log_softmax)
         ctx.grads = (grad, xgrad)
         if results._defer_host_copy:
             return input.new_zeros(1)
@@ -404,14 +427,15 @@ class _ChainStep(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return (ctx.grads[0], ctx.grads[1]) + (None,) * 11
+        return (ctx.grads[0], ctx.grads[1]) + (None,) * 12
 
 
 def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
               xent_regularize, kaldi_way, want_grad, deriv_weights=None, out_of_range_regularize=0.0, per_sequence=False,
-              isolate=False):
+              isolate=False, xent_log_softmax=False):
     """``per_sequence`` / ``isolate`` (``_failure_options``): the same step through ``tc_chain_step_per_sequence``, which also
-    fills the sequences' own values, allocated next to ``out``.  Otherwise:
+    fills the sequences' own values, allocated next to ``out``.  ``xent_log_softmax`` (``_xent_options``) with the xent branch
+    active: that step through ``tc_chain_step_log_softmax``, whose workspace also holds the row statistics.  Otherwise:
     One ``tc_chain_step_strided``, in the layout ``classify_layout`` finds (a time-major view as the 2-D rows it is;
     gradients of channel-last views come back as views of dense tensors).  ``want_grad=False`` is the evaluation step
     (``grad == NULL``): forward recursions only, no gradient tensors -- [K] ``ComputeChainObjfAndDeriv`` with ``nnet_output_deriv == NULL``; ``deriv_weights``
@@ -450,13 +474,17 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
     xgrad = torch.empty(gshape, dtype=x.dtype, device=device) if use_xent and want_grad else None
     with torch.cuda.device(device):
         cur = torch.cuda.current_stream(device)
+        log_softmax = bool(xent_log_softmax) and use_xent  # (without the xent branch the option does nothing)
         key = (S, T, layout != TC_LAYOUT_ROWS, use_xent, dtype)  # (a channel-last step has the (B, C, T) step's workspace)
+        if log_softmax:
+            key += ("log_softmax",)
         sizes = den_graph.__dict__.setdefault("_step_bytes", {}) if isinstance(den_graph, io.DenominatorGraph) else {}
         nbytes = sizes.get(key)
         if nbytes is None:
-            nbytes = lib.tc_chain_step_strided_workspace_bytes(den_ptr, S, T, layout, int(use_xent), dtype)
+            sizer = lib.tc_chain_step_log_softmax_workspace_bytes if log_softmax else lib.tc_chain_step_strided_workspace_bytes
+            nbytes = sizer(den_ptr, S, T, layout, int(use_xent), dtype)
             if nbytes < 0:
-                check(int(nbytes), "tc_chain_step_strided_workspace_bytes")
+                check(int(nbytes), "tc_chain_step_log_softmax_workspace_bytes" if log_softmax else "tc_chain_step_strided_workspace_bytes")
             sizes[key] = nbytes
         capturing = torch.cuda.is_current_stream_capturing()
         # (inside a graph capture the workspace comes from the graph's own pool and lives as long as the graph does)
@@ -475,6 +503,10 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         seq = None
         if per_sequence or isolate:
             seq = torch.empty((S, 6), dtype=torch.float64, device=device)
+        if log_softmax:
+            check(lib.tc_chain_step_log_softmax(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail, int(bool(isolate)),
+                                                _ptr(seq), 1), "tc_chain_step_log_softmax")
+        elif per_sequence or isolate:
             check(lib.tc_chain_step_per_sequence(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail, int(bool(isolate)),
                                                  _ptr(seq)), "tc_chain_step_per_sequence")
         else:
@@ -703,10 +735,12 @@ def chain_loss(input, den_graph, supervision,
                l2_regularize=0.0, leaky_hmm_coefficient=1e-5,
                xent_regularize=0.0, xent_input=None, kaldi_way=False, *, deriv_weights=None, **options):
     """``options``, keyword-only (the module docstring): ``out_of_range_regularize=0.0`` (``_options``), ``per_sequence=False``
-    and ``on_failure="minibatch"`` (``_failure_options``)."""
+    and ``on_failure="minibatch"`` (``_failure_options``), ``xent_log_softmax=False`` (``_xent_options``)."""
     per_sequence, isolate = _failure_options(options)
+    log_softmax = _xent_options(options, kaldi_way)
     return _chain_loss_into(ChainResults(), input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                            xent_regularize, xent_input, kaldi_way, deriv_weights, _options(options), per_sequence, isolate)
+                            xent_regularize, xent_input, kaldi_way, deriv_weights, _options(options), per_sequence, isolate,
+                            log_softmax)
 
 
 # What introspection reports stays the reference's signature (torchain/functions.py:128-130), the drop-in surface callers
@@ -717,7 +751,8 @@ chain_loss.__signature__ = inspect.signature(chain_loss).replace(
 
 
 def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                     xent_input, kaldi_way, deriv_weights=None, out_of_range_regularize=0.0, per_sequence=False, isolate=False):
+                     xent_input, kaldi_way, deriv_weights=None, out_of_range_regularize=0.0, per_sequence=False, isolate=False,
+                     xent_log_softmax=False):
     """``chain_loss`` with the ``ChainResults`` given (parallel.chain_loss_data_parallel passes one that defers the
     host copy of the three floats until after its all-reduce): check the options, plan, one call."""
     deriv_weights = _deriv_weights(deriv_weights, _rows_of(input))
@@ -726,13 +761,14 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
     x, xe = _step_inputs(input, xent_input, want_grad)
     if want_grad:
         loss = _ChainStep.apply(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                                kaldi_way, deriv_weights, c, per_sequence, isolate)
+                                kaldi_way, deriv_weights, c, per_sequence, isolate, xent_log_softmax)
         return loss, results
     # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the forward
     # recursions only; deriv_weights and the penalty are checked above and not used.  The reference has no such check
     # (functions.py:74,82) and pays for a training step.
     out, _, _ = _run_step(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                          kaldi_way, want_grad=False, per_sequence=per_sequence, isolate=isolate)
+                          kaldi_way, want_grad=False, per_sequence=per_sequence, isolate=isolate,
+                          xent_log_softmax=xent_log_softmax)
     # (the loss of an up-cast dtype the step does not take keeps that dtype)
     like = x if input.dtype in _STEP_DTYPES else input
     return (like.new_zeros(1) if results._defer_host_copy else out[3:4].to(like.dtype)), results

@@ -18,7 +18,7 @@ import inspect
 import numpy as np
 import torch
 
-from .functions import ChainResults, _chain_loss_into, _failure_options, _options
+from .functions import ChainResults, _chain_loss_into, _failure_options, _options, _xent_options
 
 
 def shard_range(num_sequences, rank, world_size):
@@ -167,15 +167,19 @@ def chain_loss_data_parallel(input, den_graph, supervision, l2_regularize=0.0, l
     ``chain_loss`` takes it; the term is per element of the local gradient, so every rank passes the same value and nothing
     else is needed.  ``per_sequence`` / ``on_failure`` (keyword-only, as ``chain_loss`` takes them): the rank's local sums are
     already the survivors', so the one all-reduce of four doubles is unchanged and the global results are the sum of the
-    ranks' masked ones; ``results.per_sequence`` stays this rank's own sequences."""
+    ranks' masked ones; ``results.per_sequence`` stays this rank's own sequences.  ``xent_log_softmax`` (keyword-only, as
+    ``chain_loss`` takes it): the log-softmax acts on the rows of the local shard, and the reduced ``xent_objf`` is the sum of
+    the ranks' terms -- nothing else changes here."""
     per_sequence, isolate = _failure_options(options)
+    log_softmax = _xent_options(options, kaldi_way)
     c = _options(options, "chain_loss_data_parallel")
     if input.is_cuda and hasattr(den_graph, "prepare"):
         sync_den_graph_variant(den_graph, input.device, group)
     results = ChainResults()
     results._defer_host_copy = bool(input.is_cuda)
     loss, results = _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
-                                     xent_regularize, xent_input, kaldi_way, deriv_weights, c, per_sequence, isolate)
+                                     xent_regularize, xent_input, kaldi_way, deriv_weights, c, per_sequence, isolate,
+                                     log_softmax)
     all_reduce_results(results, group=group, device=input.device if input.is_cuda else None, even_if_alone=even_if_alone)
     with torch.no_grad():
         loss.copy_(results.loss)
