@@ -729,6 +729,62 @@ int tc_den_best_path(tc_den_graph *g, int32_t S, const void *nnet_output, int dt
                      int32_t max_frames, int32_t *pdf_dev /* [S * T] */, int32_t *state_dev /* nullable, [S * (T + 1)] */,
                      double *score_dev /* [S] */, void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* ---- the denominator graph's weights on caller-built supervisions ------------------------------------------------------
+ * Every supervision Kaldi writes into an eg has been composed with the normalization FST of den.fst ([K]
+ * AddWeightToSupervisionFst, DenominatorGraph::GetNormalizationFst; the end-to-end egs: --normalization-fst-scale), which
+ * makes the numerator a weighted subset of the denominator's paths -- a path the phone LM forbids is gone, one it allows
+ * carries -log pi(h_0) - sum log w -- and so bounds the objective by 0.  (The reference takes such supervisions from the
+ * egs: src/my_lib.h:21.)  tc_den_compose does that for supervisions the caller built.  Host code only: no GPU is
+ * touched, the graph is only read (tc_den_graph_hash and every result of a step on it stay what they were), and any number
+ * of threads may call it on one handle.
+ *
+ * The normalization acceptor N of a graph: the states of den.fst plus a start q0; every arc h -> h' (pdf p, probability w)
+ * at cost -log w; for every state h with pi(h) > 0 and every arc h -> h' an arc q0 -> h' with label p at cost
+ * -log pi(h) - log w (the epsilon-removed form); every state final at cost 0.  pi and w are the handle's float32 values
+ * (tc_den_graph_initial_probs, tc_den_graph_arcs: the ones the denominator kernels use), the logarithms are float64; an
+ * arc with w == 0 is on no path and is left out.  N's costs are multiplied by `scale` (finite, >= 0; [K] e2e
+ * normalization_fst_scale; 0 only restricts the paths).  The leaky-HMM coefficient does not enter.
+ *
+ * Input: S acceptors concatenated exactly as tc_supervision_create_ragged (e2e == 0: `start` is not read, state 0 starts
+ * every sequence) or tc_supervision_create_e2e (e2e != 0) take them.  Output, per sequence, the product with N: start
+ * (s_0, q0); an arc (s, h) --p--> (s', h') for every pair of an input arc and an arc of N with its label, at cost
+ * float32(double(c_sup) + scale * c_N); the final cost of (s, h) is that of s; trimmed to the states that are reachable and
+ * lead to a final state.  Two arcs of N with the same source and label stay two arcs: nothing is determinised or
+ * minimised, so a non-deterministic den.fst is summed over.  ([K] determinises in the tropical semiring afterwards, which
+ * would keep only the best of the start states' terms; here several LM histories per supervision state stay alive for
+ * the first few phones, which costs states and keeps the sum.)
+ * Order (the same input gives the same bytes): breadth-first from the start, states taken in increasing new id, their
+ * input arcs in input order, for each the matching arcs of N in the order the handle keeps the graph's arcs (for q0:
+ * h ascending, then its arcs); a state gets the next id when first reached; trimming keeps the relative order.  The start
+ * is state 0 of every output, and a time-unfolded input comes out in time order: what tc_supervision_create_ragged asks.
+ * Status per sequence: 0; 1 = the product is empty (no path of the input is in the graph); 2 = the product has more than
+ * max_states states before trimming ([K] kSupervisionMaxStates = 200000) or does not fit the int32 offsets.  A sequence of
+ * status 1 or 2 has no states in the output and changes nothing for the others: every sequence's output is that of the
+ * call on it alone.
+ * Size: composed end-to-end acceptors can exceed TC_E2E_MAX_STATES / TC_E2E_MAX_ARCS, composed regular ones can move
+ * from the resident to the level-windowed numerator; tc_den_compose_info and tc_supervision_stats tell beforehand.
+ * TC_ERR_BAD_FST (nothing is read out of bounds): offsets that do not start at 0 or decrease, a sequence without states,
+ * a label outside 1 .. label_dim, a next state or start outside the sequence, a NaN or -inf cost.  A label above the
+ * graph's number of pdfs matches nothing.  TC_ERR_INVALID_ARGUMENT: a null pointer, S, label_dim or max_states < 1, a
+ * scale that is negative or not finite.
+ * The result is owned by the caller (tc_den_compose_free).  tc_den_compose_sizes: out3 = {S, states, arcs} of the
+ * concatenated output.  tc_den_compose_info: status[S] and info4[S][4] = states, arcs of the input and of the output (any
+ * pointer may be NULL).  tc_den_compose_copy: the output's arrays in the layout of the input (seq_state_begin S + 1, start
+ * S, arc_begin states + 1, ...; any pointer may be NULL).
+ * tc_den_graph_arcs: the graph's arcs as the handle keeps them (num_arcs entries each, host memory, any may be NULL):
+ * source, destination, 0-based pdf, probability. */
+typedef struct tc_den_compose_result tc_den_compose_result;
+int tc_den_graph_arcs(const tc_den_graph *graph, int32_t *src, int32_t *dst, int32_t *pdf, float *prob);
+int tc_den_compose(tc_den_compose_result **out, const tc_den_graph *graph, int32_t num_sequences, int32_t label_dim,
+                   int e2e, const int32_t *seq_state_begin, const int32_t *start /* e2e only */, const int32_t *arc_begin,
+                   const int32_t *arc_ilabel, const float *arc_weight, const int32_t *arc_nextstate,
+                   const float *final_weight, float scale, int64_t max_states);
+int tc_den_compose_sizes(const tc_den_compose_result *result, int64_t *out3);
+int tc_den_compose_info(const tc_den_compose_result *result, int32_t *status, int64_t *info4);
+int tc_den_compose_copy(const tc_den_compose_result *result, int32_t *seq_state_begin, int32_t *start, int32_t *arc_begin,
+                        int32_t *arc_ilabel, float *arc_weight, int32_t *arc_nextstate, float *final_weight);
+void tc_den_compose_free(tc_den_compose_result *result);
+
 /* The cross-entropy objective Kaldi's chain trainer reports next to the chain objective ([K]
  * nnet-chain-training.cc: TraceMatMat(xent_output, xent_deriv, kTrans), xent_deriv = w * numerator posteriors);
  * the reference leaves it as a TODO (torchain/functions.py:88-89).  objf_dev: device double[1].  Needs

@@ -203,6 +203,18 @@ def _load():
     L.tc_den_best_path_workspace_bytes.argtypes = [vp, i32, i32]
     L.tc_den_best_path.restype = C.c_int
     L.tc_den_best_path.argtypes = [vp, i32, vp, C.c_int, C.c_int, i64, i32, i64, vp, i32, vp, vp, vp, vp, i64, C.c_int, vp]
+    L.tc_den_graph_arcs.restype = C.c_int
+    L.tc_den_graph_arcs.argtypes = [vp, vp, vp, vp, vp]
+    L.tc_den_compose.restype = C.c_int
+    L.tc_den_compose.argtypes = [C.POINTER(vp), vp, i32, i32, C.c_int, vp, vp, vp, vp, vp, vp, vp, f32, i64]
+    L.tc_den_compose_sizes.restype = C.c_int
+    L.tc_den_compose_sizes.argtypes = [vp, vp]
+    L.tc_den_compose_info.restype = C.c_int
+    L.tc_den_compose_info.argtypes = [vp, vp, vp]
+    L.tc_den_compose_copy.restype = C.c_int
+    L.tc_den_compose_copy.argtypes = [vp] * 8
+    L.tc_den_compose_free.restype = None
+    L.tc_den_compose_free.argtypes = [vp]
     return L
 
 

@@ -42,6 +42,45 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _concat_fsts(fsts, e2e, who):
+    """The per-sequence CSR tuples of ``from_fsts`` (``e2e`` false) / ``from_e2e_fsts`` as the concatenated arrays the C
+    ABI takes: ``(seq_state_begin, start, arc_begin, ilabel, arc_weight, nextstate, final)``."""
+    seq_begin, starts, ab, il, aw, nx, fin = [0], [], [np.zeros(1, np.int32)], [], [], [], []
+    arcs = 0
+    for i, f in enumerate(fsts):
+        if len(f) != (6 if e2e else 5):
+            raise ValueError("%s: sequence %d: an FST is a tuple of %d arrays" % (who, i, 6 if e2e else 5))
+        start, (arc_begin, ilabel, arc_weight, nextstate, final) = (f[0], f[1:]) if e2e else (0, f)
+        arc_begin = np.asarray(arc_begin, dtype=np.int64)
+        final = np.asarray(final, dtype=np.float32).ravel()
+        if arc_begin.shape != (len(final) + 1,) or arc_begin[0] != 0:
+            raise ValueError("%s: sequence %d: arc_begin must have len(final) + 1 entries starting at 0" % (who, i))
+        if any(np.asarray(x).size != arc_begin[-1] for x in (ilabel, arc_weight, nextstate)):
+            raise ValueError("%s: sequence %d: ilabel, arc_weight and nextstate must have arc_begin[-1] entries" % (who, i))
+        seq_begin.append(seq_begin[-1] + len(final))
+        starts.append(int(start))
+        ab.append((arc_begin[1:] + arcs).astype(np.int32))
+        arcs += int(arc_begin[-1])
+        il.append(np.asarray(ilabel, dtype=np.int32).ravel())
+        aw.append(np.asarray(arc_weight, dtype=np.float32).ravel())
+        nx.append(np.asarray(nextstate, dtype=np.int32).ravel())
+        fin.append(final)
+    return (_i32(seq_begin), _i32(starts), _i32(np.concatenate(ab)), _i32(np.concatenate(il)), _f32(np.concatenate(aw)),
+            _i32(np.concatenate(nx)), _f32(np.concatenate(fin)))
+
+
+def _normalized(who, den_graph, fsts, e2e, scale, label_dim):
+    """``fsts`` composed with ``den_graph``'s normalization acceptor for a constructor: an empty or oversized product is
+    an error that names the sequences."""
+    out, info = den_graph._normalize(fsts, e2e, scale, 200000, label_dim, who)
+    bad = [i for i, f in enumerate(out) if f is None]
+    if bad:
+        empty = [i for i in bad if info["status"][i] == 1]
+        raise ValueError("%s: sequences %s have no path in the denominator graph%s" % (who, empty, "" if empty == bad else
+                         "; sequences %s exceed %d states once composed" % ([i for i in bad if i not in empty], 200000)))
+    return out
+
+
 class DenominatorGraph:
     """``DenominatorGraph(rspec, n_pdf)`` as in the reference (``io.py:51-54`` ->
     ``my_lib_denominator_graph_new``, ``src/my_lib_example.cpp:129-134``): ``rspec`` is the path of an
@@ -130,6 +169,69 @@ class DenominatorGraph:
         check(lib.tc_den_graph_debug_walk(self.ptr, int(direction), _p(gather), _p(pdf_factor), _p(out)),
               "tc_den_graph_debug_walk")
         return out
+
+    def arcs(self):
+        """The graph's arcs as the handle keeps them (``tc_den_graph_arcs``): ``(src, dst, pdf, prob)``, ``pdf`` 0-based,
+        ``prob`` the float32 probabilities the denominator kernels use."""
+        n = self.num_arcs
+        src, dst, pdf, prob = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        check(lib.tc_den_graph_arcs(self.ptr, _p(src), _p(dst), _p(pdf), _p(prob)), "tc_den_graph_arcs")
+        return src, dst, pdf, prob
+
+    def normalize_fsts(self, fsts, e2e=False, scale=1.0, max_states=200000):
+        """Puts this graph's weights on supervisions the caller built (``tc_den_compose``): every FST composed with the
+        graph's normalization acceptor, as [K] ``AddWeightToSupervisionFst`` does to every supervision Kaldi writes into an
+        eg.  A path the graph does not contain is gone, one it contains gains ``scale * (-log pi(h_0) - sum log w)`` (summed
+        over the start states and parallel arcs that admit it: nothing is determinised), so the objective of the result is
+        bounded by 0.  ``scale``: [K] e2e ``normalization_fst_scale``; 0 only restricts the paths.
+
+        ``fsts``: per-sequence tuples as ``Supervision.from_fsts`` (``e2e`` false) or ``from_e2e_fsts`` takes them.  Returns
+        ``(fsts_out, info)``: ``fsts_out`` in the same form -- start state 0, states in breadth-first order, so a
+        time-unfolded input stays in time order -- with ``None`` for a sequence whose product is empty or has more than
+        ``max_states`` states before trimming; ``info``: per-sequence numpy arrays ``status`` (0, 1 = empty, 2 = too large),
+        ``states_in``, ``arcs_in``, ``states_out``, ``arcs_out``.  Composed end-to-end FSTs can exceed the end-to-end
+        numerator's 2048 states / 8192 arcs, composed regular ones can move to the level-windowed numerator: ``info`` and
+        ``Supervision.stats()`` say so before anything runs.  Host only: no GPU is touched and the graph is not modified."""
+        return self._normalize(fsts, e2e, scale, max_states, self.n_pdf, "normalize_fsts")
+
+    def _normalize(self, fsts, e2e, scale, max_states, label_dim, who):
+        fsts = list(fsts)
+        if not fsts:
+            raise ValueError("%s: no FSTs" % who)
+        scale = float(scale)
+        if not (scale >= 0.0) or scale == float("inf"):
+            raise ValueError("%s: the normalization scale must be finite and >= 0, got %r" % (who, scale))
+        if int(max_states) < 1:
+            raise ValueError("%s: max_states must be at least 1" % who)
+        sb, st, ab, il, aw, nx, fin = _concat_fsts(fsts, bool(e2e), who)
+        res = C.c_void_p()
+        check(lib.tc_den_compose(C.byref(res), self.ptr, len(fsts), int(label_dim), int(bool(e2e)), _p(sb), _p(st), _p(ab), _p(il),
+                                 _p(aw), _p(nx), _p(fin), scale, int(max_states)), "tc_den_compose")
+        try:
+            S = len(fsts)
+            sizes = np.zeros(3, np.int64)
+            check(lib.tc_den_compose_sizes(res, _p(sizes)), "tc_den_compose_sizes")
+            ns, na = int(sizes[1]), int(sizes[2])
+            status, info4 = np.zeros(S, np.int32), np.zeros((S, 4), np.int64)
+            check(lib.tc_den_compose_info(res, _p(status), _p(info4)), "tc_den_compose_info")
+            osb, ost, oab = np.zeros(S + 1, np.int32), np.zeros(S, np.int32), np.zeros(ns + 1, np.int32)
+            oil, onx = np.zeros(na, np.int32), np.zeros(na, np.int32)
+            oaw, ofin = np.zeros(na, np.float32), np.zeros(ns, np.float32)
+            check(lib.tc_den_compose_copy(res, _p(osb), _p(ost), _p(oab), _p(oil), _p(oaw), _p(onx), _p(ofin)), "tc_den_compose_copy")
+        finally:
+            lib.tc_den_compose_free(res)
+        out = []
+        for s in range(S):
+            if status[s] != 0:
+                out.append(None)
+                continue
+            s0, s1 = int(osb[s]), int(osb[s + 1])
+            a0, a1 = int(oab[s0]), int(oab[s1])
+            f = (oab[s0:s1 + 1] - a0, oil[a0:a1].copy(), oaw[a0:a1].copy(), onx[a0:a1].copy(), ofin[s0:s1].copy())
+            out.append(((int(ost[s]),) + f) if e2e else f)
+        info = {"status": status, "states_in": info4[:, 0].copy(), "arcs_in": info4[:, 1].copy(),
+                "states_out": info4[:, 2].copy(), "arcs_out": info4[:, 3].copy()}
+        return out, info
 
     def best_path(self, nnet_output, frames=None, return_states=False, max_workspace_bytes=1 << 30, workspace=None, out=None,
                   n_batch=None):
@@ -263,7 +365,7 @@ class Supervision:
         return cls(handle)
 
     @classmethod
-    def from_e2e_fsts(cls, weight, frames_per_sequence, label_dim, fsts):
+    def from_e2e_fsts(cls, weight, frames_per_sequence, label_dim, fsts, den_graph=None, normalization_scale=1.0):
         """End-to-end supervision ([K] ``Supervision::e2e_fsts``): one acceptor per sequence, not unfolded in time.
         ``fsts`` is a list of per-sequence ``(start, arc_begin, ilabel, arc_weight, nextstate, final)`` in CSR form
         (``ilabel`` = pdf_id + 1, tropical costs, ``final`` = inf for a state that is not final).
@@ -271,10 +373,17 @@ class Supervision:
         ``frames_per_sequence``: an int, or one length per sequence (a "ragged" minibatch of whole utterances).  Then
         ``n_frame`` and ``shape`` use the longest length ``Tmax``: every tensor keeps its ``(B, C, Tmax)`` / ``(Tmax * B, C)``
         shape, frames ``t >= frames[s]`` of sequence ``s`` are padding that influences nothing, and every gradient is
-        exactly zero there.  The lengths live in the handle: ``chain_loss`` and the other calls take no new argument."""
+        exactly zero there.  The lengths live in the handle: ``chain_loss`` and the other calls take no new argument.
+
+        ``den_graph``: a ``DenominatorGraph`` whose weights the FSTs do not carry yet -- they are composed with its
+        normalization acceptor first (``DenominatorGraph.normalize_fsts``, costs times ``normalization_scale``: [K] e2e
+        ``normalization_fst_scale``), which bounds the objective by 0.  A sequence without a path in the graph raises
+        ``ValueError`` naming the sequences.  ``None``: the FSTs are taken as they are."""
         fsts = list(fsts)
         if not fsts:
             raise ValueError("from_e2e_fsts: no FSTs")
+        if den_graph is not None:
+            fsts = _normalized("from_e2e_fsts", den_graph, fsts, True, normalization_scale, label_dim)
         ragged = not np.isscalar(frames_per_sequence) and np.ndim(frames_per_sequence) > 0
         if ragged:
             lengths = np.asarray(frames_per_sequence)
@@ -314,7 +423,7 @@ class Supervision:
         return cls(handle)
 
     @classmethod
-    def from_fsts(cls, weight, frames_per_sequence, label_dim, fsts):
+    def from_fsts(cls, weight, frames_per_sequence, label_dim, fsts, den_graph=None, normalization_scale=1.0):
         """Regular supervisions of unequal lengths (a "ragged" minibatch of whole utterances): one time-unfolded acceptor
         per sequence, as alignments and lattices give them.  ``fsts`` is a list of per-sequence
         ``(arc_begin, ilabel, arc_weight, nextstate, final)`` in CSR form -- each what ``from_fst`` takes with
@@ -325,10 +434,15 @@ class Supervision:
         ``n_frame`` and ``shape`` use the longest length ``Tmax``, as for ``from_e2e_fsts`` with a list of lengths: every
         tensor keeps its ``(B, C, Tmax)`` / ``(Tmax * B, C)`` shape, frames ``t >= frames[s]`` of sequence ``s`` are padding
         that influences nothing, and every gradient is exactly zero there.  For every sequence the numerator computes the
-        bits it computes on that sequence alone."""
+        bits it computes on that sequence alone.
+
+        ``den_graph``, ``normalization_scale``: as for ``from_e2e_fsts`` -- the FSTs are composed with the graph's
+        normalization acceptor first, a sequence without a path in the graph raises ``ValueError`` naming the sequences."""
         fsts = list(fsts)
         if not fsts:
             raise ValueError("from_fsts: no FSTs")
+        if den_graph is not None:
+            fsts = _normalized("from_fsts", den_graph, fsts, False, normalization_scale, label_dim)
         lengths = np.asarray(frames_per_sequence)
         if lengths.shape != (len(fsts),) or lengths.dtype.kind not in "iu":
             raise ValueError("from_fsts: frames_per_sequence must be one int per sequence")
@@ -360,10 +474,10 @@ class Supervision:
         return cls(handle)
 
     @classmethod
-    def from_sequences(cls, sups):
+    def from_sequences(cls, sups, den_graph=None, normalization_scale=1.0):
         """A ragged minibatch from single-sequence regular supervisions (``torchain_amd.synth.SupFst`` with
         ``num_sequences == 1``: what the egs readers return for one eg), each of its own ``frames_per_sequence``.  They must
-        share ``weight`` and ``label_dim``."""
+        share ``weight`` and ``label_dim``.  ``den_graph``, ``normalization_scale``: as for ``from_fsts``."""
         sups = list(sups)
         if not sups:
             raise ValueError("from_sequences: no supervisions")
@@ -375,7 +489,48 @@ class Supervision:
             if float(s.weight) != float(sups[0].weight) or int(s.label_dim) != int(sups[0].label_dim):
                 raise ValueError("from_sequences: supervision %d differs from the first in weight or label_dim" % i)
         return cls.from_fsts(sups[0].weight, [int(s.frames_per_sequence) for s in sups], sups[0].label_dim,
-                             [(s.arc_begin, s.ilabel, s.arc_weight, s.nextstate, s.final) for s in sups])
+                             [(s.arc_begin, s.ilabel, s.arc_weight, s.nextstate, s.final) for s in sups],
+                             den_graph=den_graph, normalization_scale=normalization_scale)
+
+    @classmethod
+    def from_alignments(cls, weight, pdfs, label_dim, frames=None, den_graph=None, normalization_scale=1.0):
+        """Regular supervisions from frame-level pdf alignments, e.g. what ``best_path`` of a flat-start model's handle
+        returns: one linear acceptor per sequence at cost 0, through ``from_fsts``.  ``pdfs``: int ``(B, Tmax)``, 0-based,
+        ``-1`` in the padding; ``frames``: the sequences' lengths, by default the count of non-negative entries of each
+        row.  With ``den_graph`` the alignment carries the graph's weights, ``-log pi - sum log w`` summed over the start
+        states that admit it.  ``ValueError``: a ``-1`` inside a sequence (``best_path`` found no path for it), a pdf outside
+        ``label_dim``, an alignment the graph does not contain.  Tolerance around the phone boundaries needs the tree and
+        the transition model and stays with the caller, who passes the widened FSTs to ``from_fsts``."""
+        if isinstance(pdfs, torch.Tensor):
+            pdfs = pdfs.detach().cpu().numpy()
+        pdfs = np.asarray(pdfs)
+        if pdfs.ndim != 2 or pdfs.dtype.kind not in "iu" or pdfs.shape[0] < 1:
+            raise ValueError("from_alignments: pdfs must be an int (B, Tmax) array")
+        B, Tmax = pdfs.shape
+        if frames is None:
+            lengths = (pdfs >= 0).sum(axis=1)
+        else:
+            lengths = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+            if lengths.shape != (B,) or lengths.dtype.kind not in "iu":
+                raise ValueError("from_alignments: frames must be one int per sequence")
+        bad = [b for b in range(B) if not 1 <= int(lengths[b]) <= Tmax]
+        if bad:
+            raise ValueError("from_alignments: sequences %s have no frames (or more than the array holds)" % bad)
+        bad = [b for b in range(B) if (pdfs[b, :int(lengths[b])] < 0).any() or (pdfs[b, int(lengths[b]):] != -1).any()]
+        if bad:
+            raise ValueError("from_alignments: sequences %s have a -1 inside their frames or a pdf in their padding" % bad)
+        bad = [b for b in range(B) if (pdfs[b, :int(lengths[b])] >= int(label_dim)).any()]
+        if bad:
+            raise ValueError("from_alignments: sequences %s have a pdf outside 0 .. %d" % (bad, int(label_dim) - 1))
+        fsts = []
+        for b in range(B):
+            n = int(lengths[b])
+            final = np.full(n + 1, np.inf, np.float32)
+            final[n] = 0.0
+            fsts.append((np.minimum(np.arange(n + 2), n).astype(np.int32), (pdfs[b, :n] + 1).astype(np.int32),
+                         np.zeros(n, np.float32), np.arange(1, n + 1, dtype=np.int32), final))
+        return cls.from_fsts(weight, [int(x) for x in lengths], label_dim, fsts, den_graph=den_graph,
+                             normalization_scale=normalization_scale)
 
     @property
     def is_e2e(self):
