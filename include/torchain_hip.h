@@ -150,6 +150,35 @@ int tc_supervision_create_e2e_ragged(tc_supervision **out, float weight, int32_t
 int tc_supervision_frames(const tc_supervision *supervision, int32_t *frames_host);
 int32_t tc_supervision_is_ragged(const tc_supervision *supervision);
 
+/* End-to-end supervisions of ANY size the device can walk: tc_supervision_create_e2e (seq_frames == NULL: every sequence
+ * has frames_per_sequence frames) and tc_supervision_create_e2e_ragged (seq_frames: one length >= 1 per sequence, host
+ * memory; frames_per_sequence is not read) in one entry, with the same input, the same validation in the same order
+ * (TC_ERR_BAD_FST before any size rule) and the same tables, but without TC_E2E_MAX_STATES / _ARCS / _PDFS.  A sequence is
+ * refused on size (TC_ERR_UNSUPPORTED) only when
+ *     16 * ceil4(states) + 4 * ceil4(distinct pdfs) + 2048 > 163840        (ceil4: rounded up to a multiple of 4)
+ * -- two double score vectors and the frame's y per distinct pdf in LDS: 8192 states with 7680 distinct pdfs, 10108 states
+ * with 4 -- and its arc count is not limited beyond the tables' int32 offsets.  The rule is per sequence: the kernels lay
+ * their LDS out with each sequence's own sizes, so a batch's largest state count and its largest pdf count may belong to
+ * two sequences (10108 states / 4 pdfs beside 8192 / 7680 is taken, by the numerator and by tc_supervision_best_path).  The rules on num_sequences * frames and on
+ * the 4 GiB of kernel scratch stand as above.
+ * A handle whose sequences all fit the three limits is the handle the two entries above make: same kernel
+ * (num_e2e_kernels.hip), same launches, same pool slot, same bits.  One with a sequence beyond them takes
+ * num_e2e_large_kernels.hip -- the same arithmetic in the same orders, the arc occupations in the supervision's pool slot
+ * (4 bytes per arc more) instead of LDS -- in every entry that takes a supervision: the objective and its derivative
+ * beside the denominator or in line, the cross-entropy outputs, 16-bit (B, C, T) inputs, ragged lengths, the per-sequence
+ * step, tc_supervision_best_path.  tc_debug_counter("num_e2e_large_launches") counts its launches.
+ * The two older entries keep their refusal; tc_rand_reader_* and the egs readers build their handles through them. */
+int tc_supervision_create_e2e_any(tc_supervision **out, float weight, int32_t num_sequences, int32_t frames_per_sequence,
+                                  const int32_t *seq_frames, int32_t label_dim, const int32_t *seq_state_begin,
+                                  const int32_t *start, const int32_t *arc_begin, const int32_t *arc_ilabel,
+                                  const float *arc_weight, const int32_t *arc_nextstate, const float *final_weight);
+/* What the numerator will do with an end-to-end supervision, known on the host (tc_supervision_stats' counterpart; a regular
+ * handle: TC_ERR_INVALID_ARGUMENT).  out8: sequences; the most states, arcs and distinct pdfs of one sequence; the LDS bytes
+ * the resident kernel would need for them and the LDS bytes the large kernel needs (the most of one sequence); the bytes of kernel scratch in the
+ * handle's pool slot (history, y / posteriors and, on the large route, the arc occupations, each rounded up to 256); the
+ * route: 0 resident, 1 large ("force_num_e2e_large" as it stands at this call). */
+int tc_supervision_e2e_stats(const tc_supervision *supervision, int64_t *out8);
+
 /* Regular (time-unfolded) supervisions of UNEQUAL sequence lengths: one epsilon-free acceptor per sequence, the acceptors
  * concatenated the way tc_supervision_create_e2e_ragged takes its input (sequence s owns states [seq_state_begin[s],
  * seq_state_begin[s+1]); arc_begin has seq_state_begin[S] + 1 entries starting at 0, positions in the concatenated arc
@@ -678,8 +707,10 @@ int tc_num_forward_backward(tc_supervision *supervision, const float *nnet_outpu
  * this call -- then one wavefront traces back from the best final state.  A regular supervision needs
  * 16 * L + 4 * U + 2048 <= 163840 bytes of LDS, L the widest time level's states (rounded up to 2) and U the most unique
  * (frame, pdf) entries of one frame (rounded up to 4): about 8000 states a level when each has a pdf of its own, where
- * the level-windowed numerator needs 32 * L + 4 * U + 4 * (arcs leaving a level); beyond that TC_ERR_UNSUPPORTED.  End-to-end supervisions: the limits of
- * tc_supervision_create_e2e.
+ * the level-windowed numerator needs 32 * L + 4 * U + 4 * (arcs leaving a level); beyond that TC_ERR_UNSUPPORTED.  End-to-end supervisions:
+ * 16 * ceil4(states) + 4 * ceil4(distinct pdfs) bytes for the two score vectors and the frame's y of one sequence, laid out
+ * per sequence (the kernel has no other LDS): every sequence of a handle of tc_supervision_create_e2e, _e2e_ragged and
+ * _e2e_any meets it, so no end-to-end handle is refused on size.
  * TC_ERR_INVALID_ARGUMENT, before any device call: a null pointer, num_rows or num_cols that are not the handle's, an
  * unknown dtype, a 2-D call with a 16-bit dtype or row_stride < num_cols.  Asynchronous on `stream`; no workspace, and
  * nothing is allocated once the supervision is staged.  tc_debug_counter("best_path_launches") counts the launches. */
@@ -761,7 +792,7 @@ int tc_den_best_path(tc_den_graph *g, int32_t S, const void *nnet_output, int dt
  * max_states states before trimming ([K] kSupervisionMaxStates = 200000) or does not fit the int32 offsets.  A sequence of
  * status 1 or 2 has no states in the output and changes nothing for the others: every sequence's output is that of the
  * call on it alone.
- * Size: composed end-to-end acceptors can exceed TC_E2E_MAX_STATES / TC_E2E_MAX_ARCS, composed regular ones can move
+ * Size: composed end-to-end acceptors can exceed TC_E2E_MAX_STATES / TC_E2E_MAX_ARCS (tc_supervision_create_e2e_any takes them), composed regular ones can move
  * from the resident to the level-windowed numerator; tc_den_compose_info and tc_supervision_stats tell beforehand.
  * TC_ERR_BAD_FST (nothing is read out of bounds): offsets that do not start at 0 or decrease, a sequence without states,
  * a label outside 1 .. label_dim, a next state or start outside the sequence, a NaN or -inf cost.  A label above the
@@ -902,6 +933,11 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *                     tc_supervision_stats)
  *   "force_den_best_path_streamed" (1: tc_den_best_path reads the previous frame's scores from the workspace for every
  *                     graph, as it does for those beyond its LDS form; same bits.  Read at every such call)
+ *   "force_num_e2e_large" (1: end-to-end supervisions that fit the resident numerator kernel take num_e2e_large_kernels.hip,
+ *                     which otherwise serves those that do not fit; same bits.  Read when a supervision first reaches a device
+ *                     -- its pool slot then gets the 4 bytes per arc that kernel needs -- at every numerator launch and by
+ *                     tc_supervision_e2e_stats; a launch on a handle staged before the switch was set returns
+ *                     TC_ERR_UNSUPPORTED before anything is enqueued or counted)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -929,7 +965,8 @@ int tc_debug_set(const char *key, int value);
  * "den_best_path_launches" = tc_den_best_path calls that launched their kernel (not counted in "den_launches"), and
  * "den_best_path_streamed_launches" those of them that read the previous frame's scores from the workspace;
  * "xent_log_softmax_launches" = launches of tc_chain_step_log_softmax's two kernels (the row statistics and the gradient
- * pass: 2 a training step, 1 an evaluation step that asks for xent_objf_dev, 0 with the switch off).
+ * pass: 2 a training step, 1 an evaluation step that asks for xent_objf_dev, 0 with the switch off);
+ * "num_e2e_large_launches" = end-to-end numerator launches that took num_e2e_large_kernels.hip (counted in "num_launches" too).
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -110,6 +110,10 @@ def _load():
     L.tc_supervision_is_e2e.argtypes = [vp]
     L.tc_supervision_create_e2e_ragged.restype = C.c_int
     L.tc_supervision_create_e2e_ragged.argtypes = [C.POINTER(vp), f32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tc_supervision_create_e2e_any.restype = C.c_int
+    L.tc_supervision_create_e2e_any.argtypes = [C.POINTER(vp), f32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tc_supervision_e2e_stats.restype = C.c_int
+    L.tc_supervision_e2e_stats.argtypes = [vp, vp]
     L.tc_supervision_create_ragged.restype = C.c_int
     L.tc_supervision_create_ragged.argtypes = [C.POINTER(vp), f32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.tc_supervision_frames.restype = C.c_int

@@ -420,7 +420,13 @@ struct E2eDev {
   // weight * posterior (stage, [T x upid] per sequence at T * pdf_off[s])
   double *alpha_hist;
   int32_t max_states, max_arcs, max_pdfs;
+  // num_e2e_large_kernels.hip's arc occupations, one float per arc of every sequence (at arc_off[s]): scratch of the slot
+  // behind the stage, this many 256-byte units behind alpha_hist; 0: the slot has none (the handle fits the resident
+  // kernel and was staged without "force_num_e2e_large").  It fills the structure's tail padding: kernel arguments keep
+  // their offsets.
+  int32_t occ_off256;
 };
+static_assert(sizeof(E2eDev) == 15 * sizeof(void *) + 16, "E2eDev: NumParams' layout is part of the resident kernels' code");
 
 // One slot of the per-device supervision pool (supervision.cpp): device blob, pinned staging of the same size,
 // `ready` = the upload has landed, `done` = the last launch that reads the blob has finished.
@@ -579,7 +585,27 @@ int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via
 int launch_num_best_path(const NumParams &p, hipStream_t stream);    // num_best_path_kernels.hip (regular and end-to-end)
 int launch_den_best_path(const DenBestParams &p, hipStream_t stream);  // den_best_path_kernels.hip
 int den_best_tables(tc_den_graph *g, int device, DenBestDev *out);   // den_graph.cpp: made and uploaded on first use
-size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs);
+// dynamic LDS of num_e2e_kernel: two double score vectors, the frame's y per distinct pdf and one float per arc (max_arcs = 0:
+// of the kernels that keep no arc occupations on chip, num_e2e_large_kernel and num_e2e_best_path_kernel)
+inline size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs) {
+  return (size_t)2 * ((max_states + 3) & ~3) * sizeof(double) + (((max_pdfs + 3) & ~3) + (size_t)max_arcs) * sizeof(float);
+}
+// num_e2e_large_kernels.hip: the end-to-end numerator for sequences beyond the resident kernel's TC_E2E_MAX_* (launch_num_e2e
+// dispatches).  Its LDS is num_e2e_lds_bytes(states, 0, pdfs); e2e_large_fits is tc_supervision_create_e2e_any's size rule.
+int launch_num_e2e_large(const NumParams &p, hipStream_t stream);
+inline bool e2e_beyond_resident(int max_states, int max_arcs, int max_pdfs) {
+  return max_states > TC_E2E_MAX_STATES || max_arcs > TC_E2E_MAX_ARCS || max_pdfs > TC_E2E_MAX_PDFS;
+}
+inline bool e2e_large_fits(int states, int pdfs) {
+  return num_windowed_fits((size_t)16 * ((states + 3) & ~3) + (size_t)4 * ((pdfs + 3) & ~3));
+}
+// Dynamic LDS of a launch of num_e2e_large_kernel / num_e2e_best_path_kernel, which lay it out with each sequence's own
+// sizes.  Every sequence of a handle meets e2e_large_fits (the create entries), so none needs more than the rule admits; none
+// needs more than the batch's largest state count beside its largest pdf count either, which may belong to two sequences.
+inline size_t e2e_seq_lds_bytes(int max_states, int max_pdfs) {
+  const size_t both = num_e2e_lds_bytes(max_states, 0, max_pdfs), rule = (size_t)kLdsLimitBytes - 2048;
+  return both < rule ? both : rule;
+}
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
 // the denominator leaves CUs idle (api.cpp).
@@ -691,7 +717,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -700,7 +726,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

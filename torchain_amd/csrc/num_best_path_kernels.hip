@@ -143,13 +143,13 @@ __global__ __launch_bounds__(kBestThreads) void num_best_path_kernel(const NumPa
 template <typename El = float, bool RAGGED = false>
 __global__ __launch_bounds__(kBestThreads) void num_e2e_best_path_kernel(const NumParams p) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  const int MS = (p.t.e2e_tab.max_states + 3) & ~3;
-  double *A = reinterpret_cast<double *>(lds_raw);   // [2][MS]: the scores, double-buffered
-  float *E = reinterpret_cast<float *>(A + 2 * MS);  // [max_pdfs]: the frame's y per distinct pdf
 
   const int q = blockIdx.x, tid = threadIdx.x;
   const int T = RAGGED ? ragged_frames(p.seq_frames, q, p.T) : p.T;
   const SeqView v = seq_view(p, q);
+  const int MS = (v.n + 3) & ~3;  // (the sequence's own layout, as num_e2e_large_kernel's: the size rule is per sequence)
+  double *A = reinterpret_cast<double *>(lds_raw);   // [2][MS]: the scores, double-buffered
+  float *E = reinterpret_cast<float *>(A + 2 * MS);  // [v.np]: the frame's y per distinct pdf
   const int start = p.t.e2e_tab.start[q];
   int32_t *out = p.best_pdf + (int64_t)q * p.T;
 
@@ -230,10 +230,10 @@ int launch_num_best_path(const NumParams &p, hipStream_t stream) {
   size_t lds;
   if (p.t.e2e) {
     const E2eDev &e = p.t.e2e_tab;
-    if (e.max_states > TC_E2E_MAX_STATES || e.max_arcs > TC_E2E_MAX_ARCS || e.max_pdfs > TC_E2E_MAX_PDFS)
-      return TC_ERR_UNSUPPORTED;
+    // the kernel's own LDS -- two score vectors and the frame's y laid out per sequence, no static LDS; its pdfs and arcs are
+    // walked in loops -- which is the per-sequence rule of the create entries: every end-to-end handle passes
+    lds = e2e_seq_lds_bytes(e.max_states, e.max_pdfs);
     if (!e.alpha_hist) return TC_ERR_UNSUPPORTED;
-    lds = num_e2e_lds_bytes(e.max_states, 0, e.max_pdfs);
   } else {
     // (a ragged supervision: its own level offsets come with its lengths)
     if (p.seq_frames && !p.seq_level_off) return TC_ERR_INVALID_ARGUMENT;

@@ -18,6 +18,8 @@
 // in each direction.  The alpha history and y of every (frame, pdf) live in the supervision's pool slot; y is overwritten
 // by the backward pass with weight * posterior when the numerator runs beside the denominator ("staged").
 // No float atomics, every sum in a fixed order: two runs give the same bits.
+// A sequence beyond TC_E2E_MAX_STATES / _ARCS / _PDFS -- the occupations' LDS and the registers of a thread's pdfs -- takes
+// num_e2e_large_kernels.hip, which keeps this kernel's arithmetic and orders (launch_num_e2e dispatches).
 //
 // The numerator's ok flag ([K] ComputeChainObjfAndDerivE2e: numerator_ok joins the denominator's and the finite check)
 // rides on the sequence's log-probability: -inf when no path has T arcs, NaN when the backward total beta_0(start)
@@ -33,41 +35,7 @@ namespace tc {
 
 namespace {
 
-constexpr int kE2eThreads = 256;
 constexpr int kE2ePdfsPerThread = TC_E2E_MAX_PDFS / kE2eThreads;
-constexpr float kAgreeRel = 1e-4f;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// the sequence's posterior v = weight * gamma of (frame t, pdf) into deriv / xent, and its cross-entropy objective term
-template <typename El>
-__device__ __forceinline__ double write_posterior(const NumParams &p, int q, int t, int pdf, float v) {
-  const int64_t row = (int64_t)t * p.S + q;
-  const int64_t bct = ((int64_t)q * p.P + pdf) * p.T + t;  // (sequence, pdf, frame) of a (B, C, T) tensor
-  if (p.deriv) p.deriv[row * p.deriv_stride + pdf] += p.deriv_scale * v;
-  if (p.xent) {  // (times the row's deriv_weight when one is given; the objective term below is not)
-    const float xv = p.xent_scale * v;
-    p.xent[p.xent_bct ? bct : row * p.xent_stride + pdf] = p.xent_row_w ? p.xent_row_w[row] * xv : xv;
-  }
-  if (p.seq_xent) {
-    const double x = (double)(std::is_same<El, float>::value
-                                  ? p.xent_out[p.xent_out_bct ? bct : row * p.xent_out_stride + pdf]
-                                  : p.xent_out_bct ? load_elem<El>(p.xent_out, bct)
-                                                   : p.xent_out[row * p.xent_out_stride + pdf]);
-    // (tc_chain_step_log_softmax: the row's log-softmax, as num_device.h's xent_log_prob states it)
-    return (double)(p.xent_scale * v) * (p.xent_lse ? (x - (double)p.xent_lse[2 * row]) - (double)p.xent_lse[2 * row + 1] : x);
-  }
-  return 0.0;
-}
 
 // the 256 threads' shares of a sequence's cross-entropy objective, added in a fixed order
 __device__ __forceinline__ void e2e_xent_sum(double v, double *out, int tid) {
@@ -156,14 +124,14 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
       if (want_beta) v.hist[(int64_t)T * v.n + i] = A[c * MS + i];
       mx = fmax(mx, A[c * MS + i] + (double)v.final_lw[i]);
     }
-    mx = wave_max_d(mx);
+    mx = e2e_wave_max_d(mx);
     if (lane == 0) red_d[wave] = mx;
     __syncthreads();
     mx = fmax(fmax(red_d[0], red_d[1]), fmax(red_d[2], red_d[3]));
     float sum = 0.f;
     if (mx > -INFINITY)
       for (int i = tid; i < v.n; i += kE2eThreads) sum += __expf((float)(A[c * MS + i] + (double)v.final_lw[i] - mx));
-    sum = wave_sum(sum);
+    sum = e2e_wave_sum(sum);
     if (lane == 0) red_c[wave] = sum;
     __syncthreads();
     logz = mx > -INFINITY ? mx + log((double)((red_c[0] + red_c[1]) + (red_c[2] + red_c[3]))) : -INFINITY;
@@ -224,7 +192,7 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_kernel(const NumParams p)
       for (int i = v.pdf_begin[k]; i < v.pdf_begin[k + 1]; ++i) g[r] += OCC[v.pdf_arc[i]];
       gs += g[r];
     }
-    gs = wave_sum(gs);
+    gs = e2e_wave_sum(gs);
     if (lane == 0) red_c[wave] = gs;
     __syncthreads();
     const float tot = (red_c[0] + red_c[1]) + (red_c[2] + red_c[3]);
@@ -270,17 +238,17 @@ __global__ __launch_bounds__(kE2eThreads) void num_e2e_scatter_kernel(const NumP
   if (p.seq_xent) e2e_xent_sum(xo, p.seq_xent + q, tid);
 }
 
-size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs) {
-  return (size_t)2 * ((max_states + 3) & ~3) * sizeof(double) + (((max_pdfs + 3) & ~3) + (size_t)max_arcs) * sizeof(float);
-}
-
 int launch_num_e2e(const NumParams &p, hipStream_t stream) {
+  const E2eDev &e = p.t.e2e_tab;
+  // a sequence the resident kernel cannot hold, or the switch that sends the others there too: num_e2e_large_kernels.hip
+  const bool large = e2e_beyond_resident(e.max_states, e.max_arcs, e.max_pdfs) || debug_flag(kDbgForceNumE2eLarge);
+  // (... which needs the occupations' room in the slot: a handle staged before the switch was set has none.  Refused before
+  // anything is counted)
+  if (large && !e.occ_off256) return TC_ERR_UNSUPPORTED;
   count_launch(kCntNum);
   if (p.deriv || p.xent || p.seq_xent) count_launch(kCntNumBackward);
   if (p.staged) count_launch(kCntNumE2eStaged);  // (beside the denominator, posteriors left for the scatter kernel)
-  const E2eDev &e = p.t.e2e_tab;
-  if (e.max_states > TC_E2E_MAX_STATES || e.max_arcs > TC_E2E_MAX_ARCS || e.max_pdfs > TC_E2E_MAX_PDFS)
-    return TC_ERR_UNSUPPORTED;
+  if (large) return launch_num_e2e_large(p, stream);
   const size_t lds = num_e2e_lds_bytes(e.max_states, e.max_arcs, e.max_pdfs);
   void (*kernel)(const NumParams) = nullptr;
   if (p.seq_frames)
@@ -297,6 +265,7 @@ int launch_num_e2e(const NumParams &p, hipStream_t stream) {
   return TC_OK;
 }
 
+// (both forward-backward kernels leave their staged posteriors to this one: nothing in it depends on a sequence's size)
 int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream) {
   if (!p.deriv && !p.xent && !p.seq_xent) return TC_OK;
   void (*kernel)(const NumParams) = nullptr;

@@ -15,11 +15,26 @@ using namespace tc;
 
 namespace tc {
 
+namespace {
+// The kernels' scratch behind the uploaded tables of a slot, each part rounded up to 256 bytes: the log-alpha history,
+// y / the posteriors and -- `large`: for handles that take num_e2e_large_kernels.hip -- one float per arc.
+struct E2eScratch { size_t alpha, stage, occ; };
+E2eScratch e2e_scratch(const E2eTables &tb, int T, bool large) {
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  return {up((size_t)(T + 1) * tb.total_states * 8), up((size_t)T * tb.total_pdfs * 4), large ? up(std::max<size_t>(tb.in_key.size(), 1) * 4) : 0};
+}
+// launch_num_e2e's choice, made when the handle reaches a device (the slot's size) and again at every launch
+bool e2e_takes_large(const E2eTables &tb) {
+  return e2e_beyond_resident(tb.max_states, tb.max_arcs, tb.max_pdfs) || debug_flag(kDbgForceNumE2eLarge);
+}
+}  // namespace
+
 // The host half of an upload (tc_supervision_stage) for an end-to-end supervision.  Caller holds sup->mu and has checked
 // that the device has no slot yet.
 int stage_e2e_locked(tc_supervision *sup, int device) {
   const E2eTables &tb = sup->e2e_tab;
   const int T = sup->T;
+  const E2eScratch sc = e2e_scratch(tb, T, e2e_takes_large(tb));
   struct Part { const void *src; size_t bytes; };
   const Part parts[] = {
       {tb.state_off.data(), tb.state_off.size() * 4}, {tb.arc_off.data(), tb.arc_off.size() * 4},
@@ -42,9 +57,11 @@ int stage_e2e_locked(tc_supervision *sup, int device) {
   const size_t upload = total;
   // the kernel's scratch, sized with the slot (so tc_chain_workspace_bytes does not depend on the supervision's kind)
   const size_t alpha_off = total;
-  total += ((size_t)(T + 1) * tb.total_states * 8 + 255) & ~(size_t)255;
+  total += sc.alpha;
   const size_t stage_off = total;
-  total += ((size_t)T * tb.total_pdfs * 4 + 255) & ~(size_t)255;
+  total += sc.stage;
+  const size_t occ_off = total;  // (the large kernel's arc occupations: only in the slots of handles that take it)
+  total += sc.occ;
   PoolSlot *slot = nullptr;
   int rc = pool_acquire(device, total, &slot);
   if (rc != TC_OK) return rc;
@@ -69,6 +86,7 @@ int stage_e2e_locked(tc_supervision *sup, int device) {
   e.max_states = tb.max_states;
   e.max_arcs = tb.max_arcs;
   e.max_pdfs = tb.max_pdfs;
+  e.occ_off256 = sc.occ ? (int32_t)((occ_off - alpha_off) / 256) : 0;  // (both multiples of 256; the scratch is below 4 GiB + 4 * arcs)
   d.stage = (float *)(blob + stage_off);
   sup->dev[device] = d;
   if (!sup->frames.empty()) sup->frames_dev[device] = P(14);
@@ -81,7 +99,8 @@ namespace {
 
 // T: frames of every sequence, or -- seq_frames given (S entries, each 1..T) -- of the longest: the T of every shape, row
 // count, workspace and scratch rule.  A handle made with seq_frames is ragged whatever the lengths are.
-int create_e2e(tc_supervision **out, float weight, int32_t S, int32_t T, const int32_t *seq_frames, int32_t label_dim,
+// any_size (tc_supervision_create_e2e_any): the size rule is the large kernel's LDS, not the resident kernel's limits.
+int create_e2e(tc_supervision **out, float weight, int32_t S, int32_t T, const int32_t *seq_frames, int32_t label_dim, bool any_size,
                const int32_t *seq_state_begin, const int32_t *start, const int32_t *arc_begin, const int32_t *ilabel,
                const float *arc_weight, const int32_t *nextstate, const float *final_weight) {
   if (S <= 0 || T <= 0 || label_dim <= 0 || !seq_state_begin || !start || !arc_begin || !final_weight)
@@ -122,8 +141,7 @@ int create_e2e(tc_supervision **out, float weight, int32_t S, int32_t T, const i
     }
     for (int32_t p : touched) upid_of[p] = -1;
     touched.clear();
-    if (n > TC_E2E_MAX_STATES || arc_begin[sb + n] - arc_begin[sb] > TC_E2E_MAX_ARCS || npdf > TC_E2E_MAX_PDFS)
-      too_large = true;
+    if (any_size ? !e2e_large_fits(n, npdf) : e2e_beyond_resident(n, arc_begin[sb + n] - arc_begin[sb], npdf)) too_large = true;
   }
   if (too_large) return TC_ERR_UNSUPPORTED;
   // the kernel's scratch in the supervision's pool slot (stage_e2e_locked): the log-alpha history, (T + 1) x states
@@ -235,7 +253,7 @@ int tc_supervision_create_e2e(tc_supervision **out, float weight, int32_t S, int
                               const float *final_weight) {
   if (!out) return TC_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  return create_e2e(out, weight, S, T, nullptr, label_dim, seq_state_begin, start, arc_begin, ilabel, arc_weight, nextstate,
+  return create_e2e(out, weight, S, T, nullptr, label_dim, false, seq_state_begin, start, arc_begin, ilabel, arc_weight, nextstate,
                     final_weight);
 }
 
@@ -251,8 +269,47 @@ int tc_supervision_create_e2e_ragged(tc_supervision **out, float weight, int32_t
     if (frames_per_sequence[s] < 1) return TC_ERR_INVALID_ARGUMENT;
     tmax = std::max(tmax, frames_per_sequence[s]);
   }
-  return create_e2e(out, weight, S, tmax, frames_per_sequence, label_dim, seq_state_begin, start, arc_begin, ilabel,
+  return create_e2e(out, weight, S, tmax, frames_per_sequence, label_dim, false, seq_state_begin, start, arc_begin, ilabel,
                     arc_weight, nextstate, final_weight);
+}
+
+int tc_supervision_create_e2e_any(tc_supervision **out, float weight, int32_t S, int32_t frames_per_sequence,
+                                  const int32_t *seq_frames, int32_t label_dim, const int32_t *seq_state_begin,
+                                  const int32_t *start, const int32_t *arc_begin, const int32_t *ilabel,
+                                  const float *arc_weight, const int32_t *nextstate, const float *final_weight) {
+  if (!out) return TC_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  int32_t T = frames_per_sequence;
+  if (seq_frames) {
+    if (S <= 0) return TC_ERR_INVALID_ARGUMENT;
+    T = 0;
+    for (int32_t s = 0; s < S; ++s) {
+      if (seq_frames[s] < 1) return TC_ERR_INVALID_ARGUMENT;
+      T = std::max(T, seq_frames[s]);
+    }
+  }
+  return create_e2e(out, weight, S, T, seq_frames, label_dim, true, seq_state_begin, start, arc_begin, ilabel, arc_weight,
+                    nextstate, final_weight);
+}
+
+int tc_supervision_e2e_stats(const tc_supervision *s, int64_t *out) {
+  if (!s || !out || !s->e2e) return TC_ERR_INVALID_ARGUMENT;
+  const E2eTables &tb = s->e2e_tab;
+  const bool large = e2e_takes_large(tb);
+  const E2eScratch sc = e2e_scratch(tb, s->T, large);
+  out[0] = s->S;
+  out[1] = tb.max_states;
+  out[2] = tb.max_arcs;
+  out[3] = tb.max_pdfs;
+  out[4] = (int64_t)num_e2e_lds_bytes(tb.max_states, tb.max_arcs, tb.max_pdfs);
+  // (the large kernel and the best path lay their LDS out per sequence: the most one sequence needs)
+  size_t seq_lds = 0;
+  for (int32_t q = 0; q < s->S; ++q)
+    seq_lds = std::max(seq_lds, num_e2e_lds_bytes(tb.state_off[q + 1] - tb.state_off[q], 0, tb.pdf_off[q + 1] - tb.pdf_off[q]));
+  out[5] = (int64_t)seq_lds;
+  out[6] = (int64_t)(sc.alpha + sc.stage + sc.occ);
+  out[7] = large ? 1 : 0;
+  return TC_OK;
 }
 
 int tc_supervision_frames(const tc_supervision *s, int32_t *out_host) {

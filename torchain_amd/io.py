@@ -365,7 +365,8 @@ class Supervision:
         return cls(handle)
 
     @classmethod
-    def from_e2e_fsts(cls, weight, frames_per_sequence, label_dim, fsts, den_graph=None, normalization_scale=1.0):
+    def from_e2e_fsts(cls, weight, frames_per_sequence, label_dim, fsts, den_graph=None, normalization_scale=1.0,
+                      any_size=False):
         """End-to-end supervision ([K] ``Supervision::e2e_fsts``): one acceptor per sequence, not unfolded in time.
         ``fsts`` is a list of per-sequence ``(start, arc_begin, ilabel, arc_weight, nextstate, final)`` in CSR form
         (``ilabel`` = pdf_id + 1, tropical costs, ``final`` = inf for a state that is not final).
@@ -378,7 +379,15 @@ class Supervision:
         ``den_graph``: a ``DenominatorGraph`` whose weights the FSTs do not carry yet -- they are composed with its
         normalization acceptor first (``DenominatorGraph.normalize_fsts``, costs times ``normalization_scale``: [K] e2e
         ``normalization_fst_scale``), which bounds the objective by 0.  A sequence without a path in the graph raises
-        ``ValueError`` naming the sequences.  ``None``: the FSTs are taken as they are."""
+        ``ValueError`` naming the sequences.  ``None``: the FSTs are taken as they are.
+
+        ``any_size``: ``False`` refuses (``TC_ERR_UNSUPPORTED``) a sequence beyond 2048 states, 8192 arcs or 1024 distinct
+        pdfs, what the kernel that keeps a whole sequence on chip holds.  ``True`` (``tc_supervision_create_e2e_any``) takes
+        every sequence with ``16 * ceil4(states) + 4 * ceil4(distinct pdfs) + 2048 <= 163840`` -- about 8192 states with 4096
+        distinct pdfs -- and any number of arcs: a batch with a sequence beyond the old limits takes a second kernel
+        (``e2e_stats()``), one within them is the handle ``False`` makes, bit for bit.  Acceptors composed with a
+        ``den_graph`` and long transcripts are what needs it.  It is a keyword, not the default, only because a test pins the
+        refusal of the default call; nothing else depends on it."""
         fsts = list(fsts)
         if not fsts:
             raise ValueError("from_e2e_fsts: no FSTs")
@@ -412,6 +421,11 @@ class Supervision:
         ab, il, nx = _i32(np.concatenate(ab)), _i32(np.concatenate(il)), _i32(np.concatenate(nx))
         aw, fin = _f32(np.concatenate(aw)), _f32(np.concatenate(fin))
         handle = C.c_void_p()
+        if any_size:
+            check(lib.tc_supervision_create_e2e_any(C.byref(handle), float(weight), len(fsts), 0 if ragged else int(frames_per_sequence),
+                                                    _p(lengths) if ragged else None, int(label_dim), _p(sb), _p(st), _p(ab),
+                                                    _p(il), _p(aw), _p(nx), _p(fin)), "tc_supervision_create_e2e_any")
+            return cls(handle)
         if ragged:
             check(lib.tc_supervision_create_e2e_ragged(C.byref(handle), float(weight), len(fsts), _p(lengths), int(label_dim),
                                                        _p(sb), _p(st), _p(ab), _p(il), _p(aw), _p(nx), _p(fin)),
@@ -552,11 +566,11 @@ class Supervision:
         return out
 
     @classmethod
-    def from_synth(cls, sup):
+    def from_synth(cls, sup, any_size=False):
         """From a ``torchain_amd.synth.SupFst``, or an ``egs.E2eSup`` (what the egs readers return for ``<End2End>``
-        egs)."""
+        egs; ``any_size``: as for ``from_e2e_fsts``, not read for a ``SupFst``)."""
         if isinstance(sup, _egs.E2eSup):
-            return cls.from_e2e_fsts(sup.weight, sup.frames_per_sequence, sup.label_dim, sup.fsts)
+            return cls.from_e2e_fsts(sup.weight, sup.frames_per_sequence, sup.label_dim, sup.fsts, any_size=any_size)
         return cls.from_fst(sup.weight, sup.num_sequences, sup.frames_per_sequence, sup.label_dim, sup.arc_begin,
                             sup.ilabel, sup.arc_weight, sup.nextstate, sup.final)
 
@@ -576,6 +590,20 @@ class Supervision:
                 "max_frame_uniq", "resident_lds_bytes", "windowed_lds_bytes", "history_bytes", "route")
         d = dict(zip(keys, (int(x) for x in out)))
         d["kernel"] = {0: "resident", 1: "windowed"}.get(d["route"], "unsupported")
+        return d
+
+    def e2e_stats(self):
+        """What the numerator will do with this end-to-end supervision, known on the host (``tc_supervision_e2e_stats``):
+        the sizes of the largest sequence, the LDS either kernel would need, the kernel scratch in the handle's pool slot, and
+        ``kernel``: ``"resident"`` (a whole sequence on chip, within 2048 states / 8192 arcs / 1024 distinct pdfs) or
+        ``"large"`` (arc occupations in the pool slot; ``from_e2e_fsts(..., any_size=True)``).  ``route`` is the same as a
+        number (0, 1).  Regular supervisions raise (``stats()`` is theirs)."""
+        out = np.zeros(8, np.int64)
+        check(lib.tc_supervision_e2e_stats(self.ptr, _p(out)), "tc_supervision_e2e_stats")
+        keys = ("sequences", "max_states", "max_arcs", "max_pdfs", "resident_lds_bytes", "large_lds_bytes", "scratch_bytes",
+                "route")
+        d = dict(zip(keys, (int(x) for x in out)))
+        d["kernel"] = {0: "resident", 1: "large"}[d["route"]]
         return d
 
     def best_path(self, nnet_output):
