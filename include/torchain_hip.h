@@ -938,6 +938,9 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *                     -- its pool slot then gets the 4 bytes per arc that kernel needs -- at every numerator launch and by
  *                     tc_supervision_e2e_stats; a launch on a handle staged before the switch was set returns
  *                     TC_ERR_UNSUPPORTED before anything is enqueued or counted)
+ *   "no_full_layout" (1: the fused tied kernel never runs its full-layout twin -- every plane of states and pdfs whole,
+ *                     16-byte rows, no cross-entropy zero rows, no hub states, DESIGN.md 4.1 -- but the general
+ *                     instantiation; same bits.  Read at every such launch)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -966,7 +969,8 @@ int tc_debug_set(const char *key, int value);
  * "den_best_path_streamed_launches" those of them that read the previous frame's scores from the workspace;
  * "xent_log_softmax_launches" = launches of tc_chain_step_log_softmax's two kernels (the row statistics and the gradient
  * pass: 2 a training step, 1 an evaluation step that asks for xent_objf_dev, 0 with the switch off);
- * "num_e2e_large_launches" = end-to-end numerator launches that took num_e2e_large_kernels.hip (counted in "num_launches" too).
+ * "num_e2e_large_launches" = end-to-end numerator launches that took num_e2e_large_kernels.hip (counted in "num_launches" too);
+ * "tied_full_layout_launches" = launches of the fused tied kernel's full-layout twin (counted in "den_launches" too).
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

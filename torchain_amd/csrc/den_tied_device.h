@@ -200,16 +200,23 @@ __device__ __forceinline__ uint32_t hi16w(uint32_t x) {
 // read in the rare commit block is the first thing the register allocator spills, and its reload would sit in
 // the middle of the walk behind a vmcnt(0)), 256 contiguous bytes per wave, twice the rate of ds_write_b32 --
 // and the cursor is one scalar.
-struct RowCommit {
+// SEC = false (schedules without hub states: no secondary rows): the cursor only advances.
+template <bool SEC>
+struct RowCommitT {
   uint32_t row;       // byte address of lane 0's slot of the current row
   uint32_t sec_row;   // ... of the wave's first secondary row
   int left;           // own rows still to come
   __device__ __forceinline__ void commit(float v) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tds_write_addtid_b32 %0" : : "v"(v), "s"(row) : "memory", "m0");
-    --left;
-    row = left == 0 ? sec_row : row + 256u;
+    if constexpr (SEC) {
+      --left;
+      row = left == 0 ? sec_row : row + 256u;
+    } else {
+      row += 256u;
+    }
   }
 };
+typedef RowCommitT<true> RowCommit;
 
 // acc(row) += w * SRC[off] over one chunk.  Row ends are wave-uniform bits of the schedule's mask word m
 // (one word per two chunks; bit u: a row ends with the SECOND cell of pair u, bit 8 + u: with its FIRST
@@ -218,8 +225,8 @@ struct RowCommit {
 // faster per cell but need 14-21 % more cells; issuing the next chunk's gathers ahead of this chunk's sums
 // gains nothing; without any row ends the same loop would run 1.6x faster -- the commits, two taken branches
 // each, are what the rows cost.)
-template <uint32_t SRC, int HALF>
-__device__ __forceinline__ void do_chunk(const Chunk6 &q, uint32_t m, float &acc, RowCommit &rc) {
+template <uint32_t SRC, int HALF, class RC>
+__device__ __forceinline__ void do_chunk(const Chunk6 &q, uint32_t m, float &acc, RC &rc) {
   uint32_t o[8];
   o[0] = lo16(q.oc.x);
   o[1] = hi16(q.oc.x);
@@ -264,9 +271,9 @@ __device__ __forceinline__ uint32_t wave_masks(const ScheduleDev &sc, int wave, 
 // walk (see the kernels).
 constexpr int kWalkEnd = -1000;  // last call of a walk's hook when nothing is resident: whatever is still pending
 
-template <uint32_t SRC, int RES, class AfterChunk>
+template <uint32_t SRC, int RES, class RC, class AfterChunk>
 __device__ __forceinline__ void walk(const Chunk6 (&res)[RES > 0 ? RES : 1], Chunk6 &qa, rsrc_t sbase,
-                                     uint32_t lane16, int nchunks, uint32_t vmask, RowCommit rc,
+                                     uint32_t lane16, int nchunks, uint32_t vmask, RC rc,
                                      AfterChunk after_chunk TC_WALK_ARG) {
   static_assert(RES % 2 == 0, "a mask word covers two chunks");
   // The wave's mask words sit in ONE vector register, word i in lane i (wave_masks() below), and come out through

@@ -51,13 +51,49 @@ __device__ __forceinline__ float vload_f32(const float *ptr) {
 // den_tied_planes.hip).  pb: byte address of exp(y_t); aGM: of gamma_t (u32 fixed point).
 // forward: alpha_t(g) * asum_{t-1} = p(f(g)) * sum_{h != g} w alpha'_{t-1}(h) + p(s(g)) * w_s * alpha'_{t-1}(g); with
 // B_t(g) the two parts are the occupations in frame t-1 of the forward-class arcs into g and of its self-loop
-template <bool GAMMA>
-__device__ __forceinline__ float tied_fwd_state(uint32_t pb, uint32_t aGM, float inv_prev, uint32_t fsx, float wsx, float Fx, float alx,
-                                                float bx, float gs, float &dpart) {
-  const float pf = ldsf(pb + (fsx & 0xffffu)), ps = ldsf(pb + (fsx >> 16));
-  const float sp = ps * (wsx * alx);
-  const float a = fmaf(pf, Fx, sp) * inv_prev;
+// Both formulas are written for one state (V = float, U = uint32_t) or for the four states of a thread's float4 (V = f4,
+// U = u4): the same operations element by element -- the contractions the compiler makes of the one-state form are
+// spelled out as vfma below, so the four-state form cannot round differently -- but the four gathers issue together,
+// the arithmetic packs (v_pk_mul_f32 / v_pk_fma_f32) and the fixed-point adds follow in a row.
+__device__ __forceinline__ float vfma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ f4 vfma(f4 a, f4 b, f4 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ float vmax0(float a) { return fmaxf(a, 0.f); }
+__device__ __forceinline__ f4 vmax0(f4 a) { return f4{fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)}; }
+// LDS addresses base + offset: of one state, formed where the formula names them (as the one-state text always did); of
+// four, base and offsets travel apart and each address is formed at its access -- formed ahead, the four would hold
+// registers across the arithmetic, which the fused kernel does not have
+struct LdsAt4 {
+  uint32_t base;
+  u4 off;
+};
+__device__ __forceinline__ uint32_t lds_at(uint32_t base, uint32_t off) { return base + off; }
+__device__ __forceinline__ LdsAt4 lds_at(uint32_t base, u4 off) { return LdsAt4{base, off}; }
+__device__ __forceinline__ float lds_gather(uint32_t a) { return ldsf(a); }
+__device__ __forceinline__ f4 lds_gather(LdsAt4 a) {
+  return f4{ldsf(a.base + a.off.x), ldsf(a.base + a.off.y), ldsf(a.base + a.off.z), ldsf(a.base + a.off.w)};
+}
+__device__ __forceinline__ void gamma_add_v(uint32_t a, float v) { gamma_add_a(a, v); }
+__device__ __forceinline__ void gamma_add_v(LdsAt4 a, f4 v) {
+  gamma_add_a(a.base + a.off.x, v.x);
+  gamma_add_a(a.base + a.off.y, v.y);
+  gamma_add_a(a.base + a.off.z, v.z);
+  gamma_add_a(a.base + a.off.w, v.w);
+}
+
+// ... before the division by asum_{t-1}; sp: its self-loop part
+template <class V, class U>
+__device__ __forceinline__ V tied_fwd_sum(uint32_t pb, U fsx, V wsx, V Fx, V alx, V &sp) {
+  const V pf = lds_gather(lds_at(pb, fsx & 0xffffu)), ps = lds_gather(lds_at(pb, fsx >> 16));
+  sp = ps * (wsx * alx);
+  return vfma(pf, Fx, sp);
+}
+template <bool GAMMA, class V, class U>
+__device__ __forceinline__ V tied_fwd_state(uint32_t pb, uint32_t aGM, float inv_prev, U fsx, V wsx, V Fx, V alx, V bx, float gs,
+                                            float &dpart) {
+  V sp;
+  const V a = tied_fwd_sum(pb, fsx, wsx, Fx, alx, sp) * inv_prev;
   if constexpr (GAMMA) {
+    static_assert(std::is_same<V, float>::value, "the frames with gamma run the one-state form");
     const float g = gs * bx, spn = sp * inv_prev;
     gamma_add_a(aGM + (fsx >> 16), g * spn);
     gamma_add_a(aGM + (fsx & 0xffffu), g * fmaxf(a - spn, 0.f));
@@ -73,26 +109,37 @@ __device__ __forceinline__ float tied_fwd_state(uint32_t pb, uint32_t aGM, float
 // outputs, profiles/r02_peaky.txt: keeping the un-dashed alpha in the history instead changes nothing; the plane-wise
 // kernel does keep it un-dashed and passes asum_up = 0).
 // The self-loop arc also adds vf_s = w_s * beta_{t+1}(g) * p_t(s(g)) to beta'_t(g) * asum_t (PURE: to U_t(g)).
-template <bool PURE>
-__device__ __forceinline__ float tied_bwd_state(uint32_t pb, uint32_t aGM, uint32_t fsx, float wsx, float bo, float alx, float aupx,
-                                                float cpx, float ax, float inv_as, float asum_up) {
-  const float ps_ws = ldsf(pb + (fsx >> 16)) * wsx;
+template <bool PURE, class V, class U>
+__device__ __forceinline__ V tied_bwd_state(uint32_t pb, uint32_t aGM, U fsx, V wsx, V bo, V alx, V aupx, V cpx, V ax, float inv_as,
+                                            float asum_up) {
+  const V ps_ws = lds_gather(lds_at(pb, fsx >> 16)) * wsx;
   if constexpr (!PURE) {
-    const float selfpart = ps_ws * alx * inv_as;  // self-loop part of alpha_{t+1}(g)
-    const float bos = kGammaScale * bo;            // power-of-two scale: exact
-    gamma_add_a(aGM + (fsx >> 16), bos * selfpart);
+    const V sa = ps_ws * alx;
+    const V selfpart = sa * inv_as;     // self-loop part of alpha_{t+1}(g)
+    const V bos = kGammaScale * bo;     // power-of-two scale: exact
+    gamma_add_v(lds_at(aGM, fsx >> 16), bos * selfpart);
 #ifndef TC_ABL_NOFADD  /* (ablation: what the forward-class half of the gamma adds costs) */
-    gamma_add_a(aGM + (fsx & 0xffffu), bos * fmaxf((aupx - cpx * asum_up) - selfpart, 0.f));
+    // The compiler fuses both products into their subtractions: fma(-inv_as, sa, fma(-asum_up, cpx, aupx)).  The four-state
+    // form says so itself; the one-state form is left to the compiler, which keeps its instruction streams what they were
+    // (spelled out it gives the same instructions in another order: profiles/full_layout/README.md).
+    if constexpr (std::is_same<V, float>::value)
+      gamma_add_v(lds_at(aGM, fsx & 0xffffu), bos * vmax0((aupx - cpx * asum_up) - selfpart));
+    else
+      gamma_add_v(lds_at(aGM, fsx & 0xffffu), bos * vmax0(vfma((V)-inv_as, sa, vfma((V)-asum_up, cpx, aupx))));
 #endif
   }
-  return fmaf(ps_ws, bo, ax);
+  return vfma(ps_ws, bo, ax);
 }
 
 // MITM = false: the fused kernel (per-state tables parked in LDS during the forward phase, phase stamps of the
 // diagnostic builds, normalisers to the workspace after the phase); true: the two roles of den_tied_mitm.hip
 // (gamma region live from frame 0, normalisers to the workspace frame by frame, the B history).
-template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, int RESF, int RESB, bool MITM>
+// FULL (the fused kernel's twin for full layouts, chosen at launch by tied_full_layout(), den_tied_kernel.hip): every plane of states and
+// of pdfs is whole, rows are 16-byte aligned, no cross-entropy zero rows, no hub states, the parked tables fit -- what the
+// general form asks per frame is true at compile time.
+template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, int RESF, int RESB, bool MITM, bool FULL = false>
 struct TiedSeq {
+  static_assert(!(FULL && MITM), "the two-workgroup roles run the general form");
   const DenParams &p;
   const uint32_t tid, lane;
   const int wave, s;
@@ -168,7 +215,15 @@ struct TiedSeq {
         M(meet) {}
 
   // which of its JV float4s of states a thread really has
-  __device__ __forceinline__ bool plane_on(int j) const { return j < planes; }
+  __device__ __forceinline__ bool plane_on(int j) const { return FULL || j < planes; }
+  // ... and whether the float4 of pdfs that starts at pdf i0 exists
+  __device__ __forceinline__ bool pdf_on(int i0) const { return FULL || i0 < Ps; }
+  // 16-byte row accesses (api.cpp: y_vec, d_vec)
+  __device__ __forceinline__ int yvec() const { return FULL ? 1 : p.y_vec; }
+  __device__ __forceinline__ int dvec() const { return FULL ? 1 : p.d_vec; }
+  // the forward phase's per-state tables are parked in LDS
+  __device__ __forceinline__ bool tabs_parked() const { return FULL || tabs_lds; }
+  typedef RowCommitT<!FULL> Rows;
 
   // diagnostic builds (-DTC_PHASE_STAMPS): per-phase cycle totals of a phase's frames, by wave, to p.stamps + base
   __device__ __forceinline__ void stamps_reset() {
@@ -188,24 +243,27 @@ struct TiedSeq {
   // the cross-entropy output's derivative is zero outside the numerator's posteriors: its row of frame t, written where
   // the derivative's row of that frame is (DenParams::xent_zero)
   __device__ __forceinline__ void xent_zero_row(int t) {
-    if (p.xent_zero) {
+    if (!FULL && p.xent_zero) {
       const rsrc_t xrow = make_rsrc(p.xent_zero + ((int64_t)t * S + s) * p.xent_stride, row_bytes);
 #pragma unroll
       for (int v = 0; v < PV; ++v)
-        if (4 * ((int)tid + kThreads * v) < Ps) row_st(xrow, own16 + v * kPlane, p.x_vec, mk4(0.f));
+        if (pdf_on(4 * ((int)tid + kThreads * v))) row_st(xrow, own16 + v * kPlane, p.x_vec, mk4(0.f));
     }
   }
 
   // ---- the per-state formulas (tied_fwd_state / tied_bwd_state above), with this object's scale and regions
-  template <bool GAMMA>
-  __device__ __forceinline__ float fwd_state(uint32_t fsx, float wsx, float Fx, float alx, float bx, float gs, float &dpart) {
+  // (one state at a time, or the four of a float4)
+  template <bool GAMMA, class V, class U>
+  __device__ __forceinline__ V fwd_state(U fsx, V wsx, V Fx, V alx, V bx, float gs, float &dpart) {
     return tied_fwd_state<GAMMA>(kPB, aGM, inv_prev, fsx, wsx, Fx, alx, bx, gs, dpart);
   }
-  template <bool PURE>
-  __device__ __forceinline__ float bwd_state(uint32_t pb, uint32_t fsx, float wsx, float bo, float alx, float aupx, float cpx, float ax,
-                                             float inv_as, float asum_up) {
+  template <bool PURE, class V, class U>
+  __device__ __forceinline__ V bwd_state(uint32_t pb, U fsx, V wsx, V bo, V alx, V aupx, V cpx, V ax, float inv_as, float asum_up) {
     return tied_bwd_state<PURE>(pb, aGM, fsx, wsx, bo, alx, aupx, cpx, ax, inv_as, asum_up);
   }
+  // Which form the per-state passes call: a plane's four states in one statement (the full-layout twin), or state by
+  // state -- the general instantiations, the two-workgroup roles among them, keep the instruction streams they had.
+  static constexpr bool kPlaneMath = FULL;
 
   // ================================================================================================== forward
   // ---- t = 0: alpha_0 = pi, alpha'_0 = pi + leaky*pi*sum(pi)   ([K] AlphaFirstFrame + AlphaDash(0)); then the
@@ -218,11 +276,18 @@ struct TiedSeq {
       pi4[j] = plane_on(j) ? bld4(r_pi, own16, j * kPlane) : mk4(0.f);
       part += hsum(pi4[j]);
     }
-    asum = block_sum_a(part, aRed, wave, lane);
+    // (FULL: the float4 statements below take the sum as a value, not from the member.  With every plane's statement
+    // unconditional the compiler turns the member's read and splat into one 16-byte load of four members, which then stay
+    // in memory for the whole kernel -- as a private array that it moves to LDS, in front of the dynamic block.)
+    float asum_v = 0.f;
+    if constexpr (FULL)
+      asum = asum_v = block_sum_a(part, aRed, wave, lane);
+    else
+      asum = block_sum_a(part, aRed, wave, lane);
 #pragma unroll
     for (int j = 0; j < JV; ++j)
       if (plane_on(j)) {
-        const f4 a = pi4[j] + (leaky * pi4[j]) * asum;
+        const f4 a = pi4[j] + (leaky * pi4[j]) * (FULL ? asum_v : asum);
         lds4_st(kA0 + own16 + j * kPlane, a);
         bst4(make_rsrc(hist, 4u * Hs), own16 + j * kPlane, a);
       }
@@ -232,8 +297,8 @@ struct TiedSeq {
 #pragma unroll
       for (int v = 0; v < PV; ++v) {
         const int i0 = 4 * ((int)tid + kThreads * v);
-        if (i0 < Ps) {
-          const f4 yv = row_ld(yrow, own16 + v * kPlane, p.y_vec);
+        if (pdf_on(i0)) {
+          const f4 yv = row_ld(yrow, own16 + v * kPlane, yvec());
           y2 += hsum(yv * yv);
           lds4_st(kPB + 4u * i0, exp4(yv));
         }
@@ -269,7 +334,7 @@ struct TiedSeq {
     tabs_lds = (p.L.off_red - p.L.off_g) >= 2 * Hs;
     aFS = aGM;
     aWS = aGM + 4u * (uint32_t)Hs;
-    if (tabs_lds) {
+    if (tabs_parked()) {
 #pragma unroll
       for (int j = 0; j < JV; ++j)
         if (plane_on(j)) {
@@ -310,7 +375,7 @@ struct TiedSeq {
     if (t < T) {  // y_t under the arc walk
       const rsrc_t yrow = make_rsrc(p.y + ((int64_t)t * S + s) * p.y_stride, row_bytes);
 #pragma unroll
-      for (int v = 0; v < PV; ++v) yreg[v] = row_ld(yrow, own16 + v * kPlane, p.y_vec);
+      for (int v = 0; v < PV; ++v) yreg[v] = row_ld(yrow, own16 + v * kPlane, yvec());
     }
     float n_t = 1.f;
     if (GAMMA && t < T) n_t = vload_f32(bn + t);  // for c^_{t+1}
@@ -322,7 +387,7 @@ struct TiedSeq {
     // (GAMMA frames: rows above the meeting frame have no reader.)
     age_prio_on(wave);
     bool stored = false;  // (nothing resident: the four wave generations store after streamed pair 0, 1, 2, 3)
-    const RowCommit frc{aACC + 256u * (uint32_t)(K * wave), fsec, K};
+    const Rows frc{aACC + 256u * (uint32_t)(K * wave), fsec, K};
     walk<kA0, RESF>(fres, q0, fbase, lane16, fnch, fmask, frc, [&](int i) {
       if (!kHistFromPass && !GAMMA && t > 1 && !stored && (RESF > 0 ? i == store_slot : (i == kWalkEnd || i == -1 - (wave >> 2)))) {
         stored = true;
@@ -338,7 +403,8 @@ struct TiedSeq {
     TC_STAMP(2)
     // graphs with hub states: the secondary rows of a state are walked by lanes of the wave that owns it
     // (schedule_owner.cpp), and a wave's LDS operations execute in order: no barrier
-    for (int e = ffx0; e < ffx1; ++e) fold_row(p.fwd.fix[e], vrow, aACC, Hs, K);
+    if constexpr (!FULL)
+      for (int e = ffx0; e < ffx1; ++e) fold_row(p.fwd.fix[e], vrow, aACC, Hs, K);
     TC_STAMP(3)
     part = 0.f;
     float dpart = 0.f;
@@ -347,8 +413,8 @@ struct TiedSeq {
 #pragma unroll
     for (int j = 0; j < JV; ++j)
       if (plane_on(j)) {
-        fs[j] = tabs_lds ? lds4u(aFS + own16 + j * kPlane) : bld4u(r_fs, own16, j * kPlane);
-        ws[j] = tabs_lds ? lds4(aWS + own16 + j * kPlane) : bld4(r_ws, own16, j * kPlane);
+        fs[j] = tabs_parked() ? lds4u(aFS + own16 + j * kPlane) : bld4u(r_fs, own16, j * kPlane);
+        ws[j] = tabs_parked() ? lds4(aWS + own16 + j * kPlane) : bld4(r_ws, own16, j * kPlane);
         cpi[j] = bld4(r_pi, own16, j * kPlane);  // pi: first touched behind the reduction, which hides its L2 trip
       }
     const float gs = kGammaScale * chat;
@@ -368,9 +434,17 @@ struct TiedSeq {
 #ifndef TC_ABL_NOHIST
         if (kHistFromPass && !GAMMA) bst4(hist_prev, own16 + j * kPlane, al);
 #endif
-        v4[j] = f4{fwd_state<GAMMA>(fs[j].x, ws[j].x, F.x, al.x, bt[j].x, gs, dpart), fwd_state<GAMMA>(fs[j].y, ws[j].y, F.y, al.y, bt[j].y, gs, dpart),
-                   fwd_state<GAMMA>(fs[j].z, ws[j].z, F.z, al.z, bt[j].z, gs, dpart), fwd_state<GAMMA>(fs[j].w, ws[j].w, F.w, al.w, bt[j].w, gs, dpart)};
-        part += hsum(v4[j]);
+        if constexpr (kPlaneMath && !GAMMA) {
+          f4 sp;
+          const f4 f = tied_fwd_sum(kPB, fs[j], ws[j], F, al, sp);
+          v4[j] = f * inv_prev;
+          // the sum of the four as the compiler contracts it in the state-by-state form: the products by inv_prev of the first
+          // and the third fuse into the additions (x + y) and (z + w) of hsum
+          part += fmaf(f.x, inv_prev, v4[j].y) + fmaf(f.z, inv_prev, v4[j].w);
+        } else
+          v4[j] = f4{fwd_state<GAMMA>(fs[j].x, ws[j].x, F.x, al.x, bt[j].x, gs, dpart), fwd_state<GAMMA>(fs[j].y, ws[j].y, F.y, al.y, bt[j].y, gs, dpart),
+                     fwd_state<GAMMA>(fs[j].z, ws[j].z, F.z, al.z, bt[j].z, gs, dpart), fwd_state<GAMMA>(fs[j].w, ws[j].w, F.w, al.w, bt[j].w, gs, dpart)};
+        if constexpr (!(kPlaneMath && !GAMMA)) part += hsum(v4[j]);
       }
     }
     f4 yp[PV];
@@ -379,7 +453,7 @@ struct TiedSeq {
       // (index clamped, assignment unconditional)
       const rsrc_t yprev = make_rsrc(p.y + ((int64_t)(t - 1) * S + s) * p.y_stride, row_bytes);
 #pragma unroll
-      for (int v = 0; v < PV; ++v) yp[v] = row_ld(yprev, own16 + v * kPlane, p.y_vec);
+      for (int v = 0; v < PV; ++v) yp[v] = row_ld(yprev, own16 + v * kPlane, yvec());
       const rsrc_t brow = make_rsrc(bhist + (int64_t)(t + 1 <= T ? t + 1 : T) * hist_step, 4u * Hs);
 #pragma unroll
       for (int j = 0; j < JV; ++j) bt[j] = bld4(brow, own16, j * kPlane);
@@ -388,13 +462,15 @@ struct TiedSeq {
     } else {
       asum = block_sum_a(part, aRed, wave, lane);
     }
+    float asum_v = 0.f;  // (FULL: a value for the float4 statement below, see forward_begin)
+    if constexpr (FULL) asum_v = asum;
     __builtin_amdgcn_sched_barrier(0);  // (keeps the multiply by leaky, and with it the wait for pi, down here)
     TC_STAMP(4)
     part_tot = 0.f;
 #pragma unroll
     for (int j = 0; j < JV; ++j)
       if (plane_on(j)) {
-        const f4 a = v4[j] + (leaky * cpi[j]) * asum;
+        const f4 a = v4[j] + (leaky * cpi[j]) * (FULL ? asum_v : asum);
         lds4_st(kA0 + own16 + j * kPlane, a);
         part_tot += hsum(a);
       }
@@ -406,12 +482,12 @@ struct TiedSeq {
 #pragma unroll
       for (int v = 0; v < PV; ++v) {
         const int i0 = 4 * ((int)tid + kThreads * v);
-        if (i0 < Ps) {
+        if (pdf_on(i0)) {
           const u4 gu = lds4u(aGM + 4u * i0);
           lds4_st(aGM + 4u * i0, mk4(0.f));
           f4 o = sa * f4{(float)gu.x, (float)gu.y, (float)gu.z, (float)gu.w} - p.l2_scale * yp[v];
-          if (ACCUM) o += row_ld(drow, own16 + v * kPlane, p.d_vec);
-          row_st(drow, own16 + v * kPlane, p.d_vec, o);
+          if (ACCUM) o += row_ld(drow, own16 + v * kPlane, dvec());
+          row_st(drow, own16 + v * kPlane, dvec(), o);
         }
       }
       xent_zero_row(t - 1);
@@ -421,7 +497,7 @@ struct TiedSeq {
 #pragma unroll
       for (int v = 0; v < PV; ++v) {
         const int i0 = 4 * ((int)tid + kThreads * v);
-        if (i0 < Ps) {
+        if (pdf_on(i0)) {
           y2 += hsum(yreg[v] * yreg[v]);
           lds4_st(kPB + 4u * i0, exp4(yreg[v]));
         }
@@ -441,7 +517,7 @@ struct TiedSeq {
 #pragma unroll
     for (int v = 0; v < PV; ++v) {
       const int i0 = 4 * ((int)tid + kThreads * v);
-      if (i0 < Ps) lds4_st(aGM + 4u * i0, mk4(0.f));
+      if (pdf_on(i0)) lds4_st(aGM + 4u * i0, mk4(0.f));
     }
   }
 
@@ -528,8 +604,8 @@ struct TiedSeq {
 #pragma unroll
       for (int v = 0; v < PV; ++v) {
         const int i0 = 4 * ((int)tid + kThreads * v);
-        ycur[v] = row_ld(yrow, own16 + v * kPlane, p.y_vec);
-        if (i0 < Ps) {
+        ycur[v] = row_ld(yrow, own16 + v * kPlane, yvec());
+        if (pdf_on(i0)) {
           lds4_st(pb_cur + 4u * i0, exp4(ycur[v]));
           lds4_st(aGM + 4u * i0, mk4(0.f));
         }
@@ -608,7 +684,7 @@ struct TiedSeq {
 #ifdef TC_ABL_NOY2
       for (int v = 0; v < PV; ++v) ynext[v] = mk4(0.25f) * (float)t;  // (ablation: what the backward pass's second read of y costs)
 #else
-      for (int v = 0; v < PV; ++v) ynext[v] = row_ld(yrow, own16 + v * kPlane, p.y_vec);
+      for (int v = 0; v < PV; ++v) ynext[v] = row_ld(yrow, own16 + v * kPlane, yvec());
 #endif
       if (!PURE && !kHistByDma) {  // (kHistByDma: the row is in aAL, or on its way there)
         const rsrc_t hist_t = make_rsrc(hist + (int64_t)t * hist_step, 4u * Hs);
@@ -632,7 +708,7 @@ struct TiedSeq {
     // profiles/store_placement/README.md)
     age_prio_on(wave);
     bool dstored = false;
-    const RowCommit brc{aACC + 256u * (uint32_t)(K * wave), bsec, K};
+    const Rows brc{aACC + 256u * (uint32_t)(K * wave), bsec, K};
     // (PURE: the history row of B_{t+1}, still in this thread's registers, leaves the same way; row T went out in
     // backward_begin, the last pure frame's row goes out in backward_store_row)
     walk<kA0, RESB>(bres, q0, bbase, lane16, bnch, bmask, brc, [&](int i) {
@@ -649,7 +725,7 @@ struct TiedSeq {
           const rsrc_t drow = make_rsrc(p.deriv + ((int64_t)(t + 1) * S + s) * p.deriv_stride, row_bytes);
 #pragma unroll
           for (int v = 0; v < PV; ++v)
-            if (4 * ((int)tid + kThreads * v) < Ps) row_st(drow, own16 + v * kPlane, p.d_vec, lds4(pb_next + own16 + v * kPlane));
+            if (pdf_on(4 * ((int)tid + kThreads * v))) row_st(drow, own16 + v * kPlane, dvec(), lds4(pb_next + own16 + v * kPlane));
           xent_zero_row(t + 1);
         }
       }
@@ -661,11 +737,12 @@ struct TiedSeq {
 #pragma unroll
       for (int v = 0; v < PV; ++v) {
         const int i0 = 4 * ((int)tid + kThreads * v);
-        if (i0 < Ps) lds4_st(pb_next + 4u * i0, exp4(ynext[v]));
+        if (pdf_on(i0)) lds4_st(pb_next + 4u * i0, exp4(ynext[v]));
       }
     }
     TC_STAMP(2)
-    for (int e = bfx0; e < bfx1; ++e) fold_row(p.bwd.fix[e], vrow, aACC, Hs, K);  // (no barrier: as in the forward pass)
+    if constexpr (!FULL)
+      for (int e = bfx0; e < bfx1; ++e) fold_row(p.bwd.fix[e], vrow, aACC, Hs, K);  // (no barrier: as in the forward pass)
     TC_STAMP(3)
     f4 b4[JV];
     uint32_t fpk[JV][2];  // forward-pdf offsets of the owned states, kept for the Y update below
@@ -707,10 +784,14 @@ struct TiedSeq {
         const f4 al = (!PURE && kHistByDma) ? lds4(aAL + own16 + j * kPlane) : areg[j];
         const f4 aup = (!PURE && kHistByDma) ? areg[j] : (!PURE && ALPHA_LDS) ? lds4(aAL + own16 + j * kPlane) : aup_g;
         if (!PURE && kHistByDma) areg[j] = al;
-        a.x = bwd_state<PURE>(pb_cur, fs.x, ws.x, bown[j].x, al.x, aup.x, cp.x, a.x, inv_as, asum_up);
-        a.y = bwd_state<PURE>(pb_cur, fs.y, ws.y, bown[j].y, al.y, aup.y, cp.y, a.y, inv_as, asum_up);
-        a.z = bwd_state<PURE>(pb_cur, fs.z, ws.z, bown[j].z, al.z, aup.z, cp.z, a.z, inv_as, asum_up);
-        a.w = bwd_state<PURE>(pb_cur, fs.w, ws.w, bown[j].w, al.w, aup.w, cp.w, a.w, inv_as, asum_up);
+        if constexpr (kPlaneMath) {
+          a = bwd_state<PURE>(pb_cur, fs, ws, bown[j], al, aup, cp, a, inv_as, asum_up);
+        } else {
+          a.x = bwd_state<PURE>(pb_cur, fs.x, ws.x, bown[j].x, al.x, aup.x, cp.x, a.x, inv_as, asum_up);
+          a.y = bwd_state<PURE>(pb_cur, fs.y, ws.y, bown[j].y, al.y, aup.y, cp.y, a.y, inv_as, asum_up);
+          a.z = bwd_state<PURE>(pb_cur, fs.z, ws.z, bown[j].z, al.z, aup.z, cp.z, a.z, inv_as, asum_up);
+          a.w = bwd_state<PURE>(pb_cur, fs.w, ws.w, bown[j].w, al.w, aup.w, cp.w, a.w, inv_as, asum_up);
+        }
         b4[j] = PURE ? a : a * inv_as;  // [K] * inv_arbitrary_scale
         fpk[j][0] = (fs.x & 0xffffu) | (fs.y << 16);
         fpk[j][1] = (fs.z & 0xffffu) | (fs.w << 16);
@@ -747,20 +828,20 @@ struct TiedSeq {
 #pragma unroll
       for (int v = 0; v < PV; ++v) {
         const int i0 = 4 * ((int)tid + kThreads * v);
-        if (i0 < Ps) {
+        if (pdf_on(i0)) {
           const u4 gu = lds4u(aGM + 4u * i0);
           lds4_st(aGM + 4u * i0, mk4(0.f));
           const f4 g = f4{(float)gu.x, (float)gu.y, (float)gu.z, (float)gu.w} * kGammaInvScale;
           if (t == 0) part_g += hsum(g);
           f4 o = p.deriv_weight * g - p.l2_scale * ycur[v];
-          if (ACCUM) o += row_ld(drow, own16 + v * kPlane, p.d_vec);
+          if (ACCUM) o += row_ld(drow, own16 + v * kPlane, dvec());
 #ifndef TC_ABL_NODERIV
           if (kDeferDeriv && t > 0)
             lds4_st(pb_cur + 4u * i0, o);  // (and the cross-entropy output's zero row with it, under the next walk)
           else
-            row_st(drow, own16 + v * kPlane, p.d_vec, o);
+            row_st(drow, own16 + v * kPlane, dvec(), o);
 #else
-          if (o.x == 123.456f) row_st(drow, own16 + v * kPlane, p.d_vec, o);
+          if (o.x == 123.456f) row_st(drow, own16 + v * kPlane, dvec(), o);
 #endif
         }
       }
@@ -783,7 +864,7 @@ struct TiedSeq {
 #pragma unroll
       for (int v = 0; v < PV; ++v) {
         const int i0 = 4 * ((int)tid + kThreads * v);
-        if (i0 < Ps) lds4_st(kPB + 4u * i0, exp4(ynext[v]));
+        if (pdf_on(i0)) lds4_st(kPB + 4u * i0, exp4(ynext[v]));
       }
       __syncthreads();
     }

@@ -29,9 +29,11 @@ namespace {
 // (the frames themselves: den_tied_frames.h, shared with den_tied_mitm.hip)
 // RAGGED (DenParams::seq_frames): the sequence runs its own T_s frames (launch_den_mode passes no fwd_norm then; batches
 // of 8 sequences up to half the chip take den_tied_mitm.hip's RAGGED instantiation instead)
-template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, bool WANT_DERIV, int RESF, int RESB, bool RAGGED = false>
+// FULL: the twin for full layouts (tied_full_layout below; den_tied_frames.h says what it leaves out)
+template <int JV, int PV, bool ALPHA_LDS, bool ACCUM, bool WANT_DERIV, int RESF, int RESB, bool RAGGED = false, bool FULL = false>
 __global__ __launch_bounds__(kThreads) void den_tied_kernel(const DenParams p) {
-  TiedSeq<JV, PV, ALPHA_LDS, ACCUM, RESF, RESB, false> q(p, (int)blockIdx.x, 0, RAGGED ? ragged_frames(p.seq_frames(), (int)blockIdx.x, p.T) : 0);
+  static_assert(!(FULL && RAGGED), "ragged batches run the general form");
+  TiedSeq<JV, PV, ALPHA_LDS, ACCUM, RESF, RESB, false, FULL> q(p, (int)blockIdx.x, 0, RAGGED ? ragged_frames(p.seq_frames(), (int)blockIdx.x, p.T) : 0);
   const int T = q.T;
   // ---- forward: alpha'_0, frames 1..T, total probability
   q.forward_begin();
@@ -81,6 +83,14 @@ int launch_jp(const DenParams &p, int accumulate, size_t lds_bytes, hipStream_t 
     k = al ? den_tied_kernel<JV, PV, true, true, true, RF, RB, RAGGED> : den_tied_kernel<JV, PV, false, true, true, RF, RB, RAGGED>;
   else
     k = al ? den_tied_kernel<JV, PV, true, false, true, RF, RB, RAGGED> : den_tied_kernel<JV, PV, false, false, true, RF, RB, RAGGED>;
+  // The full-layout twin exists for 8 states per thread and one plane of pdfs (the C2 / C3 class); the other layout
+  // classes would each add two instantiations of the largest kernel of the library.
+  if constexpr (JV == kJvSmall && PV == kPvSmall && !RAGGED) {
+    if (tied_full_layout(p)) {
+      k = accumulate ? den_tied_kernel<JV, PV, true, true, true, RF, RB, false, true> : den_tied_kernel<JV, PV, true, false, true, RF, RB, false, true>;
+      count_launch(kCntTiedFullLayout);
+    }
+  }
   TC_HIP_CHECK(allow_dynamic_lds((const void *)k, lds_bytes));
   hipLaunchKernelGGL(k, dim3(p.S), dim3(kThreads), lds_bytes, stream, p);
   TC_HIP_CHECK(hipGetLastError());
@@ -90,6 +100,29 @@ int launch_jp(const DenParams &p, int accumulate, size_t lds_bytes, hipStream_t 
 }  // namespace
 
 static_assert(TC_RESF <= kTiedMinChunks && TC_RESB <= kTiedMinChunks, "the resident prefix must exist in every wave's stream");
+
+// Whether a launch takes the full-layout twin: everything TiedSeq<..., FULL> takes for granted, checked here.
+//   * 8 states per thread and one plane of pdfs, every float4 of both in use (8192 positions, 4096 pdfs);
+//   * the roomy layout with room for the two parked per-state tables;
+//   * rows of y and of the derivative that take 16-byte accesses;
+//   * no cross-entropy output to zero (so its rows' alignment, x_vec, has no reader), no hub states in either schedule,
+//     a uniform batch, a derivative asked for;
+//   * not a diagnostic build: the phase stamps and the ablations are statements about the general form.
+bool tied_full_layout(const DenParams &p) {
+#if defined(TC_PHASE_STAMPS) || defined(TC_ABL_NOATOM) || defined(TC_ABL_NODERIV) || defined(TC_ABL_NOFADD) || defined(TC_ABL_NOGAM) || \
+    defined(TC_ABL_NOGATHER) || defined(TC_ABL_NOHIST) || defined(TC_ABL_NOHISTLOAD) || defined(TC_ABL_NOPARK) ||                      \
+    defined(TC_ABL_NOSTREAM) || defined(TC_ABL_NOWALKSTORE) || defined(TC_ABL_NOY2) || defined(TC_NO_BWD_DEFER) || defined(TC_NO_HIST_DMA)
+  return false;
+#else
+  if (debug_flag(kDbgNoFullLayout)) return false;
+  if (p.L.JV != kJvSmall || p.L.PV != kPvSmall || p.L.planewise) return false;
+  if (p.L.Hs != 4 * kThreads * kJvSmall || p.L.Ps != 4 * kThreads * kPvSmall || p.P != p.L.Ps) return false;
+  if (!p.L.alpha_in_lds || p.L.off_red - p.L.off_g < 2 * p.L.Hs) return false;
+  if (!p.deriv || !p.y_vec || !p.d_vec || p.xent_zero) return false;
+  if (p.fwd.nfix != 0 || p.bwd.nfix != 0) return false;
+  return p.seq_frames() == nullptr;
+#endif
+}
 
 int launch_den_tied(const DenParams &p, int accumulate, hipStream_t stream) {
   const size_t lds = (size_t)layout_lds_bytes(p.L, p.T);
