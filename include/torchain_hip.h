@@ -760,6 +760,73 @@ int tc_den_best_path(tc_den_graph *g, int32_t S, const void *nnet_output, int dt
                      int32_t max_frames, int32_t *pdf_dev /* [S * T] */, int32_t *state_dev /* nullable, [S * (T + 1)] */,
                      double *score_dev /* [S] */, void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* The expected frame accuracy of the DENOMINATOR graph's paths against a frame-level reference, and its gradient: the
+ * lattice-free sMBR criterion (Kanda et al. 2018), the step [K] takes after chain training with a decoder and lattices
+ * (run_discriminative.sh) and this library takes on den.fst alone.  Per sequence
+ *     E_s[A] = sum_paths P(path | y_s) * sum_t a_t(pdf_t(path))
+ * under the denominator's own model -- p_t(j) = exp(clamp(y_t(j), +-30)), the graph's initial probabilities, the leaky-HMM
+ * coefficient, every state final -- with a_t(j) = 1 where 0 <= ref_t < P and class(j) == class(ref_t), else 0.
+ *   S, nnet_output, num_rows, num_cols, row_stride : the 2-D float32 matrix (T*S, P), row t*S + s, rows row_stride floats
+ *                 apart; num_rows == S * max_frames, num_cols == the graph's pdfs.  (The C entries take this layout only.)
+ *   seq_frames_dev : device int32[S], the sequences' lengths T_s (held to 1 .. max_frames), or NULL: max_frames each.
+ *   ref_dev     : device int32[S * T], entry s * T + t the 0-based reference pdf of frame t (the layout tc_den_best_path
+ *                 and tc_supervision_best_path write).  A value outside 0 .. P-1 in a valid frame: the frame scores
+ *                 nothing (silence, say).  Padding entries are not read.
+ *   class_dev   : NULL (identity: state-level sMBR), or device int32[P], a map of the pdfs to classes of any values -- a
+ *                 pdf -> phone map gives an MPFE-style criterion.
+ * tc_den_expected_accuracy: the value.
+ *   gamma       : device float32 (T*S, P), rows gamma_stride floats apart: scratch that holds, on return, the DENOMINATOR
+ *                 POSTERIORS gamma_t(j) of the batch -- a by-product callers may use.  The entry runs
+ *                 tc_den_forward_backward (with lengths: tc_den_forward_backward_ragged) into it, deriv_weight 1, l2_scale
+ *                 0, accumulate 0, by whatever kernel the graph's class takes; a ragged batch's padding rows are +0.
+ *   frame_acc_dev : device float32[S * T], entry s * T + t the frame's expected accuracy m_t = sum_j gamma_t(j) a_t(j),
+ *                 summed in double (a lane's pdfs in order, then a butterfly over the wave); 0 in padding frames.
+ *   acc_dev     : device double[S], E_s = sum_t m_t, a double sum of those float32 values in frame order.
+ *   One further launch (den_accuracy_kernels.hip), one workgroup per sequence.  It also looks at every nnet_output element
+ *   of the sequence's valid frames, as tc_den_best_path does: a sequence with a NaN or +-inf there gets acc NaN (and NaN in
+ *   its valid frames of frame_acc_dev); the other sequences keep their bits.
+ *   Workspace: tc_den_expected_accuracy_workspace_bytes == tc_chain_workspace_bytes.
+ *   TC_ERR_UNSUPPORTED, passed through: lengths on a graph of the streamed path.
+ * tc_den_expected_accuracy_grad: grad[t*S + s, :] = seq_scale[s] * dE_s / dy_t, overwritten, one store per element
+ * (seq_scale_dev: NULL or device float32[S]; NULL: 1).  Padding rows, and every row of a sequence with a NaN or +-inf in its
+ * valid frames, are exactly +0.  Every row sums to 0 up to rounding.
+ *   frame_acc_dev : what tc_den_expected_accuracy left.  The kernel subtracts m_t from a_t: the gradient does not depend
+ *                 on these constants, its float32 arithmetic does (without them it is the small difference of terms of
+ *                 the size of E[A]).
+ *   One launch (den_accuracy_kernels.hip, whose header states the recursions), one workgroup per sequence: a forward pass
+ *   that carries the accuracy mass beside alpha, a backward pass that carries it beside beta and forms the gradient pdf by
+ *   pdf, over three CSRs of the FST's own arcs (by destination, by source, by pdf; built from the graph on the first call
+ *   per device, in device memory of their own: the tables of the training step are not touched, and a step on the graph
+ *   gives the same bits before and after).  Vectors are float32, every sum over arcs or states is a double.  No atomics and
+ *   fixed orders: a sequence's bits depend neither on the call, nor on its place in the batch, nor on the other sequences.
+ *   Workspace (tc_den_expected_accuracy_grad_workspace_bytes), per sequence, Hs and Ps the graph's states and pdfs rounded
+ *   up to 4: alpha'_t and A'_t of every frame, 2 * (T + 1) * Hs floats; 1 / asum_t, T + 1 floats rounded up to 4; and
+ *   4 * Hs + 2 * Ps floats for the per-frame vectors; the whole rounded up to 256 bytes, 16-byte aligned.
+ *   The per-frame vectors -- four by state, two by pdf -- stay in LDS while 16 * Hs + 8 * Ps + 1024 <= 163840 bytes (for
+ *   instance 8192 states with 3968 pdfs); beyond that the same code keeps them in the workspace, with the same bits
+ *   ("den_accuracy_grad_streamed_launches" counts those launches, tc_debug_set("force_den_accuracy_streamed", 1) sends
+ *   every graph that way).  Graphs of every size, lengths on every graph.
+ * Both: TC_ERR_INVALID_ARGUMENT, before any device call: a null pointer (class_dev, seq_frames_dev and seq_scale_dev may
+ * be null), S or max_frames <= 0, num_rows != S * max_frames, num_cols that are not the graph's, a row, gamma or grad stride
+ * below num_cols, a leaky-HMM coefficient that is negative or not finite, pointers that are not aligned to their elements.
+ * TC_ERR_WORKSPACE: a workspace that is null, too small or not 16-byte aligned.  Asynchronous on `stream`; nothing is
+ * allocated after the graph's first calls on the device.  tc_debug_counter("den_accuracy_launches") and
+ * ("den_accuracy_grad_launches") count the calls that launched their kernel. */
+int64_t tc_den_expected_accuracy_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T);
+int tc_den_expected_accuracy(tc_den_graph *g, int32_t S, const float *nnet_output, int64_t num_rows, int32_t num_cols,
+                             int64_t row_stride, const int32_t *seq_frames_dev /* nullable: T each */, int32_t max_frames,
+                             float leaky_hmm_coefficient, const int32_t *ref_dev /* [S * T] */,
+                             const int32_t *class_dev /* nullable, [P] */, float *gamma, int64_t gamma_stride,
+                             float *frame_acc_dev /* [S * T] */, double *acc_dev /* [S] */, void *workspace,
+                             int64_t workspace_bytes, int device, void *stream);
+int64_t tc_den_expected_accuracy_grad_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T);
+int tc_den_expected_accuracy_grad(tc_den_graph *g, int32_t S, const float *nnet_output, int64_t num_rows, int32_t num_cols,
+                                  int64_t row_stride, const int32_t *seq_frames_dev /* nullable: T each */,
+                                  int32_t max_frames, float leaky_hmm_coefficient, const int32_t *ref_dev /* [S * T] */,
+                                  const int32_t *class_dev /* nullable, [P] */, const float *frame_acc_dev /* [S * T] */,
+                                  const float *seq_scale_dev /* nullable, [S]: 1 */, float *grad, int64_t grad_stride,
+                                  void *workspace, int64_t workspace_bytes, int device, void *stream);
+
 /* ---- the denominator graph's weights on caller-built supervisions ------------------------------------------------------
  * Every supervision Kaldi writes into an eg has been composed with the normalization FST of den.fst ([K]
  * AddWeightToSupervisionFst, DenominatorGraph::GetNormalizationFst; the end-to-end egs: --normalization-fst-scale), which
@@ -941,6 +1008,8 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *   "no_full_layout" (1: the fused tied kernel never runs its full-layout twin -- every plane of states and pdfs whole,
  *                     16-byte rows, no cross-entropy zero rows, no hub states, DESIGN.md 4.1 -- but the general
  *                     instantiation; same bits.  Read at every such launch)
+ *   "force_den_accuracy_streamed" (1: tc_den_expected_accuracy_grad keeps its per-frame vectors in the workspace for every
+ *                     graph, as it does for those beyond its LDS form; same bits.  Read at every such call)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -970,7 +1039,11 @@ int tc_debug_set(const char *key, int value);
  * "xent_log_softmax_launches" = launches of tc_chain_step_log_softmax's two kernels (the row statistics and the gradient
  * pass: 2 a training step, 1 an evaluation step that asks for xent_objf_dev, 0 with the switch off);
  * "num_e2e_large_launches" = end-to-end numerator launches that took num_e2e_large_kernels.hip (counted in "num_launches" too);
- * "tied_full_layout_launches" = launches of the fused tied kernel's full-layout twin (counted in "den_launches" too).
+ * "tied_full_layout_launches" = launches of the fused tied kernel's full-layout twin (counted in "den_launches" too);
+ * "den_accuracy_launches" = tc_den_expected_accuracy calls that launched their row kernel (the denominator launch in front of
+ * it counts in "den_launches" and "den_backward_launches" as any other), "den_accuracy_grad_launches" =
+ * tc_den_expected_accuracy_grad calls that launched their kernel, and "den_accuracy_grad_streamed_launches" those of them
+ * that kept the per-frame vectors in the workspace.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -207,6 +207,16 @@ def _load():
     L.tc_den_best_path_workspace_bytes.argtypes = [vp, i32, i32]
     L.tc_den_best_path.restype = C.c_int
     L.tc_den_best_path.argtypes = [vp, i32, vp, C.c_int, C.c_int, i64, i32, i64, vp, i32, vp, vp, vp, vp, i64, C.c_int, vp]
+    L.tc_den_expected_accuracy_workspace_bytes.restype = i64
+    L.tc_den_expected_accuracy_workspace_bytes.argtypes = [vp, i32, i32]
+    L.tc_den_expected_accuracy.restype = C.c_int
+    L.tc_den_expected_accuracy.argtypes = [vp, i32, vp, i64, i32, i64, vp, i32, f32, vp, vp, vp, i64, vp, vp, vp, i64,
+                                           C.c_int, vp]
+    L.tc_den_expected_accuracy_grad_workspace_bytes.restype = i64
+    L.tc_den_expected_accuracy_grad_workspace_bytes.argtypes = [vp, i32, i32]
+    L.tc_den_expected_accuracy_grad.restype = C.c_int
+    L.tc_den_expected_accuracy_grad.argtypes = [vp, i32, vp, i64, i32, i64, vp, i32, f32, vp, vp, vp, vp, vp, i64, vp, i64,
+                                                C.c_int, vp]
     L.tc_den_graph_arcs.restype = C.c_int
     L.tc_den_graph_arcs.argtypes = [vp, vp, vp, vp, vp]
     L.tc_den_compose.restype = C.c_int

@@ -4,6 +4,7 @@
 // the kernels on the caller's stream.  No host synchronisation; no allocation once the per-device supervision
 // pool (supervision.cpp) is warm.
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <string>
 #include <cstring>
@@ -546,6 +547,99 @@ int tc_den_best_path(tc_den_graph *g, int32_t S, const void *y, int dtype, int l
   p.score_out = score_dev;
   p.resident = den_best_resident(g->H) && !debug_flag(kDbgForceDenBestStreamed);
   return launch_den_best_path(p, (hipStream_t)stream_v);
+}
+
+int64_t tc_den_expected_accuracy_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {
+  return tc_chain_workspace_bytes(g, S, T);
+}
+
+int64_t tc_den_expected_accuracy_grad_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {
+  if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
+  return den_acc_grad_workspace_bytes(g->H, g->P, S, T);
+}
+
+// what the two entries check alike, in front of any device call
+static int den_accuracy_args(const tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                             const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
+                             const int32_t *class_dev, const float *frame_acc_dev, const void *out, int64_t out_stride) {
+  if (!g || !y || !ref_dev || !frame_acc_dev || !out || S <= 0 || max_frames <= 0) return TC_ERR_INVALID_ARGUMENT;
+  if (rows != (int64_t)S * max_frames || cols != g->P || y_stride < cols || out_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!(leaky >= 0.0f) || !(leaky <= FLT_MAX)) return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)seq_frames_dev | (uintptr_t)ref_dev | (uintptr_t)class_dev | (uintptr_t)frame_acc_dev | (uintptr_t)y) & 3) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  return TC_OK;
+}
+
+int tc_den_expected_accuracy(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                             const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
+                             const int32_t *class_dev, float *gamma, int64_t gamma_stride, float *frame_acc_dev,
+                             double *acc_dev, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  int rc = den_accuracy_args(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev,
+                             frame_acc_dev, gamma, gamma_stride);
+  if (rc != TC_OK) return rc;
+  if (!acc_dev || ((uintptr_t)acc_dev & 7) != 0 || ((uintptr_t)gamma & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
+  if (!workspace || tc_chain_workspace_bytes(g, S, max_frames) > workspace_bytes || !aligned16(workspace))
+    return TC_ERR_WORKSPACE;
+  // the denominator posteriors, by whatever kernel the graph's class takes
+  rc = seq_frames_dev ? tc_den_forward_backward_ragged(g, S, y, rows, cols, y_stride, leaky, 1.0f, 0.0f, 0, gamma, gamma_stride,
+                                                       seq_frames_dev, max_frames, nullptr, nullptr, workspace,
+                                                       workspace_bytes, device, stream_v)
+                      : tc_den_forward_backward(g, S, y, rows, cols, y_stride, leaky, 1.0f, 0.0f, 0, gamma, gamma_stride,
+                                                nullptr, nullptr, workspace, workspace_bytes, device, stream_v);
+  if (rc != TC_OK) return rc;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  DenAccRowParams p;
+  p.y = y;
+  p.gamma = gamma;
+  p.y_stride = y_stride;
+  p.gamma_stride = gamma_stride;
+  p.S = S;
+  p.T = max_frames;
+  p.P = g->P;
+  p.seq_frames = seq_frames_dev;
+  p.ref = ref_dev;
+  p.pdf_class = class_dev;
+  p.frame_acc = frame_acc_dev;
+  p.acc = acc_dev;
+  return launch_den_accuracy_rows(p, (hipStream_t)stream_v);
+}
+
+int tc_den_expected_accuracy_grad(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                                  const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
+                                  const int32_t *class_dev, const float *frame_acc_dev, const float *seq_scale_dev,
+                                  float *grad, int64_t grad_stride, void *workspace, int64_t workspace_bytes, int device,
+                                  void *stream_v) {
+  int rc = den_accuracy_args(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev,
+                             frame_acc_dev, grad, grad_stride);
+  if (rc != TC_OK) return rc;
+  if ((((uintptr_t)grad | (uintptr_t)seq_scale_dev) & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
+  if (!workspace || den_acc_grad_workspace_bytes(g->H, g->P, S, max_frames) > workspace_bytes || !aligned16(workspace))
+    return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  DenAccGradParams p;
+  rc = den_acc_tables(g, device, &p.t);
+  if (rc != TC_OK) return rc;
+  p.y = y;
+  p.y_stride = y_stride;
+  p.S = S;
+  p.T = max_frames;
+  p.H = g->H;
+  p.P = g->P;
+  p.Hs = (int)den_acc_round4(g->H);
+  p.Ps = (int)den_acc_round4(g->P);
+  p.leaky = leaky;
+  p.seq_frames = seq_frames_dev;
+  p.ref = ref_dev;
+  p.pdf_class = class_dev;
+  p.frame_acc = frame_acc_dev;
+  p.seq_scale = seq_scale_dev;
+  p.grad = grad;
+  p.grad_stride = grad_stride;
+  p.workspace = (char *)workspace;
+  p.resident = den_acc_resident(g->H, g->P) && !debug_flag(kDbgForceDenAccStreamed);
+  return launch_den_accuracy_grad(p, (hipStream_t)stream_v);
 }
 
 }  // extern "C"

@@ -206,6 +206,63 @@ inline int64_t den_best_workspace_bytes(int H, int S, int T) {
   return (((int64_t)S * (T + 1) * den_best_row_floats(H) * 4) + 255) & ~(int64_t)255;
 }
 
+// The expected frame accuracy over the graph and its gradient (tc_den_expected_accuracy*, den_accuracy_kernels.hip): the
+// FST's own states and arcs again, as three CSRs of the same A arcs -- by destination state (forward pass), by source
+// state (backward pass) and by pdf (gradient) -- each in the order of the graph's arc list within a row.  `other` is the
+// arc's source state in `in`, its destination in `out`; `pdf_arcs` carries both.  w is the handle's float32 probability.
+struct DenAccArc {
+  int32_t other, pdf;
+  float w;
+};
+struct DenAccPdfArc {
+  int32_t src, dst;
+  float w;
+};
+struct DenAccDev {
+  const int32_t *in_begin = nullptr, *out_begin = nullptr;  // [H + 1]
+  const int32_t *pdf_begin = nullptr;                       // [P + 1]
+  const DenAccArc *in_arcs = nullptr, *out_arcs = nullptr;  // [A]
+  const DenAccPdfArc *pdf_arcs = nullptr;                   // [A]
+  const float *pi = nullptr;                                // [H]
+  void *blob = nullptr;
+};
+// tc_den_expected_accuracy's row kernel: m_t = sum_j gamma_t(j) a_t(j), E_s = sum_t m_t, and the scan of y
+struct DenAccRowParams {
+  const float *y, *gamma;
+  int64_t y_stride, gamma_stride;
+  int S, T, P;
+  const int32_t *seq_frames, *ref, *pdf_class;
+  float *frame_acc;  // [S][T]
+  double *acc;       // [S]
+};
+struct DenAccGradParams {
+  DenAccDev t;
+  const float *y;
+  int64_t y_stride;
+  int S, T, H, P, Hs, Ps;  // T: the longest sequence's frames; Hs, Ps: H, P rounded up to 4
+  float leaky;
+  const int32_t *seq_frames, *ref, *pdf_class;  // [S] nullable, [S][T], [P] nullable
+  const float *frame_acc;                       // [S][T]: the centring constants m_t
+  const float *seq_scale;                       // [S] nullable: 1
+  float *grad;
+  int64_t grad_stride;
+  char *workspace;  // den_acc_grad_workspace_bytes: per sequence [alpha' | A' | 1 / asum | streamed vectors]
+  int resident;     // the per-frame vectors in LDS (den_acc_resident), else in the workspace
+};
+__host__ __device__ inline int64_t den_acc_round4(int n) { return ((int64_t)n + 3) & ~(int64_t)3; }
+// floats of the per-frame vectors: two pairs of state vectors (forward: alpha, A and alpha', A'; backward: beta, B of the
+// two frames) and the frame's exp(y) / asum and centred accuracies by pdf
+__host__ __device__ inline int64_t den_acc_frame_floats(int H, int P) { return 4 * den_acc_round4(H) + 2 * den_acc_round4(P); }
+constexpr int kDenAccSmallLds = 1024;  // the block reductions' slots, rounded up
+inline bool den_acc_resident(int H, int P) { return 4 * den_acc_frame_floats(H, P) + kDenAccSmallLds <= (int64_t)160 * 1024; }
+// per sequence, in floats: alpha'_0..T, A'_0..T, 1 / asum_0..T, and room for the per-frame vectors of the streamed form
+__host__ __device__ inline int64_t den_acc_seq_floats(int H, int P, int T) {
+  return 2 * (int64_t)(T + 1) * den_acc_round4(H) + den_acc_round4(T + 1) + den_acc_frame_floats(H, P);
+}
+inline int64_t den_acc_grad_workspace_bytes(int H, int P, int S, int T) {
+  return (((int64_t)S * den_acc_seq_floats(H, P, T) * 4) + 255) & ~(int64_t)255;
+}
+
 // LDS layout of the fused kernel, in floats: [P | A | ACC | GAMMA | ALPHA? | red | asum].  exp(y)
 // (P) starts at offset 0 and its region has the compile-time size PV * 4096 of the kernel
 // instantiation, so the gather source A (alpha' forward, beta backward) has a compile-time base.
@@ -350,6 +407,8 @@ struct tc_den_graph {
   // tc_den_best_path's tables (den_best_path_kernels.hip), in a blob of their own per device: made on that call's first
   // use (den_best_tables, under `mu`), so `dev` and what the training step reads are what they are without it
   std::map<int, tc::DenBestDev> best_dev;
+  // ... and tc_den_expected_accuracy_grad's (den_accuracy_kernels.hip, den_acc_tables), kept the same way
+  std::map<int, tc::DenAccDev> acc_dev;
 };
 
 // ---- numerator -----------------------------------------------------------------------------------
@@ -587,6 +646,9 @@ int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via
 int launch_num_best_path(const NumParams &p, hipStream_t stream);    // num_best_path_kernels.hip (regular and end-to-end)
 int launch_den_best_path(const DenBestParams &p, hipStream_t stream);  // den_best_path_kernels.hip
 int den_best_tables(tc_den_graph *g, int device, DenBestDev *out);   // den_graph.cpp: made and uploaded on first use
+int launch_den_accuracy_rows(const DenAccRowParams &p, hipStream_t stream);  // den_accuracy_kernels.hip
+int launch_den_accuracy_grad(const DenAccGradParams &p, hipStream_t stream);
+int den_acc_tables(tc_den_graph *g, int device, DenAccDev *out);     // den_graph.cpp: made and uploaded on first use
 // dynamic LDS of num_e2e_kernel: two double score vectors, the frame's y per distinct pdf and one float per arc (max_arcs = 0:
 // of the kernels that keep no arc occupations on chip, num_e2e_large_kernel and num_e2e_best_path_kernel)
 inline size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs) {
@@ -719,7 +781,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -728,7 +790,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -426,7 +426,7 @@ extern "C" {
 int tc_debug_set(const char *key, int value) {
   static const char *const names[kDbgCount] = {"force_general", "force_streamed", "no_split", "no_pdf_banks",
                                                "no_bank_search", "sched_trace", "no_phase_split", "no_num_overlap", "no_pair",
-                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout"};
+                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout", "force_den_accuracy_streamed"};
   if (!key) return TC_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < kDbgCount; ++i)
     if (!strcmp(key, names[i])) {
@@ -466,7 +466,7 @@ int64_t tc_debug_counter(const char *key) {
   if (key && !strcmp(key, "pool_device_allocs")) return pool_counter(0);
   if (key && !strcmp(key, "pool_reuses")) return pool_counter(1);
   static const char *const names[kCntCount] = {"den_launches", "den_backward_launches", "num_launches", "num_backward_launches", "layout_launches",
-                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches"};
+                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches"};
   for (int i = 0; key && i < kCntCount; ++i)
     if (!strcmp(key, names[i])) return g_launches[i].load(std::memory_order_relaxed);
   return -1;
@@ -657,6 +657,14 @@ void tc_den_graph_free(tc_den_graph *g) {
     }
   }
   for (auto &kv : g->best_dev) {
+    int cur = 0;
+    if (kv.second.blob && hipGetDevice(&cur) == hipSuccess) {
+      (void)hipSetDevice(kv.first);
+      (void)hipFree(kv.second.blob);
+      (void)hipSetDevice(cur);
+    }
+  }
+  for (auto &kv : g->acc_dev) {
     int cur = 0;
     if (kv.second.blob && hipGetDevice(&cur) == hipSuccess) {
       (void)hipSetDevice(kv.first);
@@ -1133,6 +1141,70 @@ int tc::den_best_tables(tc_den_graph *g, int device, DenBestDev *out) {
   d.logpi = (const float *)(blob + off_pi);
   d.blob = blob;
   g->best_dev[device] = d;
+  *out = d;
+  return TC_OK;
+}
+
+// tc_den_expected_accuracy_grad's tables: the FST's arcs three times, as CSRs by destination state, by source state and by
+// pdf, each row in the order of the graph's arc list, with the handle's float32 probabilities.  Built and uploaded on the
+// first call per device, into a blob of their own; g->dev and g->best_dev are neither read nor written.
+int tc::den_acc_tables(tc_den_graph *g, int device, DenAccDev *out) {
+  std::lock_guard<std::mutex> lock(g->mu);
+  auto it = g->acc_dev.find(device);
+  if (it != g->acc_dev.end()) {
+    *out = it->second;
+    return TC_OK;
+  }
+  const int H = g->H, P = g->P;
+  const int64_t A = g->A;
+  auto csr = [&](const std::vector<int32_t> &key, int n) {
+    std::vector<int32_t> begin(n + 1, 0);
+    for (int64_t a = 0; a < A; ++a) ++begin[key[a] + 1];
+    for (int i = 0; i < n; ++i) begin[i + 1] += begin[i];
+    return begin;
+  };
+  const std::vector<int32_t> in_begin = csr(g->arc_dst, H), out_begin = csr(g->arc_src, H), pdf_begin = csr(g->arc_pdf, P);
+  const size_t An = (size_t)std::max<int64_t>(A, 1);
+  std::vector<DenAccArc> in_arcs(An, DenAccArc{0, 0, 0.f}), out_arcs(An, DenAccArc{0, 0, 0.f});
+  std::vector<DenAccPdfArc> pdf_arcs(An, DenAccPdfArc{0, 0, 0.f});
+  {
+    std::vector<int32_t> fi(in_begin.begin(), in_begin.end() - 1), fo(out_begin.begin(), out_begin.end() - 1),
+        fp(pdf_begin.begin(), pdf_begin.end() - 1);
+    for (int64_t a = 0; a < A; ++a) {
+      in_arcs[fi[g->arc_dst[a]]++] = DenAccArc{g->arc_src[a], g->arc_pdf[a], g->arc_prob[a]};
+      out_arcs[fo[g->arc_src[a]]++] = DenAccArc{g->arc_dst[a], g->arc_pdf[a], g->arc_prob[a]};
+      pdf_arcs[fp[g->arc_pdf[a]]++] = DenAccPdfArc{g->arc_src[a], g->arc_dst[a], g->arc_prob[a]};
+    }
+  }
+  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const void *src[7] = {in_begin.data(), out_begin.data(), pdf_begin.data(), in_arcs.data(),
+                        out_arcs.data(), pdf_arcs.data(), g->initial_probs.data()};
+  const size_t bytes[7] = {in_begin.size() * 4,  out_begin.size() * 4,           pdf_begin.size() * 4,        An * sizeof(DenAccArc),
+                           An * sizeof(DenAccArc), An * sizeof(DenAccPdfArc), (size_t)H * 4};
+  size_t off[8] = {0};
+  for (int i = 0; i < 7; ++i) off[i + 1] = off[i] + align(bytes[i]);
+  int prev = 0;
+  TC_HIP_CHECK(hipGetDevice(&prev));
+  TC_HIP_CHECK(hipSetDevice(device));
+  char *blob = nullptr;
+  hipError_t e = hipMalloc((void **)&blob, off[7]);
+  for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipMemcpy(blob + off[i], src[i], bytes[i], hipMemcpyHostToDevice);
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (blob) (void)hipFree(blob);
+    g_last_hip_error = (int)e;
+    return TC_ERR_HIP;
+  }
+  DenAccDev d;
+  d.in_begin = (const int32_t *)(blob + off[0]);
+  d.out_begin = (const int32_t *)(blob + off[1]);
+  d.pdf_begin = (const int32_t *)(blob + off[2]);
+  d.in_arcs = (const DenAccArc *)(blob + off[3]);
+  d.out_arcs = (const DenAccArc *)(blob + off[4]);
+  d.pdf_arcs = (const DenAccPdfArc *)(blob + off[5]);
+  d.pi = (const float *)(blob + off[6]);
+  d.blob = blob;
+  g->acc_dev[device] = d;
   *out = d;
   return TC_OK;
 }

@@ -802,3 +802,50 @@ def den_best_path(input, den_graph, frames=None, return_states=False, max_worksp
     with torch.no_grad():
         return den_graph.best_path(input, frames=frames, return_states=return_states, max_workspace_bytes=max_workspace_bytes,
                                    workspace=workspace, out=out, n_batch=n_batch)
+
+
+class _DenExpectedAccuracy(torch.autograd.Function):
+    """``den_expected_accuracy``: forward is one ``tc_den_expected_accuracy`` call, backward one
+    ``tc_den_expected_accuracy_grad`` call with ``grad_output`` as the sequences' scales."""
+
+    @staticmethod
+    def forward(ctx, input, den_graph, ref_pdfs, pdf_class, frames, leaky_hmm_coefficient, n_batch, max_workspace_bytes,
+                want_grad):
+        st = den_graph._expected_accuracy("den_expected_accuracy", input, ref_pdfs, pdf_class, frames, leaky_hmm_coefficient,
+                                          n_batch, max_workspace_bytes, want_grad)
+        if want_grad:
+            # (without the output itself: it points back here through its grad_fn)
+            ctx.den_graph, ctx.like = den_graph, (input.dim(), input.dtype)
+            ctx.st = {k: v for k, v in st.items() if k != "acc"}
+        return st["acc"]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        st = ctx.st
+        scale = grad_output.detach().to(device=st["y2d"].device, dtype=torch.float32).contiguous()
+        grad = ctx.den_graph._expected_accuracy_grad(st, scale)
+        dim, dtype = ctx.like
+        if dim == 3:  # (T*B, C) rows t*B + b -> (B, C, T); not a hot path
+            grad = grad.view(st["T"], st["B"], -1).permute(1, 2, 0).contiguous()
+        return (grad.to(dtype),) + (None,) * 8
+
+
+def den_expected_accuracy(input, den_graph, ref_pdfs, pdf_class=None, frames=None, leaky_hmm_coefficient=1e-5, n_batch=None,
+                          max_workspace_bytes=8 << 30):
+    """The expected frame accuracy of ``den_graph``'s paths under ``input`` against the frame-level reference ``ref_pdfs``,
+    float64 ``(B,)``, differentiable in ``input``: the lattice-free sMBR criterion (``io.DenominatorGraph.expected_accuracy``
+    states it and the arguments; ``tc_den_expected_accuracy``, ``tc_den_expected_accuracy_grad``).  Maximise
+    ``den_expected_accuracy(...).sum()``: the criterion is an accuracy, not a loss.  ``ref_pdfs`` is what ``best_path`` returns
+    for the supervision, ``pdf_class`` a pdf -> phone map for an MPFE-style criterion.
+
+    The forward pass is one denominator forward-backward and a row kernel, and nothing else runs under ``no_grad``.  The
+    backward pass is one launch of the accuracy-carrying forward-backward and, unlike ``chain_loss``, honours ``grad_output``:
+    sequence ``b``'s rows are ``grad_output[b] * dE_b/dinput``.  The gradient has the input's shape and dtype (computed in
+    float32, rounded once); padding frames and a sequence with a NaN or an infinity in its valid frames get +0.  Both passes'
+    workspaces are held against ``max_workspace_bytes`` before anything runs (``ValueError``); groups are not run."""
+    if not isinstance(den_graph, io.DenominatorGraph):
+        raise TypeError("den_expected_accuracy takes an io.DenominatorGraph, got %s" % type(den_graph).__name__)
+    # (inside forward the grad mode is off whatever the caller's: what a backward pass will need is decided here)
+    want_grad = torch.is_grad_enabled() and isinstance(input, torch.Tensor) and input.requires_grad
+    return _DenExpectedAccuracy.apply(input, den_graph, ref_pdfs, pdf_class, frames, leaky_hmm_coefficient, n_batch,
+                                      max_workspace_bytes, want_grad)

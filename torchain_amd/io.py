@@ -336,6 +336,123 @@ class DenominatorGraph:
                                            device.index, stream), "tc_den_best_path")
         return tuple(outs)
 
+    def expected_accuracy(self, nnet_output, ref_pdfs, pdf_class=None, frames=None, leaky_hmm_coefficient=1e-5, n_batch=None,
+                          max_workspace_bytes=8 << 30):
+        """The expected frame accuracy of this graph's paths under ``nnet_output`` against the frame-level reference
+        ``ref_pdfs`` (``tc_den_expected_accuracy``): the lattice-free sMBR criterion, per sequence
+        ``E[A] = sum_paths P(path | y) * sum_t a_t(pdf_t(path))`` under the denominator's own model (outputs clamped to +-30,
+        the graph's initial probabilities, ``leaky_hmm_coefficient``, every state final).  ``a_t(j)`` is 1 where
+        ``class(j) == class(ref_t)``, else 0.  Returns ``(acc, frame_acc)`` on the input's device: float64 ``(B,)`` and
+        float32 ``(B, Tmax)``, the frames' expected accuracies (0 in padding frames), which sum to ``acc``.  A sequence with
+        a NaN or an infinity in its valid frames gets NaN.
+
+        ``nnet_output``, ``frames`` and ``n_batch`` are ``best_path``'s: contiguous ``(B, C, T)`` float32 / bfloat16 / float16
+        or 2-D float32 ``(T*B, C)`` (row ``t*B + b``); anything that is not 2-D float32 is copied into such a matrix first --
+        this is not a hot path.  ``ref_pdfs``: an int tensor or array ``(B, Tmax)`` of 0-based pdfs, the layout ``best_path``
+        and ``Supervision.best_path`` return; a value outside ``0 .. n_pdf - 1`` (their ``-1``, or a caller's mark for
+        silence) means that the frame scores nothing.  ``pdf_class``: ``None`` (state-level sMBR) or ``n_pdf`` ints, e.g. a
+        pdf -> phone map for an MPFE-style criterion.  The workspace is the denominator's; beyond ``max_workspace_bytes`` a
+        ``ValueError`` names the bytes (groups of sequences are not run).  Asynchronous on the current stream; no autograd:
+        ``functions.den_expected_accuracy`` is the differentiable entry."""
+        st = self._expected_accuracy("expected_accuracy", nnet_output, ref_pdfs, pdf_class, frames, leaky_hmm_coefficient,
+                                     n_batch, max_workspace_bytes, False)
+        return st["acc"], st["frame_acc"]
+
+    def _expected_accuracy(self, who, nnet_output, ref_pdfs, pdf_class, frames, leaky, n_batch, max_workspace_bytes, want_grad):
+        """The checks, the 2-D float32 matrix and one ``tc_den_expected_accuracy`` call; returns what the gradient call needs
+        beside the results.  ``want_grad``: hold the gradient's workspace against the cap as well, before anything runs."""
+        x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("%s: nnet_output must be a CUDA tensor (only the HIP implementation is available)" % who)
+        P = self.n_pdf
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dim() == 3:
+            B, T = int(x.shape[0]), int(x.shape[2])
+            if int(x.shape[1]) != P or B < 1 or T < 1:
+                raise ValueError("%s: nnet output of shape %s is not (B, %d, T)" % (who, tuple(x.shape), P))
+            if x.dtype not in dtypes:
+                raise TypeError("%s: a (B, C, T) output must be float32, bfloat16 or float16, got %s" % (who, x.dtype))
+            if n_batch is not None and int(n_batch) != B:
+                raise ValueError("%s: n_batch = %d, but the output has %d sequences" % (who, int(n_batch), B))
+        elif x.dim() == 2:
+            if x.dtype != torch.float32:
+                raise TypeError("%s: a 2-D output must be float32, got %s" % (who, x.dtype))
+            if frames is None and n_batch is None:
+                raise ValueError("%s: a 2-D output needs `frames` or `n_batch` to tell the number of sequences" % who)
+            B = int(n_batch) if n_batch is not None else len(frames)
+            if int(x.shape[1]) != P or B < 1 or x.shape[0] < B or x.shape[0] % B != 0:
+                raise ValueError("%s: nnet output of shape %s is not (T * %d, %d)" % (who, tuple(x.shape), B, P))
+            T = int(x.shape[0]) // B
+        else:
+            raise ValueError("%s: nnet output must be (B, C, T) or (T*B, C), got shape %s" % (who, tuple(x.shape)))
+        lengths = None
+        if frames is not None:
+            lengths = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+            if lengths.ndim != 1 or lengths.dtype.kind not in "iu":
+                raise TypeError("%s: frames must be a list or an int tensor of lengths" % who)
+            if len(lengths) != B:
+                raise ValueError("%s: %d lengths for %d sequences" % (who, len(lengths), B))
+            if lengths.min() < 1 or lengths.max() > T:
+                raise ValueError("%s: every length must be in 1 .. %d, got %d .. %d" % (who, T, lengths.min(), lengths.max()))
+        device = x.device
+
+        def ints(v, shape, what):
+            t = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))
+            if t.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or tuple(t.shape) != shape:
+                raise ValueError("%s: %s must be an int tensor or array of shape %s" % (who, what, shape))
+            return t.to(device=device, dtype=torch.int32).contiguous()
+
+        ref = ints(ref_pdfs, (B, T), "ref_pdfs")
+        cls = None if pdf_class is None else ints(pdf_class, (P,), "pdf_class")
+        leaky = float(leaky)
+        if not (0.0 <= leaky < float("inf")):
+            raise ValueError("%s: the leaky-HMM coefficient must be finite and >= 0, got %r" % (who, leaky))
+        need = int(lib.tc_den_expected_accuracy_workspace_bytes(self.ptr, B, T))  # (host arithmetic only)
+        if want_grad:
+            need = max(need, int(lib.tc_den_expected_accuracy_grad_workspace_bytes(self.ptr, B, T)))
+        if need > int(max_workspace_bytes):
+            raise ValueError("%s: %d sequences of %d frames need %d bytes of workspace, %d are allowed"
+                             % (who, B, T, need, int(max_workspace_bytes)))
+        fr = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= P and x.data_ptr() % 4 == 0:
+                y2d = x
+            else:  # the existing gather entry: (b, t, :) rows of a channel-last tensor of `dtype` -> float32 row t*B + b
+                rows = x.transpose(1, 2).contiguous() if x.dim() == 3 else x.reshape(T, B, P).transpose(0, 1).contiguous()
+                y2d = torch.empty((T * B, P), dtype=torch.float32, device=device)
+                check(lib.tc_rows_gather(C.c_void_p(rows.data_ptr()), dtypes[x.dtype], B, P, T, T * P, P,
+                                         C.c_void_p(y2d.data_ptr()), P, device.index, stream), "tc_rows_gather")
+            gamma = torch.empty((T * B, P), dtype=torch.float32, device=device)
+            frame_acc = torch.empty((B, T), dtype=torch.float32, device=device)
+            acc = torch.empty((B,), dtype=torch.float64, device=device)
+            ws = torch.empty(int(lib.tc_den_expected_accuracy_workspace_bytes(self.ptr, B, T)), dtype=torch.uint8, device=device)
+            check(lib.tc_den_expected_accuracy(self.ptr, B, C.c_void_p(y2d.data_ptr()), B * T, P, y2d.stride(0),
+                                               None if fr is None else C.c_void_p(fr.data_ptr()), T, leaky,
+                                               C.c_void_p(ref.data_ptr()), None if cls is None else C.c_void_p(cls.data_ptr()),
+                                               C.c_void_p(gamma.data_ptr()), P, C.c_void_p(frame_acc.data_ptr()),
+                                               C.c_void_p(acc.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), device.index,
+                                               stream), "tc_den_expected_accuracy")
+        return {"acc": acc, "frame_acc": frame_acc, "y2d": y2d, "ref": ref, "cls": cls, "fr": fr, "B": B, "T": T,
+                "leaky": leaky}
+
+    def _expected_accuracy_grad(self, st, seq_scale):
+        """``tc_den_expected_accuracy_grad`` on what ``_expected_accuracy`` returned: the float32 ``(T*B, C)`` gradient, each
+        sequence's rows times its entry of ``seq_scale`` (float32 ``(B,)`` on the device, or ``None``)."""
+        B, T, P, y2d = st["B"], st["T"], self.n_pdf, st["y2d"]
+        device = y2d.device
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            grad = torch.empty((T * B, P), dtype=torch.float32, device=device)
+            ws = torch.empty(int(lib.tc_den_expected_accuracy_grad_workspace_bytes(self.ptr, B, T)), dtype=torch.uint8, device=device)
+            opt = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+            check(lib.tc_den_expected_accuracy_grad(self.ptr, B, C.c_void_p(y2d.data_ptr()), B * T, P, y2d.stride(0), opt(st["fr"]),
+                                                    T, st["leaky"], C.c_void_p(st["ref"].data_ptr()), opt(st["cls"]),
+                                                    C.c_void_p(st["frame_acc"].data_ptr()), opt(seq_scale),
+                                                    C.c_void_p(grad.data_ptr()), P, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                    device.index, stream), "tc_den_expected_accuracy_grad")
+        return grad
+
 
 class Supervision:
     """Reference ``io.py:20-31``: wraps a supervision handle and exposes ``n_pdf``, ``n_batch``,
