@@ -827,6 +827,45 @@ int tc_den_expected_accuracy_grad(tc_den_graph *g, int32_t S, const float *nnet_
                                   const float *seq_scale_dev /* nullable, [S]: 1 */, float *grad, int64_t grad_stride,
                                   void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* The same criterion against SOFT references: a dense per-pdf accuracy in place of ref_dev and class_dev,
+ *     a_t(j) = accuracy[(t*S + s) * accuracy_stride + j],
+ * held constant.  [K]'s chain-sMBR work (DenominatorSmbrComputation, `num_posteriors`) scores the denominator's paths against
+ * the NUMERATOR'S posteriors this way, a_t(j) = gamma_num_t(j): a regular supervision allows several paths, and a hard
+ * alignment of it under the current model moves with the model.  The matrix may hold any finite float32 -- posteriors,
+ * label-smoothed indicators, signed rewards; nothing assumes [0, 1] -- and a power of two times the matrix gives that power
+ * of two times every output, bit for bit (barring float32 underflow).  The float32 indicator of (ref_dev, class_dev) gives
+ * the bits of tc_den_expected_accuracy / _grad.
+ *   accuracy, accuracy_stride : device float32 (T*S, P), row t*S + s, rows accuracy_stride >= num_cols floats apart,
+ *                 4-byte aligned.  Rows of padding frames are not read.
+ * Every other argument, the outputs, the workspaces (tc_den_expected_accuracy_workspace_bytes,
+ * tc_den_expected_accuracy_grad_workspace_bytes serve both pairs), the launches, the two forms of the gradient kernel and
+ * "force_den_accuracy_streamed" are tc_den_expected_accuracy's and tc_den_expected_accuracy_grad's:
+ *   frame_acc_dev : m_t = sum_j gamma_t(j) a_t(j): a lane's pdfs in order, double products and sums, then a butterfly over
+ *                 the wave; rounded to float32.  acc_dev: their double sum in frame order.
+ *   gamma       : on return the denominator posteriors -- which are also dE_s / da_t(j), the derivative in the matrix.
+ *   The scan looks at the sequence's valid rows of `accuracy` as it looks at nnet_output's: a NaN or +-inf in either fails
+ *   that sequence alone (acc NaN, NaN in its valid frames of frame_acc_dev, every gradient row +0); the other sequences
+ *   keep their bits.
+ *   The gradient kernel forms a_t(j) - m_t from the row where it reads nnet_output's row; everything behind that is the
+ *   same code, with the error analysis of the hard form while |a - m| <= 1 (the error is relative to the scale of a).
+ * TC_ERR_INVALID_ARGUMENT, before any device call: what the hard pair refuses, with `accuracy` null or not 4-byte aligned
+ * and accuracy_stride < num_cols in place of the checks of ref_dev and class_dev.  TC_ERR_WORKSPACE, and TC_ERR_UNSUPPORTED
+ * passed through for lengths on a graph of the streamed path, as there.  The launches count into "den_accuracy_launches" /
+ * "den_accuracy_grad_launches" (and "..._grad_streamed_launches") and into "den_accuracy_dense_launches" /
+ * "den_accuracy_dense_grad_launches". */
+int tc_den_expected_accuracy_dense(tc_den_graph *g, int32_t S, const float *nnet_output, int64_t num_rows, int32_t num_cols,
+                                   int64_t row_stride, const int32_t *seq_frames_dev /* nullable: T each */, int32_t max_frames,
+                                   float leaky_hmm_coefficient, const float *accuracy /* (T*S, P) */, int64_t accuracy_stride,
+                                   float *gamma, int64_t gamma_stride, float *frame_acc_dev /* [S * T] */,
+                                   double *acc_dev /* [S] */, void *workspace, int64_t workspace_bytes, int device, void *stream);
+int tc_den_expected_accuracy_dense_grad(tc_den_graph *g, int32_t S, const float *nnet_output, int64_t num_rows,
+                                        int32_t num_cols, int64_t row_stride,
+                                        const int32_t *seq_frames_dev /* nullable: T each */, int32_t max_frames,
+                                        float leaky_hmm_coefficient, const float *accuracy /* (T*S, P) */,
+                                        int64_t accuracy_stride, const float *frame_acc_dev /* [S * T] */,
+                                        const float *seq_scale_dev /* nullable, [S]: 1 */, float *grad, int64_t grad_stride,
+                                        void *workspace, int64_t workspace_bytes, int device, void *stream);
+
 /* ---- the denominator graph's weights on caller-built supervisions ------------------------------------------------------
  * Every supervision Kaldi writes into an eg has been composed with the normalization FST of den.fst ([K]
  * AddWeightToSupervisionFst, DenominatorGraph::GetNormalizationFst; the end-to-end egs: --normalization-fst-scale), which
@@ -1008,8 +1047,9 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *   "no_full_layout" (1: the fused tied kernel never runs its full-layout twin -- every plane of states and pdfs whole,
  *                     16-byte rows, no cross-entropy zero rows, no hub states, DESIGN.md 4.1 -- but the general
  *                     instantiation; same bits.  Read at every such launch)
- *   "force_den_accuracy_streamed" (1: tc_den_expected_accuracy_grad keeps its per-frame vectors in the workspace for every
- *                     graph, as it does for those beyond its LDS form; same bits.  Read at every such call)
+ *   "force_den_accuracy_streamed" (1: tc_den_expected_accuracy_grad and tc_den_expected_accuracy_dense_grad keep their
+ *                     per-frame vectors in the workspace for every graph, as they do for those beyond the LDS form; same
+ *                     bits.  Read at every such call)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -1043,7 +1083,8 @@ int tc_debug_set(const char *key, int value);
  * "den_accuracy_launches" = tc_den_expected_accuracy calls that launched their row kernel (the denominator launch in front of
  * it counts in "den_launches" and "den_backward_launches" as any other), "den_accuracy_grad_launches" =
  * tc_den_expected_accuracy_grad calls that launched their kernel, and "den_accuracy_grad_streamed_launches" those of them
- * that kept the per-frame vectors in the workspace.
+ * that kept the per-frame vectors in the workspace; "den_accuracy_dense_launches" and "den_accuracy_dense_grad_launches" =
+ * those of the first two that came through tc_den_expected_accuracy_dense and tc_den_expected_accuracy_dense_grad.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

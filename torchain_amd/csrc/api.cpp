@@ -558,24 +558,31 @@ int64_t tc_den_expected_accuracy_grad_workspace_bytes(const tc_den_graph *g, int
   return den_acc_grad_workspace_bytes(g->H, g->P, S, T);
 }
 
-// what the two entries check alike, in front of any device call
+// what the entries check alike, in front of any device call.  The hard pair: ref_dev, class_dev (nullable); the dense pair:
+// accuracy, accuracy_stride (ref_dev and class_dev null).
 static int den_accuracy_args(const tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
                              const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
-                             const int32_t *class_dev, const float *frame_acc_dev, const void *out, int64_t out_stride) {
-  if (!g || !y || !ref_dev || !frame_acc_dev || !out || S <= 0 || max_frames <= 0) return TC_ERR_INVALID_ARGUMENT;
+                             const int32_t *class_dev, const float *accuracy, int64_t accuracy_stride, bool dense,
+                             const float *frame_acc_dev, const void *out, int64_t out_stride) {
+  if (!g || !y || !(dense ? (const void *)accuracy : (const void *)ref_dev) || !frame_acc_dev || !out || S <= 0 || max_frames <= 0)
+    return TC_ERR_INVALID_ARGUMENT;
   if (rows != (int64_t)S * max_frames || cols != g->P || y_stride < cols || out_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (dense && accuracy_stride < cols) return TC_ERR_INVALID_ARGUMENT;
   if (!(leaky >= 0.0f) || !(leaky <= FLT_MAX)) return TC_ERR_INVALID_ARGUMENT;
-  if ((((uintptr_t)seq_frames_dev | (uintptr_t)ref_dev | (uintptr_t)class_dev | (uintptr_t)frame_acc_dev | (uintptr_t)y) & 3) != 0)
+  if ((((uintptr_t)seq_frames_dev | (uintptr_t)ref_dev | (uintptr_t)class_dev | (uintptr_t)accuracy | (uintptr_t)frame_acc_dev |
+        (uintptr_t)y) & 3) != 0)
     return TC_ERR_INVALID_ARGUMENT;
   return TC_OK;
 }
 
-int tc_den_expected_accuracy(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
-                             const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
-                             const int32_t *class_dev, float *gamma, int64_t gamma_stride, float *frame_acc_dev,
-                             double *acc_dev, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
-  int rc = den_accuracy_args(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev,
-                             frame_acc_dev, gamma, gamma_stride);
+// tc_den_expected_accuracy and tc_den_expected_accuracy_dense
+static int den_accuracy_value(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                              const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
+                              const int32_t *class_dev, const float *accuracy, int64_t accuracy_stride, bool dense, float *gamma,
+                              int64_t gamma_stride, float *frame_acc_dev, double *acc_dev, void *workspace,
+                              int64_t workspace_bytes, int device, void *stream_v) {
+  int rc = den_accuracy_args(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev, accuracy,
+                             accuracy_stride, dense, frame_acc_dev, gamma, gamma_stride);
   if (rc != TC_OK) return rc;
   if (!acc_dev || ((uintptr_t)acc_dev & 7) != 0 || ((uintptr_t)gamma & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
   if (!workspace || tc_chain_workspace_bytes(g, S, max_frames) > workspace_bytes || !aligned16(workspace))
@@ -598,20 +605,26 @@ int tc_den_expected_accuracy(tc_den_graph *g, int32_t S, const float *y, int64_t
   p.T = max_frames;
   p.P = g->P;
   p.seq_frames = seq_frames_dev;
-  p.ref = ref_dev;
-  p.pdf_class = class_dev;
+  if (dense) {
+    p.accuracy = accuracy;
+    p.acc_stride = accuracy_stride;
+  } else {
+    p.ref = ref_dev;
+    p.pdf_class = class_dev;
+  }
   p.frame_acc = frame_acc_dev;
   p.acc = acc_dev;
-  return launch_den_accuracy_rows(p, (hipStream_t)stream_v);
+  return launch_den_accuracy_rows(p, dense, (hipStream_t)stream_v);
 }
 
-int tc_den_expected_accuracy_grad(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
-                                  const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
-                                  const int32_t *class_dev, const float *frame_acc_dev, const float *seq_scale_dev,
-                                  float *grad, int64_t grad_stride, void *workspace, int64_t workspace_bytes, int device,
-                                  void *stream_v) {
-  int rc = den_accuracy_args(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev,
-                             frame_acc_dev, grad, grad_stride);
+// tc_den_expected_accuracy_grad and tc_den_expected_accuracy_dense_grad
+static int den_accuracy_gradient(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                                 const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
+                                 const int32_t *class_dev, const float *accuracy, int64_t accuracy_stride, bool dense,
+                                 const float *frame_acc_dev, const float *seq_scale_dev, float *grad, int64_t grad_stride,
+                                 void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  int rc = den_accuracy_args(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev, accuracy,
+                             accuracy_stride, dense, frame_acc_dev, grad, grad_stride);
   if (rc != TC_OK) return rc;
   if ((((uintptr_t)grad | (uintptr_t)seq_scale_dev) & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
   if (!workspace || den_acc_grad_workspace_bytes(g->H, g->P, S, max_frames) > workspace_bytes || !aligned16(workspace))
@@ -631,15 +644,57 @@ int tc_den_expected_accuracy_grad(tc_den_graph *g, int32_t S, const float *y, in
   p.Ps = (int)den_acc_round4(g->P);
   p.leaky = leaky;
   p.seq_frames = seq_frames_dev;
-  p.ref = ref_dev;
-  p.pdf_class = class_dev;
+  if (dense) {
+    p.accuracy = accuracy;
+    p.acc_stride = accuracy_stride;
+  } else {
+    p.ref = ref_dev;
+    p.pdf_class = class_dev;
+  }
   p.frame_acc = frame_acc_dev;
   p.seq_scale = seq_scale_dev;
   p.grad = grad;
   p.grad_stride = grad_stride;
   p.workspace = (char *)workspace;
   p.resident = den_acc_resident(g->H, g->P) && !debug_flag(kDbgForceDenAccStreamed);
-  return launch_den_accuracy_grad(p, (hipStream_t)stream_v);
+  return launch_den_accuracy_grad(p, dense, (hipStream_t)stream_v);
+}
+
+int tc_den_expected_accuracy(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                             const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
+                             const int32_t *class_dev, float *gamma, int64_t gamma_stride, float *frame_acc_dev,
+                             double *acc_dev, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  return den_accuracy_value(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev, nullptr, 0,
+                            false, gamma, gamma_stride, frame_acc_dev, acc_dev, workspace, workspace_bytes, device, stream_v);
+}
+
+int tc_den_expected_accuracy_grad(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                                  const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const int32_t *ref_dev,
+                                  const int32_t *class_dev, const float *frame_acc_dev, const float *seq_scale_dev,
+                                  float *grad, int64_t grad_stride, void *workspace, int64_t workspace_bytes, int device,
+                                  void *stream_v) {
+  return den_accuracy_gradient(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, ref_dev, class_dev, nullptr, 0,
+                               false, frame_acc_dev, seq_scale_dev, grad, grad_stride, workspace, workspace_bytes, device,
+                               stream_v);
+}
+
+int tc_den_expected_accuracy_dense(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                                   const int32_t *seq_frames_dev, int32_t max_frames, float leaky, const float *accuracy,
+                                   int64_t accuracy_stride, float *gamma, int64_t gamma_stride, float *frame_acc_dev,
+                                   double *acc_dev, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  return den_accuracy_value(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, nullptr, nullptr, accuracy,
+                            accuracy_stride, true, gamma, gamma_stride, frame_acc_dev, acc_dev, workspace, workspace_bytes,
+                            device, stream_v);
+}
+
+int tc_den_expected_accuracy_dense_grad(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols,
+                                        int64_t y_stride, const int32_t *seq_frames_dev, int32_t max_frames, float leaky,
+                                        const float *accuracy, int64_t accuracy_stride, const float *frame_acc_dev,
+                                        const float *seq_scale_dev, float *grad, int64_t grad_stride, void *workspace,
+                                        int64_t workspace_bytes, int device, void *stream_v) {
+  return den_accuracy_gradient(g, S, y, rows, cols, y_stride, seq_frames_dev, max_frames, leaky, nullptr, nullptr, accuracy,
+                               accuracy_stride, true, frame_acc_dev, seq_scale_dev, grad, grad_stride, workspace,
+                               workspace_bytes, device, stream_v);
 }
 
 }  // extern "C"

@@ -231,7 +231,18 @@ struct DenAccRowParams {
   const float *y, *gamma;
   int64_t y_stride, gamma_stride;
   int S, T, P;
-  const int32_t *seq_frames, *ref, *pdf_class;
+  const int32_t *seq_frames;
+  // The hard form: ref [S][T], pdf_class [P] nullable.  The dense form (tc_den_expected_accuracy_dense; the launchers are told
+  // which): a_t(j) from row t*S + s of the float32 matrix `accuracy` (T*S, P), rows acc_stride floats apart.  The two pairs
+  // share their 16 bytes, so the struct is byte for byte the one the hard form's kernels have always read.
+  union {
+    const int32_t *ref;
+    const float *accuracy;
+  };
+  union {
+    const int32_t *pdf_class;
+    int64_t acc_stride;
+  };
   float *frame_acc;  // [S][T]
   double *acc;       // [S]
 };
@@ -241,7 +252,15 @@ struct DenAccGradParams {
   int64_t y_stride;
   int S, T, H, P, Hs, Ps;  // T: the longest sequence's frames; Hs, Ps: H, P rounded up to 4
   float leaky;
-  const int32_t *seq_frames, *ref, *pdf_class;  // [S] nullable, [S][T], [P] nullable
+  const int32_t *seq_frames;  // [S] nullable
+  union {                     // as in DenAccRowParams
+    const int32_t *ref;       // [S][T]
+    const float *accuracy;    // (T*S, P)
+  };
+  union {
+    const int32_t *pdf_class;  // [P] nullable
+    int64_t acc_stride;
+  };
   const float *frame_acc;                       // [S][T]: the centring constants m_t
   const float *seq_scale;                       // [S] nullable: 1
   float *grad;
@@ -646,8 +665,8 @@ int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via
 int launch_num_best_path(const NumParams &p, hipStream_t stream);    // num_best_path_kernels.hip (regular and end-to-end)
 int launch_den_best_path(const DenBestParams &p, hipStream_t stream);  // den_best_path_kernels.hip
 int den_best_tables(tc_den_graph *g, int device, DenBestDev *out);   // den_graph.cpp: made and uploaded on first use
-int launch_den_accuracy_rows(const DenAccRowParams &p, hipStream_t stream);  // den_accuracy_kernels.hip
-int launch_den_accuracy_grad(const DenAccGradParams &p, hipStream_t stream);
+int launch_den_accuracy_rows(const DenAccRowParams &p, bool dense, hipStream_t stream);  // den_accuracy_kernels.hip
+int launch_den_accuracy_grad(const DenAccGradParams &p, bool dense, hipStream_t stream);
 int den_acc_tables(tc_den_graph *g, int device, DenAccDev *out);     // den_graph.cpp: made and uploaded on first use
 // dynamic LDS of num_e2e_kernel: two double score vectors, the frame's y per distinct pdf and one float per arc (max_arcs = 0:
 // of the kernels that keep no arc occupations on chip, num_e2e_large_kernel and num_e2e_best_path_kernel)
@@ -790,7 +809,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

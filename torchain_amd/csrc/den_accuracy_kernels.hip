@@ -4,7 +4,12 @@
 //     E_s[A] = sum_paths P(path | y_s) * sum_t a_t(pdf_t(path)),      a_t(j) = [0 <= ref_t < P and class(j) == class(ref_t)]
 //
 // with the denominator's own model: p_t(j) = exp(clamp(y_t(j), +-kOutputLimit)), the graph's initial probabilities pi, the
-// leaky-HMM coefficient c, every state final.
+// leaky-HMM coefficient c, every state final.  DENSE (tc_den_expected_accuracy_dense, _dense_grad): a_t(j) is not that
+// indicator but element j of row t*S + s of a float32 matrix the caller gives -- the numerator's posteriors (Kaldi's
+// chain-sMBR), label-smoothed indicators, signed rewards: any finite float32.  Only the places that produce a_t(j) differ
+// (the row kernel's m_t, stage() below, and the scan, which looks at the sequence's valid rows of the matrix beside y's);
+// the recursions and the centring argument do not depend on what a_t(j) is, and the hard form's instantiations are the
+// instruction streams they were (profiles/den_accuracy_dense/kernel_isa.txt).
 //
 // The value needs nothing new: m_t = sum_j gamma_t(j) a_t(j) from the denominator posteriors the tuned kernels write, and
 // E_s = sum_t m_t (den_accuracy_rows_kernel, one workgroup per sequence, the frames in order, in double).
@@ -120,13 +125,19 @@ __device__ __forceinline__ bool finite(float v) { return fabsf(v) <= FLT_MAX; }
 
 // whether any y of the sequence's T valid frames is a NaN or an infinity (every thread gets the answer).  slot: kAccWaves
 // ints of LDS that the next user puts a barrier in front of.  (Not __syncthreads_or: it brings static LDS with it, which
-// comes off what the gradient kernel may ask for and moves the base of its dynamic region.)
-__device__ __forceinline__ bool scan_bad(const float *y, int64_t y_stride, int S, int P, int q, int T, int lane, int wave,
-                                         int *slot) {
+// comes off what the gradient kernel may ask for and moves the base of its dynamic region.)  DENSE: or any a of the same
+// rows of the accuracy matrix; its padding rows are not read either.
+template <bool DENSE>
+__device__ __forceinline__ bool scan_bad(const float *y, int64_t y_stride, const float *a, int64_t a_stride, int S, int P, int q,
+                                         int T, int lane, int wave, int *slot) {
   int bad = 0;
   for (int t = wave; t < T; t += kAccWaves) {
     const float *row = y + ((int64_t)t * S + q) * y_stride;
     for (int c = lane; c < P; c += 64) bad |= !finite(row[c]);
+    if (DENSE) {
+      const float *arow = a + ((int64_t)t * S + q) * a_stride;
+      for (int c = lane; c < P; c += 64) bad |= !finite(arow[c]);
+    }
   }
   const int any = __ballot(bad != 0) != 0;
   if (lane == 0) slot[wave] = any;
@@ -143,21 +154,28 @@ __device__ __forceinline__ int class_of(const int32_t *pdf_class, int j) { retur
 
 }  // namespace
 
+template <bool DENSE>
 __global__ __launch_bounds__(kAccThreads) void den_accuracy_rows_kernel(const DenAccRowParams p) {
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = p.seq_frames ? ragged_frames(p.seq_frames, q, p.T) : p.T;
   __shared__ int slot[kAccWaves];
-  const bool bad = scan_bad(p.y, p.y_stride, p.S, p.P, q, T, lane, wave, slot);
+  const bool bad = scan_bad<DENSE>(p.y, p.y_stride, p.accuracy, p.acc_stride, p.S, p.P, q, T, lane, wave, slot);
   float *fa = p.frame_acc + (int64_t)q * p.T;
   for (int t = wave; t < p.T; t += kAccWaves) {
     double m = 0.0;
     if (t < T && !bad) {
-      const int r = p.ref[(int64_t)q * p.T + t];
-      if (ref_ok(r, p.P)) {  // (wave-uniform)
-        const int cr = class_of(p.pdf_class, r);
+      if (DENSE) {  // (an indicator's products are g * 1 and g * 0, exact fused or not: the hard form's sum)
         const float *g = p.gamma + ((int64_t)t * p.S + q) * p.gamma_stride;
-        for (int j = lane; j < p.P; j += 64)
-          if (class_of(p.pdf_class, j) == cr) m += (double)g[j];
+        const float *a = p.accuracy + ((int64_t)t * p.S + q) * p.acc_stride;
+        for (int j = lane; j < p.P; j += 64) m += (double)g[j] * (double)a[j];
+      } else {
+        const int r = p.ref[(int64_t)q * p.T + t];
+        if (ref_ok(r, p.P)) {  // (wave-uniform)
+          const int cr = class_of(p.pdf_class, r);
+          const float *g = p.gamma + ((int64_t)t * p.S + q) * p.gamma_stride;
+          for (int j = lane; j < p.P; j += 64)
+            if (class_of(p.pdf_class, j) == cr) m += (double)g[j];
+        }
       }
       m = wave_sum(m);
     }
@@ -171,7 +189,7 @@ __global__ __launch_bounds__(kAccThreads) void den_accuracy_rows_kernel(const De
   }
 }
 
-template <bool RAGGED, bool RESIDENT>
+template <bool RAGGED, bool RESIDENT, bool DENSE>
 __global__ __launch_bounds__(kAccThreads) void den_accuracy_grad_kernel(const DenAccGradParams p) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   double *red = reinterpret_cast<double *>(lds_raw);  // [2][kAccWaves]
@@ -182,7 +200,7 @@ __global__ __launch_bounds__(kAccThreads) void den_accuracy_grad_kernel(const De
   const float scale = p.seq_scale ? p.seq_scale[q] : 1.0f;
 
   // ---- scan; the rows nobody computes ----
-  const bool bad = scan_bad(p.y, p.y_stride, S, P, q, T, lane, wave, reinterpret_cast<int *>(red));
+  const bool bad = scan_bad<DENSE>(p.y, p.y_stride, p.accuracy, p.acc_stride, S, P, q, T, lane, wave, reinterpret_cast<int *>(red));
   for (int t = (bad ? 0 : T) + wave; t < p.T; t += kAccWaves) {
     float *row = p.grad + ((int64_t)t * S + q) * p.grad_stride;
     for (int c = lane; c < P; c += 64) row[c] = 0.0f;
@@ -201,6 +219,16 @@ __global__ __launch_bounds__(kAccThreads) void den_accuracy_grad_kernel(const De
   // exp(y_t) / asum_t and the centred accuracies of frame t, by pdf (the same expressions in both passes)
   auto stage = [&](int t, float inv_t) {
     const float *yrow = p.y + ((int64_t)t * S + q) * p.y_stride;
+    if (DENSE) {  // (the dense row is read where y's is)
+      const float *arow = p.accuracy + ((int64_t)t * S + q) * p.acc_stride;
+      const float m = p.frame_acc[(int64_t)q * p.T + t];
+      for (int j = tid; j < P; j += kAccThreads) {
+        const float yc = fminf(fmaxf(yrow[j], -kOutputLimit), kOutputLimit);
+        pe[j] = expf(yc) * inv_t;
+        at[j] = arow[j] - m;
+      }
+      return;
+    }
     const int r = p.ref[(int64_t)q * p.T + t];
     const bool ok = ref_ok(r, P);
     const int cr = ok ? class_of(p.pdf_class, r) : 0;
@@ -327,9 +355,9 @@ __global__ __launch_bounds__(kAccThreads) void den_accuracy_grad_kernel(const De
 
 namespace {
 
-template <bool RAGGED, bool RESIDENT>
+template <bool RAGGED, bool RESIDENT, bool DENSE>
 int launch_grad(const DenAccGradParams &p, hipStream_t stream) {
-  void (*kernel)(const DenAccGradParams) = den_accuracy_grad_kernel<RAGGED, RESIDENT>;
+  void (*kernel)(const DenAccGradParams) = den_accuracy_grad_kernel<RAGGED, RESIDENT, DENSE>;
   const size_t lds = kDenAccSmallLds + (RESIDENT ? (size_t)4 * den_acc_frame_floats(p.H, p.P) : 0);
   TC_HIP_CHECK(allow_dynamic_lds((const void *)kernel, lds));
   hipLaunchKernelGGL(kernel, dim3(p.S), dim3(kAccThreads), lds, stream, p);
@@ -337,23 +365,37 @@ int launch_grad(const DenAccGradParams &p, hipStream_t stream) {
   return TC_OK;
 }
 
+template <bool DENSE>
+int launch_grad_form(const DenAccGradParams &p, hipStream_t stream) {
+  if (p.seq_frames) return p.resident ? launch_grad<true, true, DENSE>(p, stream) : launch_grad<true, false, DENSE>(p, stream);
+  return p.resident ? launch_grad<false, true, DENSE>(p, stream) : launch_grad<false, false, DENSE>(p, stream);
+}
+
 }  // namespace
 
-int launch_den_accuracy_rows(const DenAccRowParams &p, hipStream_t stream) {
-  if (!p.y || !p.gamma || !p.ref || !p.frame_acc || !p.acc) return TC_ERR_INVALID_ARGUMENT;
+// dense: p.accuracy and p.acc_stride are set, not p.ref and p.pdf_class
+int launch_den_accuracy_rows(const DenAccRowParams &p, bool dense, hipStream_t stream) {
+  if (!p.y || !p.gamma || !p.ref || !p.frame_acc || !p.acc) return TC_ERR_INVALID_ARGUMENT;  // (ref: or accuracy)
+  if (dense && p.acc_stride < p.P) return TC_ERR_INVALID_ARGUMENT;
   count_launch(kCntDenAccuracy);
-  hipLaunchKernelGGL(den_accuracy_rows_kernel, dim3(p.S), dim3(kAccThreads), 0, stream, p);
+  if (dense) {
+    count_launch(kCntDenAccuracyDense);
+    hipLaunchKernelGGL(den_accuracy_rows_kernel<true>, dim3(p.S), dim3(kAccThreads), 0, stream, p);
+  } else {
+    hipLaunchKernelGGL(den_accuracy_rows_kernel<false>, dim3(p.S), dim3(kAccThreads), 0, stream, p);
+  }
   TC_HIP_CHECK(hipGetLastError());
   return TC_OK;
 }
 
-int launch_den_accuracy_grad(const DenAccGradParams &p, hipStream_t stream) {
+int launch_den_accuracy_grad(const DenAccGradParams &p, bool dense, hipStream_t stream) {
   if (!p.y || !p.ref || !p.frame_acc || !p.grad || !p.workspace || !p.t.in_arcs) return TC_ERR_INVALID_ARGUMENT;
+  if (dense && p.acc_stride < p.P) return TC_ERR_INVALID_ARGUMENT;
   if (p.resident && !den_acc_resident(p.H, p.P)) return TC_ERR_INVALID_ARGUMENT;
   count_launch(kCntDenAccuracyGrad);
   if (!p.resident) count_launch(kCntDenAccuracyGradStreamed);
-  if (p.seq_frames) return p.resident ? launch_grad<true, true>(p, stream) : launch_grad<true, false>(p, stream);
-  return p.resident ? launch_grad<false, true>(p, stream) : launch_grad<false, false>(p, stream);
+  if (dense) count_launch(kCntDenAccuracyDenseGrad);
+  return dense ? launch_grad_form<true>(p, stream) : launch_grad_form<false>(p, stream);
 }
 
 }  // namespace tc

@@ -849,3 +849,87 @@ def den_expected_accuracy(input, den_graph, ref_pdfs, pdf_class=None, frames=Non
     want_grad = torch.is_grad_enabled() and isinstance(input, torch.Tensor) and input.requires_grad
     return _DenExpectedAccuracy.apply(input, den_graph, ref_pdfs, pdf_class, frames, leaky_hmm_coefficient, n_batch,
                                       max_workspace_bytes, want_grad)
+
+
+class _DenExpectedAccuracyDense(torch.autograd.Function):
+    """``den_expected_accuracy_dense``: forward is ``tc_den_expected_accuracy_dense``; backward in ``input`` is
+    ``tc_den_expected_accuracy_dense_grad`` with ``grad_output`` as the sequences' scales, backward in ``accuracy`` is
+    ``grad_output`` times the denominator posteriors the forward call left."""
+
+    @staticmethod
+    def forward(ctx, input, accuracy, den_graph, frames, leaky_hmm_coefficient, n_batch, max_workspace_bytes, want_input,
+                want_accuracy):
+        st = den_graph._expected_accuracy_dense("den_expected_accuracy_dense", input, accuracy, frames, leaky_hmm_coefficient,
+                                                n_batch, max_workspace_bytes, want_input, want_accuracy)
+        ctx.want = (want_input, want_accuracy)
+        if want_input or want_accuracy:
+            # (without the output itself: it points back here through its grad_fn; what neither gradient reads is dropped)
+            ctx.den_graph = den_graph
+            ctx.like = (input.dim(), input.dtype, accuracy.dim(), accuracy.dtype)
+            keep = {"frame_acc", "y2d", "a2d", "fr", "B", "T", "leaky", "group"} if want_input else {"fr", "B", "T"}
+            ctx.st = {k: v for k, v in st.items() if k in keep or (k == "gamma" and want_accuracy)}
+            ctx.failed = torch.isnan(st["acc"]) if want_accuracy else None
+        return st["acc"]
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        st, (want_input, want_accuracy) = ctx.st, ctx.want
+        B, T = st["B"], st["T"]
+        in_dim, in_dtype, acc_dim, acc_dtype = ctx.like
+        scale = grad_output.detach().to(dtype=torch.float32).contiguous()
+
+        def shaped(g2d, dim, dtype):  # (T*B, C) rows t*B + b -> (B, C, T); not a hot path
+            if dim == 3:
+                g2d = g2d.view(T, B, -1).permute(1, 2, 0).contiguous()
+            return g2d.to(dtype)
+
+        grad_input = grad_accuracy = None
+        if want_input and ctx.needs_input_grad[0]:
+            grad_input = shaped(ctx.den_graph._expected_accuracy_dense_grad(st, scale), in_dim, in_dtype)
+        if want_accuracy and ctx.needs_input_grad[1]:
+            gamma = st["gamma"].view(T, B, -1)
+            # +0 -- not grad_output * 0, which has grad_output's sign -- in padding rows and in every row of a failed sequence
+            valid = ~ctx.failed.view(1, B)
+            if st["fr"] is not None:
+                valid = valid & (torch.arange(T, device=gamma.device).view(T, 1) < st["fr"].view(1, B))
+            g = torch.where(valid.unsqueeze(2), gamma * scale.view(1, B, 1), gamma.new_zeros(()))
+            grad_accuracy = shaped(g.view(T * B, -1), acc_dim, acc_dtype)
+        return (grad_input, grad_accuracy) + (None,) * 7
+
+
+def den_expected_accuracy_dense(input, den_graph, accuracy, frames=None, leaky_hmm_coefficient=1e-5, n_batch=None,
+                                max_workspace_bytes=8 << 30):
+    """Lattice-free sMBR against SOFT references: the expected accuracy of ``den_graph``'s paths under ``input`` where a path
+    scores ``accuracy[t, pdf_t(path)]`` in frame ``t``, float64 ``(B,)``, differentiable in ``input`` and in ``accuracy``
+    (``io.DenominatorGraph.expected_accuracy_dense`` states it and the arguments; ``tc_den_expected_accuracy_dense``,
+    ``tc_den_expected_accuracy_dense_grad``).  Kaldi's chain-sMBR recipe is
+
+        acc = den_expected_accuracy_dense(out, graph, num_posteriors(out, supervision))
+
+    with the numerator's posteriors as a constant.  Maximise ``acc.sum()``: an accuracy, not a loss.
+
+    The gradient in ``input`` is one launch of the accuracy-carrying forward-backward per group of sequences, sequence ``b``'s
+    rows times ``grad_output[b]``, in the input's shape and dtype (float32 arithmetic, rounded once); it runs only when
+    ``input`` requires a gradient.  The gradient in ``accuracy`` is ``grad_output[b] * gamma_den``, the denominator posteriors
+    of the forward pass, in ``accuracy``'s shape and dtype; they are kept only when ``accuracy`` requires a gradient.  Padding
+    rows and every row of a sequence with a NaN or an infinity in its valid frames of either argument are exactly +0 in both.
+    Under ``no_grad`` only the value runs.  Beyond ``max_workspace_bytes`` consecutive groups of sequences run, with the
+    single call's bits; ``ValueError`` only where one sequence alone does not fit."""
+    if not isinstance(den_graph, io.DenominatorGraph):
+        raise TypeError("den_expected_accuracy_dense takes an io.DenominatorGraph, got %s" % type(den_graph).__name__)
+    # (inside forward the grad mode is off whatever the caller's: what a backward pass will need is decided here)
+    on = torch.is_grad_enabled()
+    want_input = on and isinstance(input, torch.Tensor) and input.requires_grad
+    want_accuracy = on and isinstance(accuracy, torch.Tensor) and accuracy.requires_grad
+    return _DenExpectedAccuracyDense.apply(input, accuracy, den_graph, frames, leaky_hmm_coefficient, n_batch,
+                                           max_workspace_bytes, want_input, want_accuracy)
+
+
+def num_posteriors(input, supervision, pdf_class=None):
+    """The numerator's occupation posteriors of ``supervision`` under ``input``, dense float32 ``(T*B, C)``
+    (``io.Supervision.posteriors``): the soft reference of ``den_expected_accuracy_dense``; with ``pdf_class`` pooled by class
+    (MPFE).  A constant, as in Kaldi: no autograd."""
+    if not isinstance(supervision, io.Supervision):
+        raise TypeError("num_posteriors takes an io.Supervision, got %s" % type(supervision).__name__)
+    with torch.no_grad():
+        return supervision.posteriors(input, pdf_class=pdf_class)

@@ -358,9 +358,9 @@ class DenominatorGraph:
                                      n_batch, max_workspace_bytes, False)
         return st["acc"], st["frame_acc"]
 
-    def _expected_accuracy(self, who, nnet_output, ref_pdfs, pdf_class, frames, leaky, n_batch, max_workspace_bytes, want_grad):
-        """The checks, the 2-D float32 matrix and one ``tc_den_expected_accuracy`` call; returns what the gradient call needs
-        beside the results.  ``want_grad``: hold the gradient's workspace against the cap as well, before anything runs."""
+    def _accuracy_arguments(self, who, nnet_output, frames, n_batch):
+        """The checks of the expected-accuracy entries on ``nnet_output``, ``frames`` and ``n_batch``, before any library call:
+        ``(x, B, T, lengths)``, ``x`` the detached tensor and ``lengths`` a numpy array or ``None``."""
         x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise ValueError("%s: nnet_output must be a CUDA tensor (only the HIP implementation is available)" % who)
@@ -394,6 +394,27 @@ class DenominatorGraph:
                 raise ValueError("%s: %d lengths for %d sequences" % (who, len(lengths), B))
             if lengths.min() < 1 or lengths.max() > T:
                 raise ValueError("%s: every length must be in 1 .. %d, got %d .. %d" % (who, T, lengths.min(), lengths.max()))
+        return x, B, T, lengths
+
+    def _accuracy_rows(self, x, B, T, stream):
+        """``x`` -- ``(B, C, T)`` of float32 / bfloat16 / float16 or 2-D float32 -- as a float32 matrix ``(T*B, C)``, row
+        ``t*B + b``, with unit column stride: itself, or a copy made by ``tc_rows_gather``."""
+        P, device = self.n_pdf, x.device
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= P and x.data_ptr() % 4 == 0:
+            return x
+        # the existing gather entry: (b, t, :) rows of a channel-last tensor of `dtype` -> float32 row t*B + b
+        rows = x.transpose(1, 2).contiguous() if x.dim() == 3 else x.reshape(T, B, P).transpose(0, 1).contiguous()
+        y2d = torch.empty((T * B, P), dtype=torch.float32, device=device)
+        check(lib.tc_rows_gather(C.c_void_p(rows.data_ptr()), dtypes[x.dtype], B, P, T, T * P, P,
+                                 C.c_void_p(y2d.data_ptr()), P, device.index, stream), "tc_rows_gather")
+        return y2d
+
+    def _expected_accuracy(self, who, nnet_output, ref_pdfs, pdf_class, frames, leaky, n_batch, max_workspace_bytes, want_grad):
+        """The checks, the 2-D float32 matrix and one ``tc_den_expected_accuracy`` call; returns what the gradient call needs
+        beside the results.  ``want_grad``: hold the gradient's workspace against the cap as well, before anything runs."""
+        x, B, T, lengths = self._accuracy_arguments(who, nnet_output, frames, n_batch)
+        P = self.n_pdf
         device = x.device
 
         def ints(v, shape, what):
@@ -416,13 +437,7 @@ class DenominatorGraph:
         fr = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(device)
         with torch.cuda.device(device):
             stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= P and x.data_ptr() % 4 == 0:
-                y2d = x
-            else:  # the existing gather entry: (b, t, :) rows of a channel-last tensor of `dtype` -> float32 row t*B + b
-                rows = x.transpose(1, 2).contiguous() if x.dim() == 3 else x.reshape(T, B, P).transpose(0, 1).contiguous()
-                y2d = torch.empty((T * B, P), dtype=torch.float32, device=device)
-                check(lib.tc_rows_gather(C.c_void_p(rows.data_ptr()), dtypes[x.dtype], B, P, T, T * P, P,
-                                         C.c_void_p(y2d.data_ptr()), P, device.index, stream), "tc_rows_gather")
+            y2d = self._accuracy_rows(x, B, T, stream)
             gamma = torch.empty((T * B, P), dtype=torch.float32, device=device)
             frame_acc = torch.empty((B, T), dtype=torch.float32, device=device)
             acc = torch.empty((B,), dtype=torch.float64, device=device)
@@ -452,6 +467,127 @@ class DenominatorGraph:
                                                     C.c_void_p(grad.data_ptr()), P, C.c_void_p(ws.data_ptr()), ws.numel(),
                                                     device.index, stream), "tc_den_expected_accuracy_grad")
         return grad
+
+    def expected_accuracy_dense(self, nnet_output, accuracy, frames=None, leaky_hmm_coefficient=1e-5, n_batch=None,
+                                max_workspace_bytes=8 << 30, return_posteriors=False):
+        """``expected_accuracy`` against SOFT references (``tc_den_expected_accuracy_dense``): ``a_t(j)`` is not the indicator of
+        a reference pdf but entry ``(t, j)`` of ``accuracy``, a dense matrix held constant -- the numerator's posteriors
+        (``Supervision.posteriors``: Kaldi's chain-sMBR, ``a_t(j) = gamma_num_t(j)``), label-smoothed indicators, signed
+        rewards; any finite float32.  Returns ``(acc, frame_acc)``, float64 ``(B,)`` and float32 ``(B, Tmax)``, and with
+        ``return_posteriors`` also the denominator posteriors ``gamma``, float32 ``(T*B, C)`` (row ``t*B + b``, +0 in padding
+        rows) -- which are ``d acc[b] / d accuracy``.  A sequence with a NaN or an infinity in its valid frames of
+        ``nnet_output`` or of ``accuracy`` gets NaN; the others keep their bits.  The float32 indicator of ``(ref_pdfs,
+        pdf_class)`` gives the bits of ``expected_accuracy``.
+
+        ``nnet_output``, ``frames``, ``n_batch``: as for ``expected_accuracy``.  ``accuracy`` takes the same layouts,
+        independently: 2-D float32 ``(T*B, C)`` or ``(B, C, T)`` in float32 / bfloat16 / float16 (widened to float32);
+        whatever is not a 2-D float32 matrix with unit column stride is copied into one.  Padding frames of either are not
+        read.  Shapes and dtypes are checked before any library call.
+
+        When the batch needs more than ``max_workspace_bytes``, consecutive groups of sequences run one after the other, as
+        many at a time as fit, each on copies of its rows: the outputs are the single call's, bit for bit.  ``ValueError``
+        only where one sequence alone does not fit.  Asynchronous on the current stream; no autograd:
+        ``functions.den_expected_accuracy_dense`` is the differentiable entry."""
+        st = self._expected_accuracy_dense("expected_accuracy_dense", nnet_output, accuracy, frames, leaky_hmm_coefficient,
+                                           n_batch, max_workspace_bytes, False, return_posteriors)
+        return (st["acc"], st["frame_acc"]) + ((st["gamma"],) if return_posteriors else ())
+
+    def _expected_accuracy_dense(self, who, nnet_output, accuracy, frames, leaky, n_batch, max_workspace_bytes, want_grad,
+                                 keep_gamma):
+        """The checks, the two 2-D float32 matrices and ``tc_den_expected_accuracy_dense`` on every group of sequences; returns
+        what the gradient call needs beside the results.  ``want_grad``: size the groups for the gradient's workspace as well.
+        ``keep_gamma``: the denominator posteriors of the whole batch are part of the result."""
+        x, B, T, lengths = self._accuracy_arguments(who, nnet_output, frames, n_batch)
+        P, device = self.n_pdf, x.device
+        a = accuracy.detach() if isinstance(accuracy, torch.Tensor) else accuracy
+        if not isinstance(a, torch.Tensor) or a.device != device:
+            raise ValueError("%s: accuracy must be a tensor on the output's device (%s)" % (who, device))
+        if a.dim() == 3:
+            if tuple(a.shape) != (B, P, T):
+                raise ValueError("%s: accuracy of shape %s is not (%d, %d, %d)" % (who, tuple(a.shape), B, P, T))
+            if a.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+                raise TypeError("%s: a (B, C, T) accuracy must be float32, bfloat16 or float16, got %s" % (who, a.dtype))
+        elif a.dim() == 2:
+            if tuple(a.shape) != (T * B, P):
+                raise ValueError("%s: accuracy of shape %s is not (%d, %d)" % (who, tuple(a.shape), T * B, P))
+            if a.dtype != torch.float32:
+                raise TypeError("%s: a 2-D accuracy must be float32, got %s" % (who, a.dtype))
+        else:
+            raise ValueError("%s: accuracy must be (B, C, T) or (T*B, C), got shape %s" % (who, tuple(a.shape)))
+        leaky = float(leaky)
+        if not (0.0 <= leaky < float("inf")):
+            raise ValueError("%s: the leaky-HMM coefficient must be finite and >= 0, got %r" % (who, leaky))
+
+        def need(n):  # (host arithmetic only)
+            value = int(lib.tc_den_expected_accuracy_workspace_bytes(self.ptr, n, T))
+            return max(value, int(lib.tc_den_expected_accuracy_grad_workspace_bytes(self.ptr, n, T))) if want_grad else value
+
+        cap, group = int(max_workspace_bytes), B
+        if need(B) > cap:
+            if need(1) > cap:
+                raise ValueError("%s: one sequence of %d frames needs %d bytes of workspace, %d are allowed"
+                                 % (who, T, need(1), cap))
+            group = max(1, min(B, cap // need(1)))
+            while need(group) > cap:
+                group -= 1
+            while group < B and need(group + 1) <= cap:
+                group += 1
+        fr = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            y2d, a2d = self._accuracy_rows(x, B, T, stream), self._accuracy_rows(a, B, T, stream)
+            frame_acc = torch.empty((B, T), dtype=torch.float32, device=device)
+            acc = torch.empty((B,), dtype=torch.float64, device=device)
+            gamma = torch.empty((T * B, P), dtype=torch.float32, device=device) if keep_gamma or group == B else None
+            ws = torch.empty(int(lib.tc_den_expected_accuracy_workspace_bytes(self.ptr, group, T)), dtype=torch.uint8, device=device)
+            for s0 in range(0, B, group):
+                n = min(group, B - s0)
+                yg, ag = _group_rows(y2d, s0, n, B, T), _group_rows(a2d, s0, n, B, T)
+                gg = gamma if n == B else torch.empty((T * n, P), dtype=torch.float32, device=device)
+                check(lib.tc_den_expected_accuracy_dense(self.ptr, n, C.c_void_p(yg.data_ptr()), n * T, P, yg.stride(0),
+                                                         None if fr is None else C.c_void_p(fr[s0:s0 + n].data_ptr()), T, leaky,
+                                                         C.c_void_p(ag.data_ptr()), ag.stride(0), C.c_void_p(gg.data_ptr()), P,
+                                                         C.c_void_p(frame_acc[s0:s0 + n].data_ptr()),
+                                                         C.c_void_p(acc[s0:s0 + n].data_ptr()), C.c_void_p(ws.data_ptr()),
+                                                         ws.numel(), device.index, stream), "tc_den_expected_accuracy_dense")
+                if n != B and keep_gamma:
+                    gamma.view(T, B, P)[:, s0:s0 + n].copy_(gg.view(T, n, P))
+        return {"acc": acc, "frame_acc": frame_acc, "gamma": gamma if keep_gamma else None, "y2d": y2d, "a2d": a2d, "fr": fr,
+                "B": B, "T": T, "leaky": leaky, "group": group}
+
+    def _expected_accuracy_dense_grad(self, st, seq_scale):
+        """``tc_den_expected_accuracy_dense_grad`` on what ``_expected_accuracy_dense`` returned, in its groups: the float32
+        ``(T*B, C)`` gradient in the outputs, each sequence's rows times its entry of ``seq_scale`` (float32 ``(B,)`` on the
+        device, or ``None``)."""
+        B, T, P, y2d, a2d, group = st["B"], st["T"], self.n_pdf, st["y2d"], st["a2d"], st["group"]
+        device = y2d.device
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            grad = torch.empty((T * B, P), dtype=torch.float32, device=device)
+            ws = torch.empty(int(lib.tc_den_expected_accuracy_grad_workspace_bytes(self.ptr, group, T)), dtype=torch.uint8, device=device)
+            for s0 in range(0, B, group):
+                n = min(group, B - s0)
+                yg, ag = _group_rows(y2d, s0, n, B, T), _group_rows(a2d, s0, n, B, T)
+                gg = grad if n == B else torch.empty((T * n, P), dtype=torch.float32, device=device)
+                check(lib.tc_den_expected_accuracy_dense_grad(
+                    self.ptr, n, C.c_void_p(yg.data_ptr()), n * T, P, yg.stride(0),
+                    None if st["fr"] is None else C.c_void_p(st["fr"][s0:s0 + n].data_ptr()), T, st["leaky"],
+                    C.c_void_p(ag.data_ptr()), ag.stride(0), C.c_void_p(st["frame_acc"][s0:s0 + n].data_ptr()),
+                    None if seq_scale is None else C.c_void_p(seq_scale[s0:s0 + n].data_ptr()), C.c_void_p(gg.data_ptr()), P,
+                    C.c_void_p(ws.data_ptr()), ws.numel(), device.index, stream), "tc_den_expected_accuracy_dense_grad")
+                if n != B:
+                    grad.view(T, B, P)[:, s0:s0 + n].copy_(gg.view(T, n, P))
+        return grad
+
+
+def _group_rows(m, s0, n, B, T):
+    """Sequences ``s0 .. s0 + n - 1`` of a frame-major matrix ``(T*B, C)`` with unit column stride as a matrix ``(T*n, C)`` of
+    their own, row ``t*n + s``: the matrix itself for the whole batch, a view for one sequence, a copy otherwise."""
+    if n == B:
+        return m
+    rs, cols = m.stride(0), m.shape[1]
+    g = torch.as_strided(m, (T, n, cols), (B * rs, rs, 1), m.storage_offset() + s0 * rs)
+    return g[:, 0] if n == 1 else g.reshape(T * n, cols)
 
 
 class Supervision:
@@ -761,6 +897,65 @@ class Supervision:
                                                C.c_void_p(scores.data_ptr()), device.index, stream),
                   "tc_supervision_best_path")
         return pdfs, scores
+
+    def posteriors(self, nnet_output, pdf_class=None):
+        """The numerator's occupation posteriors ``gamma_num_t(j)`` under ``nnet_output``, dense float32 ``(T*B, C)`` (row
+        ``t*B + b``) on the input's device: what Kaldi's chain-sMBR scores the denominator's paths against
+        (``DenominatorGraph.expected_accuracy_dense``, ``functions.den_expected_accuracy_dense``).  Regular and end-to-end
+        handles, uniform and ragged, on whichever numerator kernel the handle takes: ``tc_num_forward_backward`` into a zeroed
+        matrix, divided by the handle's weight (a weight of 0 raises ``ValueError``).  The rows of a sequence's valid frames sum
+        to 1; padding rows, and every row of a sequence without a path of its length, are +0.
+
+        ``pdf_class``: ``None``, or ``n_pdf`` ints that pool the posteriors by class, ``a_t(j) = sum of gamma_num_t(k) over the
+        k with class(k) == class(j)`` -- an MPFE-style accuracy (a pdf -> phone map); rows then sum to the sizes of the
+        classes met.  ``nnet_output`` is what ``chain_loss`` takes: 2-D float32 ``(T*B, C)``, or ``(B, C, T)`` in float32 /
+        bfloat16 / float16 (copied into such a matrix first).  No autograd: the result is a constant, as in Kaldi.  The handle's
+        pool slot is scratch here as for ``best_path``: a training step on the handle gives the same bits before and after."""
+        x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("posteriors: nnet_output must be a CUDA tensor (only the HIP implementation is available)")
+        S, T, P = self.n_batch, self.n_frame, self.n_pdf
+        want = (S, P, T) if x.dim() == 3 else (S * T, P)
+        if x.dim() not in (2, 3) or tuple(x.shape) != want:
+            raise ValueError("posteriors: nnet output of shape %s does not match the supervision (%s expected)"
+                             % (tuple(x.shape), want))
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dtype not in dtypes or (x.dim() == 2 and x.dtype != torch.float32):
+            raise TypeError("posteriors: the output must be float32 (or, as (B, C, T), bfloat16 or float16), got %s" % x.dtype)
+        weight = float(self.weight)
+        if not (weight != 0.0 and abs(weight) < float("inf")):
+            raise ValueError("posteriors: the supervision's weight is %r; the posteriors are the derivative divided by it" % weight)
+        device = x.device
+        cls = None
+        if pdf_class is not None:
+            cls = pdf_class.detach() if isinstance(pdf_class, torch.Tensor) else torch.from_numpy(np.asarray(pdf_class))
+            if cls.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or tuple(cls.shape) != (P,):
+                raise ValueError("posteriors: pdf_class must be an int tensor or array of shape (%d,)" % P)
+            cls = cls.to(device=device, dtype=torch.int64)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= P and x.data_ptr() % 4 == 0:
+                y2d = x
+            else:  # (b, t, :) rows of a channel-last tensor of `dtype` -> float32 row t*B + b
+                rows = x.transpose(1, 2).contiguous() if x.dim() == 3 else x.reshape(T, S, P).transpose(0, 1).contiguous()
+                y2d = torch.empty((T * S, P), dtype=torch.float32, device=device)
+                check(lib.tc_rows_gather(C.c_void_p(rows.data_ptr()), dtypes[x.dtype], S, P, T, T * P, P,
+                                         C.c_void_p(y2d.data_ptr()), P, device.index, stream), "tc_rows_gather")
+            post = torch.zeros((T * S, P), dtype=torch.float32, device=device)
+            ws = torch.empty(256 * ((S * 8 + 255) // 256) + 256, dtype=torch.uint8, device=device)  # a log-prob per sequence
+            check(lib.tc_num_forward_backward(self.ptr, C.c_void_p(y2d.data_ptr()), S * T, P, y2d.stride(0),
+                                              C.c_void_p(post.data_ptr()), P, None, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                              device.index, stream), "tc_num_forward_backward")
+            post /= weight
+            # a sequence without a path: its log-prob is not finite, whatever the kernel left in its rows
+            alive = torch.isfinite(ws[:S * 8].view(torch.float64))
+            post = torch.where(alive.view(1, S, 1), post.view(T, S, P), post.new_zeros(())).view(T * S, P)
+            if cls is not None:  # pooled by class, in double: exact for posteriors and the same in every call
+                inv = torch.unique(cls, return_inverse=True)[1]
+                member = torch.zeros((P, int(inv.max()) + 1), dtype=torch.float64, device=device)
+                member[torch.arange(P, device=device), inv] = 1.0
+                post = (post.double() @ member)[:, inv].float().contiguous()
+        return post
 
     def __del__(self, _free=lib.tc_supervision_free):
         ptr = getattr(self, "ptr", None)
