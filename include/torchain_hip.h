@@ -866,6 +866,70 @@ int tc_den_expected_accuracy_dense_grad(tc_den_graph *g, int32_t S, const float 
                                         const float *seq_scale_dev /* nullable, [S]: 1 */, float *grad, int64_t grad_stride,
                                         void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* ---- paths drawn from the denominator's posterior (den_sample_kernels.hip) -----------------------------------------------
+ * tc_den_sample_paths draws num_samples = K paths a sequence from P(path | y), the path posterior of the model that
+ * tc_den_forward_backward sums over: p_t(j) = exp(clamp(y_t(j), +-30)), the graph's initial probabilities pi, every state
+ * final, and the leaky-HMM transitions.  For any function r of a path, grad_y E[r] = E[(r - b) grad_y log P(path | y)] and
+ * grad_y log P(path | y) = onehot(pdfs of the path) - gamma_den; with the risks centred over a sequence's K samples the gamma
+ * term cancels and the estimate of the gradient is a scatter of K * T numbers: sequence-level risks (edit distance, any
+ * reward) without a second forward-backward.  The random numbers are the caller's: `uniforms_dev`, float32 in [0, 1).
+ *
+ * The model.  With c the leaky coefficient, per sequence of T frames:
+ *     alpha_0 = pi;   asum_t = sum_h alpha_t(h);   alpha'_t(h) = alpha_t(h) + c pi(h) asum_t
+ *     alpha_{t+1}(g) = sum_{h->g} alpha'_t(h) w p_t(pdf) / asum_t
+ * A latent path has levels t = 0 .. T.  At each level it holds the state it entered, pre_t, and the state it leaves from,
+ * post_t; the two differ where a leak happened.
+ * The selection rule.  For sequence s and sample k, u = uniforms[s][k] ((max_frames + 1) rows of 3):
+ *     pick(weights, u) : the first index i, in list order, whose inclusive cumulative sum exceeds u * total.  Weights, sums
+ *                        and the threshold are doubles.  If rounding leaves no such index, the last index with a positive
+ *                        weight.  A zero weight is never picked.
+ *     last state       : post_T = pick(alpha'_T over the states in state order, u[T][2]).
+ *     for t = T down to 0, with j = post_t:
+ *       leak decision  : no leak iff u[t][0] * alpha'_t(j) < alpha_t(j) (in double).  alpha'_t(j) is formed again from the
+ *                        stored alpha_t(j), pi(j) and asum_t by the forward pass's own operations, so c = 0 never leaks.
+ *       pre-leak state : pre_t = j without a leak, else pick(alpha_t over the states in state order, u[t][1]).
+ *       arc, for t > 0 : the in-arcs of pre_t in the order of the graph's arc list, each weighted by the double product
+ *                        alpha'_{t-1}(src) * w * p_{t-1}(pdf) (the frame's 1 / asum is common to the list and left out),
+ *                        picked with u[t-1][2].  pdf_{t-1} is that arc's pdf and post_{t-1} its source.
+ * Arithmetic.  alpha_t and asum_t are float32 where they are stored (the workspace); every sum over arcs or states is a
+ * double sum rounded once when stored; p_t(j) is the float32 expf of the clamped output; w and pi are the handle's float32
+ * probabilities; alpha'_t(h) = (float)((double)alpha_t(h) + (double)pi(h) * ((double)c * (double)asum_t)) wherever it is used;
+ * alpha_{t+1}(g) = (float)(sum of the doubles alpha'_t(h) * (w * p_t(pdf)) times the double 1 / asum_t).  The double sums of
+ * a pick may be associated in any way (chunks of 64 items, a prefix over the wavefront): that moves a threshold by about
+ * 1e-16 of the total.
+ * Failed sequences.  A sequence with a NaN or +-inf in its valid frames (the scan of tc_den_expected_accuracy_grad), or
+ * with an asum_t that is zero, subnormal or not finite, or with sum_h alpha'_T(h) = 0, gets -1 in every slot; the other
+ * sequences keep their bits.  Padding slots (frames >= the sequence's length, state levels above it) are -1.
+ * A sequence's output depends only on its own rows of nnet_output, its own rows of uniforms_dev, the graph and c: not on S,
+ * on its place in the batch, on K or on the other sequences.  Sample k of a K-sample call equals sample k of any other call
+ * given the same uniforms[s][k].
+ *   nnet_output : device float32 (T*S, P), row t*S + s, rows row_stride >= num_cols floats apart (2-D rows only, as the
+ *                 expected-accuracy entries take); num_rows = S * max_frames.  Rows of padding frames are not read.
+ *   seq_frames_dev : tc_den_best_path's: S device int32 lengths in 1 .. max_frames, or null (max_frames each).  Lengths work
+ *                 on graphs of every size: this entry refuses no graph.
+ *   uniforms_dev: device float32 [S][K][max_frames + 1][3], contiguous.  Row t of a sample: [0] the leak decision of level
+ *                 t, [1] the pre-leak state of level t, [2] the arc of frame t (row T_s: the last state).
+ *   pdf_dev     : device int32 [S][K][max_frames], 0-based pdfs.  state_dev (nullable): device int32
+ *                 [S][K][max_frames + 1][2], (pre_t, post_t), the FST's states.
+ *   workspace   : tc_den_sample_paths_workspace_bytes(g, S, max_frames): per sequence (T + 1) * Hs * 4 bytes (Hs: the
+ *                 states rounded up to 4) plus T + 1 floats rounded up to 4; the whole rounded up to 256 bytes; 16-byte
+ *                 aligned.
+ * One launch, one workgroup a sequence; asynchronous on `stream`; the graph's training tables are not read (a training step
+ * on the graph gives the same bits before and after) and nothing is allocated after the graph's first call on the device
+ * (which uploads the tables of tc_den_expected_accuracy_grad if that has not).  The previous frame's alpha' is in LDS while
+ * 4 * Hs + 1024 <= 163840 bytes, otherwise it is formed from the workspace's row per arc: the same bits
+ * ("den_sample_streamed_launches" counts those launches, tc_debug_set("force_den_sample_streamed", 1) sends every graph
+ * there).  "den_sample_launches" counts the launches; "den_launches" does not move.
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null graph, nnet_output, uniforms_dev or pdf_dev; S, max_frames or
+ * num_samples <= 0; num_rows != S * max_frames; num_cols != the graph's pdfs; row_stride < num_cols; a negative or
+ * non-finite coefficient; a pointer that is not 4-byte aligned.  TC_ERR_WORKSPACE: a null, short or misaligned workspace. */
+int64_t tc_den_sample_paths_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T);
+int tc_den_sample_paths(tc_den_graph *g, int32_t S, const float *nnet_output, int64_t num_rows, int32_t num_cols,
+                        int64_t row_stride, const int32_t *seq_frames_dev /* nullable */, int32_t max_frames,
+                        float leaky_hmm_coefficient, int32_t num_samples, const float *uniforms_dev /* [S][K][T+1][3] */,
+                        int32_t *pdf_dev /* [S][K][T] */, int32_t *state_dev /* nullable, [S][K][T+1][2]: pre, post */,
+                        void *workspace, int64_t workspace_bytes, int device, void *stream);
+
 /* ---- the denominator graph's weights on caller-built supervisions ------------------------------------------------------
  * Every supervision Kaldi writes into an eg has been composed with the normalization FST of den.fst ([K]
  * AddWeightToSupervisionFst, DenominatorGraph::GetNormalizationFst; the end-to-end egs: --normalization-fst-scale), which
@@ -1050,6 +1114,8 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *   "force_den_accuracy_streamed" (1: tc_den_expected_accuracy_grad and tc_den_expected_accuracy_dense_grad keep their
  *                     per-frame vectors in the workspace for every graph, as they do for those beyond the LDS form; same
  *                     bits.  Read at every such call)
+ *   "force_den_sample_streamed" (1: tc_den_sample_paths forms the previous frame's alpha' from the workspace's row for
+ *                     every graph, as it does for those beyond the LDS form; same bits.  Read at every such call)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -1084,7 +1150,9 @@ int tc_debug_set(const char *key, int value);
  * it counts in "den_launches" and "den_backward_launches" as any other), "den_accuracy_grad_launches" =
  * tc_den_expected_accuracy_grad calls that launched their kernel, and "den_accuracy_grad_streamed_launches" those of them
  * that kept the per-frame vectors in the workspace; "den_accuracy_dense_launches" and "den_accuracy_dense_grad_launches" =
- * those of the first two that came through tc_den_expected_accuracy_dense and tc_den_expected_accuracy_dense_grad.
+ * those of the first two that came through tc_den_expected_accuracy_dense and tc_den_expected_accuracy_dense_grad;
+ * "den_sample_launches" = tc_den_sample_paths calls that launched their kernel (not counted in "den_launches"), and
+ * "den_sample_streamed_launches" those of them that formed the previous frame's alpha' from the workspace.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -697,6 +697,46 @@ int tc_den_expected_accuracy_dense_grad(tc_den_graph *g, int32_t S, const float 
                                workspace_bytes, device, stream_v);
 }
 
+int64_t tc_den_sample_paths_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {
+  if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
+  return den_sample_workspace_bytes(g->H, S, T);
+}
+
+int tc_den_sample_paths(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                        const int32_t *seq_frames_dev, int32_t max_frames, float leaky, int32_t num_samples,
+                        const float *uniforms_dev, int32_t *pdf_dev, int32_t *state_dev, void *workspace,
+                        int64_t workspace_bytes, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!g || !y || !uniforms_dev || !pdf_dev || S <= 0 || max_frames <= 0 || num_samples <= 0) return TC_ERR_INVALID_ARGUMENT;
+  if (rows != (int64_t)S * max_frames || cols != g->P || y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!(leaky >= 0.0f) || !(leaky <= FLT_MAX)) return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)y | (uintptr_t)seq_frames_dev | (uintptr_t)uniforms_dev | (uintptr_t)pdf_dev | (uintptr_t)state_dev) & 3) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  if (!workspace || den_sample_workspace_bytes(g->H, S, max_frames) > workspace_bytes || !aligned16(workspace))
+    return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  DenSampleParams p;
+  const int rc = den_acc_tables(g, device, &p.t);
+  if (rc != TC_OK) return rc;
+  p.y = y;
+  p.y_stride = y_stride;
+  p.S = S;
+  p.T = max_frames;
+  p.H = g->H;
+  p.P = g->P;
+  p.Hs = (int)den_acc_round4(g->H);
+  p.K = num_samples;
+  p.leaky = leaky;
+  p.seq_frames = seq_frames_dev;
+  p.uniforms = uniforms_dev;
+  p.pdf_out = pdf_dev;
+  p.state_out = state_dev;
+  p.workspace = (char *)workspace;
+  p.resident = den_sample_resident(g->H) && !debug_flag(kDbgForceDenSampleStreamed);
+  return launch_den_sample_paths(p, (hipStream_t)stream_v);
+}
+
 }  // extern "C"
 
 // deriv_scale = 1: the reference's outputs.  deriv_scale = -1: what its backward returns (tc_chain_objf_and_grad).

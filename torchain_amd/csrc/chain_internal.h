@@ -282,6 +282,30 @@ inline int64_t den_acc_grad_workspace_bytes(int H, int P, int S, int T) {
   return (((int64_t)S * den_acc_seq_floats(H, P, T) * 4) + 255) & ~(int64_t)255;
 }
 
+// Paths drawn from the graph's path posterior (tc_den_sample_paths, den_sample_kernels.hip): the by-destination CSR of
+// DenAccDev (den_acc_tables) and nothing else of the graph.
+struct DenSampleParams {
+  DenAccDev t;
+  const float *y;
+  int64_t y_stride;
+  int S, T, H, P, Hs, K;  // T: the longest sequence's frames; Hs: H rounded up to 4; K: samples a sequence
+  float leaky;
+  const int32_t *seq_frames;  // [S] nullable
+  const float *uniforms;      // [S][K][T + 1][3]: leak decision, pre-leak state, arc (row T: the last state)
+  int32_t *pdf_out;           // [S][K][T]
+  int32_t *state_out;         // [S][K][T + 1][2]: pre, post; nullable
+  char *workspace;            // den_sample_workspace_bytes: per sequence [alpha_0..T | asum_0..T]
+  int resident;               // alpha' of the frame being read in LDS (den_sample_resident), else formed from the workspace
+};
+constexpr int kDenSampleSmallLds = 1024;  // the block reductions' slots, rounded up
+inline bool den_sample_resident(int H) { return 4 * den_acc_round4(H) + kDenSampleSmallLds <= (int64_t)160 * 1024; }
+__host__ __device__ inline int64_t den_sample_seq_floats(int H, int T) {
+  return (int64_t)(T + 1) * den_acc_round4(H) + den_acc_round4(T + 1);
+}
+inline int64_t den_sample_workspace_bytes(int H, int S, int T) {
+  return (((int64_t)S * den_sample_seq_floats(H, T) * 4) + 255) & ~(int64_t)255;
+}
+
 // LDS layout of the fused kernel, in floats: [P | A | ACC | GAMMA | ALPHA? | red | asum].  exp(y)
 // (P) starts at offset 0 and its region has the compile-time size PV * 4096 of the kernel
 // instantiation, so the gather source A (alpha' forward, beta backward) has a compile-time base.
@@ -668,6 +692,7 @@ int den_best_tables(tc_den_graph *g, int device, DenBestDev *out);   // den_grap
 int launch_den_accuracy_rows(const DenAccRowParams &p, bool dense, hipStream_t stream);  // den_accuracy_kernels.hip
 int launch_den_accuracy_grad(const DenAccGradParams &p, bool dense, hipStream_t stream);
 int den_acc_tables(tc_den_graph *g, int device, DenAccDev *out);     // den_graph.cpp: made and uploaded on first use
+int launch_den_sample_paths(const DenSampleParams &p, hipStream_t stream);  // den_sample_kernels.hip
 // dynamic LDS of num_e2e_kernel: two double score vectors, the frame's y per distinct pdf and one float per arc (max_arcs = 0:
 // of the kernels that keep no arc occupations on chip, num_e2e_large_kernel and num_e2e_best_path_kernel)
 inline size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs) {
@@ -800,7 +825,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -809,7 +834,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -426,7 +426,7 @@ extern "C" {
 int tc_debug_set(const char *key, int value) {
   static const char *const names[kDbgCount] = {"force_general", "force_streamed", "no_split", "no_pdf_banks",
                                                "no_bank_search", "sched_trace", "no_phase_split", "no_num_overlap", "no_pair",
-                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout", "force_den_accuracy_streamed"};
+                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout", "force_den_accuracy_streamed", "force_den_sample_streamed"};
   if (!key) return TC_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < kDbgCount; ++i)
     if (!strcmp(key, names[i])) {
@@ -466,7 +466,7 @@ int64_t tc_debug_counter(const char *key) {
   if (key && !strcmp(key, "pool_device_allocs")) return pool_counter(0);
   if (key && !strcmp(key, "pool_reuses")) return pool_counter(1);
   static const char *const names[kCntCount] = {"den_launches", "den_backward_launches", "num_launches", "num_backward_launches", "layout_launches",
-                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches"};
+                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches", "den_sample_launches", "den_sample_streamed_launches"};
   for (int i = 0; key && i < kCntCount; ++i)
     if (!strcmp(key, names[i])) return g_launches[i].load(std::memory_order_relaxed);
   return -1;

@@ -925,6 +925,76 @@ def den_expected_accuracy_dense(input, den_graph, accuracy, frames=None, leaky_h
                                            max_workspace_bytes, want_input, want_accuracy)
 
 
+def den_sample_paths(input, den_graph, num_samples, frames=None, leaky_hmm_coefficient=1e-5, generator=None, uniforms=None,
+                     return_states=False, max_workspace_bytes=1 << 30, workspace=None, n_batch=None):
+    """``num_samples`` paths a sequence drawn from ``den_graph``'s path posterior under ``input`` -- the denominator's own
+    model, leaky-HMM transitions included -- int32 ``(B, K, Tmax)`` (``-1`` in padding frames and for a failed sequence), and
+    with ``return_states`` the FST's states, int32 ``(B, K, Tmax + 1, 2)`` (``io.DenominatorGraph.sample_paths`` states the
+    arguments; ``tc_den_sample_paths``).  The random numbers come from ``generator`` or are given as ``uniforms``.  Autograd
+    is not involved: ``sampled_risk_surrogate`` makes a gradient of the samples."""
+    if not isinstance(den_graph, io.DenominatorGraph):
+        raise TypeError("den_sample_paths takes an io.DenominatorGraph, got %s" % type(den_graph).__name__)
+    with torch.no_grad():
+        return den_graph.sample_paths(input, num_samples, frames=frames, leaky_hmm_coefficient=leaky_hmm_coefficient,
+                                      generator=generator, uniforms=uniforms, return_states=return_states,
+                                      max_workspace_bytes=max_workspace_bytes, workspace=workspace, n_batch=n_batch)
+
+
+def sampled_risk_surrogate(input, pdfs, risks, frames=None):
+    """A SURROGATE whose gradient in ``input`` is the unbiased sampling estimate of ``grad E[r(path)]``, the expected risk of
+    the denominator graph's paths under ``input`` -- not an estimate of ``E[r]`` itself: its value means nothing.  Float64
+    ``(B,)``, plain torch, differentiable in ``input``:
+
+        L_s = 1 / (K - 1) * sum_k (r_sk - mean_k r_sk) * sum_{t < T_s} clamp(input_s,t, +-30)[pdfs_skt]
+
+    ``pdfs``: int ``(B, K, Tmax)``, ``K >= 2`` paths a sequence drawn by ``den_sample_paths`` from the same ``input``;
+    ``risks``: ``(B, K)``, any function of each path (held constant).  Why it works: ``grad E[r] = E[(r - b) grad log
+    P(path | y)]`` and ``grad log P(path | y) = onehot(pdfs of the path) - gamma_den``; with the risks centred over the
+    sequence's own samples the ``gamma_den`` term cancels, and ``1 / (K - 1)`` makes up for the centring.  The clamp is the
+    denominator's: an output outside +-30 gets exactly +0, as do padding rows.  A failed sequence (all ``-1``) gives 0.
+    ``input`` is ``(B, C, T)`` or 2-D ``(T*B, C)`` (row ``t*B + b``); ``frames``: the sequences' lengths, ``None``: wherever
+    ``pdfs >= 0``.  Training on a sequence-level risk, e.g. an edit distance to the transcript, is
+
+        pdfs = den_sample_paths(out, graph, 8, generator=gen)
+        risks = torch.tensor([[edit_distance(phones_of(p), ref[b]) for p in pdfs[b].tolist()] for b in range(B)])
+        sampled_risk_surrogate(out, pdfs, risks).sum().backward()      # minimises the expected edit distance
+    """
+    if not isinstance(input, torch.Tensor) or input.dim() not in (2, 3) or not input.is_floating_point():
+        raise ValueError("sampled_risk_surrogate: input must be a floating-point (B, C, T) or (T*B, C) tensor")
+    if not isinstance(pdfs, torch.Tensor) or pdfs.dim() != 3 or pdfs.dtype not in (torch.int32, torch.int64):
+        raise ValueError("sampled_risk_surrogate: pdfs must be an int32 or int64 tensor (B, K, Tmax)")
+    B, K, T = (int(v) for v in pdfs.shape)
+    if K < 2:
+        raise ValueError("sampled_risk_surrogate: centring the risks needs K >= 2 samples a sequence, got %d" % K)
+    if input.dim() == 3:
+        if int(input.shape[0]) != B or int(input.shape[2]) != T:
+            raise ValueError("sampled_risk_surrogate: input of shape %s is not (%d, C, %d)" % (tuple(input.shape), B, T))
+        rows = input.transpose(1, 2)  # (B, T, C)
+    else:
+        if int(input.shape[0]) != T * B:
+            raise ValueError("sampled_risk_surrogate: input of shape %s is not (%d * %d, C)" % (tuple(input.shape), T, B))
+        rows = input.reshape(T, B, -1).transpose(0, 1)
+    P = int(rows.shape[2])
+    r = torch.as_tensor(risks)
+    if tuple(r.shape) != (B, K):
+        raise ValueError("sampled_risk_surrogate: risks of shape %s are not (%d, %d)" % (tuple(r.shape), B, K))
+    r = r.detach().to(device=input.device, dtype=torch.float64)
+    pdfs = pdfs.detach().to(input.device)
+    if int(pdfs.max()) >= P:
+        raise ValueError("sampled_risk_surrogate: a pdf is outside 0 .. %d" % (P - 1))
+    valid = pdfs >= 0
+    if frames is not None:
+        lengths = torch.as_tensor(frames).detach().to(device=input.device, dtype=torch.int64)
+        if tuple(lengths.shape) != (B,) or int(lengths.min()) < 1 or int(lengths.max()) > T:
+            raise ValueError("sampled_risk_surrogate: frames must be %d lengths in 1 .. %d" % (B, T))
+        valid = valid & (torch.arange(T, device=input.device).view(1, 1, T) < lengths.view(B, 1, 1))
+    index = pdfs.clamp(min=0).to(torch.int64).transpose(1, 2)  # (B, T, K)
+    picked = rows.gather(2, index).clamp(-30.0, 30.0).to(torch.float64)
+    picked = torch.where(valid.transpose(1, 2), picked, picked.new_zeros(()))
+    weight = (r - r.mean(dim=1, keepdim=True)) / (K - 1)
+    return (picked.sum(dim=1) * weight).sum(dim=1)
+
+
 def num_posteriors(input, supervision, pdf_class=None):
     """The numerator's occupation posteriors of ``supervision`` under ``input``, dense float32 ``(T*B, C)``
     (``io.Supervision.posteriors``): the soft reference of ``den_expected_accuracy_dense``; with ``pdf_class`` pooled by class

@@ -579,6 +579,80 @@ class DenominatorGraph:
                     grad.view(T, B, P)[:, s0:s0 + n].copy_(gg.view(T, n, P))
         return grad
 
+    def sample_paths(self, nnet_output, num_samples, frames=None, leaky_hmm_coefficient=1e-5, generator=None, uniforms=None,
+                     return_states=False, max_workspace_bytes=1 << 30, workspace=None, n_batch=None):
+        """``num_samples`` paths a sequence drawn from this graph's path posterior under ``nnet_output``
+        (``tc_den_sample_paths``): exact samples of ``P(path | y)`` of the denominator's own model -- outputs clamped to
+        +-30, the graph's initial probabilities, every state final and the leaky-HMM transitions.  It is ``best_path`` with
+        draws where that one maximises.  Returns ``pdfs``, int32 ``(B, K, Tmax)``, 0-based, or with ``return_states``
+        ``(pdfs, states)``, ``states`` int32 ``(B, K, Tmax + 1, 2)``: the state a path entered level ``t`` in and the one it
+        left it from, which differ where a leak happened.  ``-1`` in padding slots, and everywhere for a sequence with a NaN
+        or an infinity in its valid frames or whose forward pass under- or overflows.
+
+        The random numbers are an input: ``uniforms``, float32 ``(B, K, Tmax + 1, 3)`` in ``[0, 1)`` on the output's device
+        (``include/torchain_hip.h`` says which decision each one takes), or ``None`` for
+        ``torch.rand((B, K, Tmax + 1, 3), generator=generator, device=...)``.  A sample depends on its sequence's rows of
+        ``nnet_output``, on its own uniforms, the graph and the coefficient alone.
+
+        ``nnet_output``, ``frames`` and ``n_batch`` are ``best_path``'s: contiguous ``(B, C, T)`` float32 / bfloat16 / float16
+        or 2-D float32 ``(T*B, C)`` (row ``t*B + b``); anything that is not 2-D float32 is copied into such a matrix first
+        (``tc_rows_gather``).  Shapes, dtypes and lengths are checked here, before any library call.  The call keeps every
+        state's forward probability of every frame, ``(Tmax + 1) * 4 * (states rounded up to 4)`` bytes a sequence; beyond
+        ``max_workspace_bytes`` (or the size of ``workspace``, a CUDA uint8 tensor to reuse) consecutive groups of sequences
+        run one after the other with the bits of one call.  Asynchronous on the current stream; no autograd:
+        ``functions.sampled_risk_surrogate`` turns the samples and their risks into a gradient."""
+        who = "sample_paths"
+        x, B, T, lengths = self._accuracy_arguments(who, nnet_output, frames, n_batch)
+        P, device = self.n_pdf, x.device
+        if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or int(num_samples) < 1:
+            raise ValueError("%s: num_samples must be an int >= 1, got %r" % (who, num_samples))
+        K = int(num_samples)
+        leaky = float(leaky_hmm_coefficient)
+        if not (0.0 <= leaky < float("inf")):
+            raise ValueError("%s: the leaky-HMM coefficient must be finite and >= 0, got %r" % (who, leaky))
+        if uniforms is not None:
+            if generator is not None:
+                raise ValueError("%s: give `uniforms` or `generator`, not both" % who)
+            if not isinstance(uniforms, torch.Tensor) or uniforms.device != device or uniforms.dtype != torch.float32:
+                raise ValueError("%s: uniforms must be a float32 tensor on the output's device (%s)" % (who, device))
+            if tuple(uniforms.shape) != (B, K, T + 1, 3):
+                raise ValueError("%s: uniforms of shape %s are not (%d, %d, %d, 3)" % (who, tuple(uniforms.shape), B, K, T + 1))
+        elif generator is not None and not isinstance(generator, torch.Generator):
+            raise TypeError("%s: generator must be a torch.Generator, got %s" % (who, type(generator).__name__))
+        if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8
+                                      or workspace.device != device or not workspace.is_contiguous()):
+            raise ValueError("%s: workspace must be a contiguous uint8 tensor on the output's device" % who)
+        need = lambda n: int(lib.tc_den_sample_paths_workspace_bytes(self.ptr, n, T))  # noqa: E731  (host arithmetic only)
+        cap = int(max_workspace_bytes) if workspace is None else min(int(max_workspace_bytes), workspace.numel())
+        group = B
+        if need(B) > cap:
+            if need(1) > cap:
+                raise ValueError("%s: one sequence needs %d bytes of workspace, %d are allowed" % (who, need(1), cap))
+            group = max(1, min(B, cap // need(1)))
+            while need(group) > cap:
+                group -= 1
+            while group < B and need(group + 1) <= cap:  # (the sizes are rounded up: as many sequences as fit)
+                group += 1
+        fr = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            u = uniforms.detach().contiguous() if uniforms is not None else torch.rand((B, K, T + 1, 3), generator=generator,
+                                                                                       device=device)
+            y2d = self._accuracy_rows(x, B, T, stream)
+            pdfs = torch.empty((B, K, T), dtype=torch.int32, device=device)
+            states = torch.empty((B, K, T + 1, 2), dtype=torch.int32, device=device) if return_states else None
+            ws = workspace if workspace is not None else torch.empty(need(group), dtype=torch.uint8, device=device)
+            for s0 in range(0, B, group):
+                n = min(group, B - s0)
+                yg = _group_rows(y2d, s0, n, B, T)
+                check(lib.tc_den_sample_paths(self.ptr, n, C.c_void_p(yg.data_ptr()), n * T, P, yg.stride(0),
+                                              None if fr is None else C.c_void_p(fr[s0:s0 + n].data_ptr()), T, leaky, K,
+                                              C.c_void_p(u[s0:s0 + n].data_ptr()), C.c_void_p(pdfs[s0:s0 + n].data_ptr()),
+                                              None if states is None else C.c_void_p(states[s0:s0 + n].data_ptr()),
+                                              C.c_void_p(ws.data_ptr()), ws.numel(), device.index, stream),
+                      "tc_den_sample_paths")
+        return (pdfs, states) if return_states else pdfs
+
 
 def _group_rows(m, s0, n, B, T):
     """Sequences ``s0 .. s0 + n - 1`` of a frame-major matrix ``(T*B, C)`` with unit column stride as a matrix ``(T*n, C)`` of
