@@ -368,7 +368,9 @@ struct TiedSeq {
 #endif
     TC_STAMP(0)
     Chunk6 q0;
-    load_chunk(q0, fbase, lane16, RESF);  // (past a short stream: readable padding, never processed)
+    // (past a short stream -- RESF = kTiedMinChunks, the full-layout twin, on a wave of the minimum: chunk fnch -- the next
+    // wave's first chunk or the array's readable padding, inside the descriptor's fnch + 2 chunks, never processed)
+    load_chunk(q0, fbase, lane16, RESF);
     __syncthreads();  // alpha'_{t-1}, exp(y_{t-1}) ready; gamma zero
     TC_STAMP(1)
     f4 yreg[PV];

@@ -62,6 +62,14 @@ __global__ __launch_bounds__(kThreads) void den_tied_kernel(const DenParams p) {
 #ifndef TC_RESB
 #define TC_RESB 4
 #endif
+// The full-layout twin's forward phase.  The kernel's register count is set by the backward phase, which holds next to
+// its resident chunks and the two stream buffers the owned states' beta and alpha' and two rows of y; the forward phase
+// holds the chunks, the buffers and one row of y, so 24 registers of every thread -- two chunks -- lie idle for its
+// frames.  Only the twin can take them: it compiles to 128 VGPRs without a spill, where the general form, at 128 with 4
+// spilled already, would spill 15 (profiles/fwd_resident/README.md).  RESB stays: the backward phase has none left.
+#ifndef TC_RESF_FULL
+#define TC_RESF_FULL 6
+#endif
 #ifndef TC_RES_JV3
 #define TC_RES_JV3 4
 #endif
@@ -85,9 +93,12 @@ int launch_jp(const DenParams &p, int accumulate, size_t lds_bytes, hipStream_t 
     k = al ? den_tied_kernel<JV, PV, true, false, true, RF, RB, RAGGED> : den_tied_kernel<JV, PV, false, false, true, RF, RB, RAGGED>;
   // The full-layout twin exists for 8 states per thread and one plane of pdfs (the C2 / C3 class); the other layout
   // classes would each add two instantiations of the largest kernel of the library.
+  // It keeps TC_RESF_FULL forward chunks resident, not RF: what its forward phase leaves idle of the registers its backward
+  // phase needs is two more chunks, and without the general form's spills it has the room (see TC_RESF_FULL above).
   if constexpr (JV == kJvSmall && PV == kPvSmall && !RAGGED) {
     if (tied_full_layout(p)) {
-      k = accumulate ? den_tied_kernel<JV, PV, true, true, true, RF, RB, false, true> : den_tied_kernel<JV, PV, true, false, true, RF, RB, false, true>;
+      constexpr int RFF = TC_RESF_FULL;
+      k = accumulate ? den_tied_kernel<JV, PV, true, true, true, RFF, RB, false, true> : den_tied_kernel<JV, PV, true, false, true, RFF, RB, false, true>;
       count_launch(kCntTiedFullLayout);
     }
   }
@@ -100,6 +111,7 @@ int launch_jp(const DenParams &p, int accumulate, size_t lds_bytes, hipStream_t 
 }  // namespace
 
 static_assert(TC_RESF <= kTiedMinChunks && TC_RESB <= kTiedMinChunks, "the resident prefix must exist in every wave's stream");
+static_assert(TC_RESF_FULL <= kTiedMinChunks && TC_RESF_FULL % 2 == 0, "the resident prefix must exist in every wave's stream");
 
 // Whether a launch takes the full-layout twin: everything TiedSeq<..., FULL> takes for granted, checked here.
 //   * 8 states per thread and one plane of pdfs, every float4 of both in use (8192 positions, 4096 pdfs);
