@@ -930,6 +930,68 @@ int tc_den_sample_paths(tc_den_graph *g, int32_t S, const float *nnet_output, in
                         int32_t *pdf_dev /* [S][K][T] */, int32_t *state_dev /* nullable, [S][K][T+1][2]: pre, post */,
                         void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
+ * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token
+ * sequences and scores each against its sequence's reference by the unit-cost Levenshtein distance: the risk of a
+ * minimum-expected-edit-distance step and the errors of a free decoding, without a copy to the host.
+ *
+ * The tokens of a path.  pdf[s][k][t] is int32 [S][K][max_frames] (K = 1 for tc_den_best_path); sequence s has T_s =
+ * seq_frames_dev[s] frames (clamped to 0 .. max_frames; null: max_frames each) and frames t >= T_s are never read.
+ * token_of_pdf is int32 [P], pdf -> token id, a negative value meaning that the pdf emits nothing (silence);
+ * start_of_pdf is uint8 [P] or null.  With c_t = token_of_pdf[pdf_t]:
+ *   collapse mode (start_of_pdf null): frame t emits c_t iff c_t >= 0 && (t == 0 || c_t != c_{t-1}).  c_{t-1} is the frame
+ *                  before's value whether or not that frame emitted: `a SIL a` gives `a a`, `a a` gives `a`.
+ *   start mode   : frame t emits c_t iff c_t >= 0 && start_of_pdf[pdf_t] != 0 -- the chain topology's split into a forward
+ *                  pdf and a self-loop pdf; it keeps `a a` apart.
+ * The emitted values in frame order are the hypothesis h[0 .. N).  A path with a valid frame whose pdf lies outside
+ * 0 .. P - 1 (the -1 of a failed sequence among them) is a failed path: len = -1, dist = -1 and -1 in every token slot.
+ * The distance.  ref is int32 [S][max_ref], ref_len int32 [S] with M_s = ref_len[s] clamped to 0 .. max_ref; tokens compare
+ * as plain integers; dist = the least number of insertions, deletions and substitutions that turn h[0 .. N) into
+ * ref[s][0 .. M_s).  Integer arithmetic throughout: there is one answer.
+ *   dist_dev, len_dev : device int32 [S][K]: the distance and N.
+ *   tokens_dev  : nullable, device int32 [S][K][max_frames]: h, then -1.  When it is null the hypotheses lie in `workspace`
+ *                 (tc_paths_edit_distance_workspace_bytes(S, K, max_frames) = 4 * S * K * max_frames rounded up to 256,
+ *                 16-byte aligned), which is otherwise not looked at.
+ *   max_ref     : 0 .. 4096.  With max_ref = 0, ref_dev and ref_len_dev may be null and dist = N: the tokens alone.
+ * A path's outputs depend on its own row, its sequence's reference and the two maps alone: not on S, K or its place.
+ * One launch, one wavefront a path, four independent wavefronts a workgroup; the previous row of the dynamic programme and
+ * the reference lie in LDS (8 * max_ref rounded up to 64 bytes a wavefront).  Nothing is allocated, nothing is atomic; the
+ * call is asynchronous on `stream` and may be captured.  "path_edit_launches" counts the launches.
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null pdf_dev, token_of_pdf_dev, dist_dev or len_dev; ref_dev or
+ * ref_len_dev null with max_ref > 0; S, K, max_frames or P <= 0; max_ref < 0; a pointer that is not 4-byte aligned.
+ * TC_ERR_UNSUPPORTED, before any device call: max_ref > 4096; S * K >= 2^31.  TC_ERR_WORKSPACE: tokens_dev null and the
+ * workspace null, short or misaligned. */
+int64_t tc_paths_edit_distance_workspace_bytes(int32_t S, int32_t K, int32_t max_frames);
+int tc_paths_edit_distance(int32_t S, int32_t K, const int32_t *pdf_dev /* [S][K][T] */,
+                           const int32_t *seq_frames_dev /* nullable */, int32_t max_frames,
+                           const int32_t *token_of_pdf_dev /* [P] */, const uint8_t *start_of_pdf_dev /* nullable, [P] */,
+                           int32_t P, const int32_t *ref_dev /* [S][max_ref] */, const int32_t *ref_len_dev /* [S] */,
+                           int32_t max_ref, int32_t *dist_dev /* [S][K] */, int32_t *len_dev /* [S][K] */,
+                           int32_t *tokens_dev /* nullable, [S][K][T] */, void *workspace, int64_t workspace_bytes, int device,
+                           void *stream);
+
+/* tc_sampled_risk_grad: the gradient of sum_s grad_output[s] * L_s in the network output, L_s the surrogate of sampled
+ * risks (functions.sampled_risk_surrogate):  L_s = sum_k weight[s][k] * sum_{t < T_s} clamp(y_s,t, +-30)[pdf[s][k][t]].
+ * It clears the gradient (one memset of grad_elems elements) and launches one kernel.  For every (s, t < T_s) one thread
+ * walks k = 0 .. K - 1; the first k to name a pdf owns the element (s, pdf, t) and stores, with one plain store,
+ *     the double sum, in k order, of grad_output[s] * weight[s][k] (a double product) over the k whose sample has that
+ *     pdf at t, rounded once to the element type (to nearest even, from the double),
+ * provided that the pdf lies in 0 .. num_pdfs - 1 and -30 <= y <= 30 (inclusive, as clamp's backward; a NaN fails).  Every
+ * other element is +0.  No atomics: the bits are a function of the inputs.
+ *   pdf_dev [S][K][max_frames] int32; seq_frames_dev nullable [S] (clamped to 0 .. max_frames); weight_dev [S][K] and
+ *   grad_output_dev [S] float64; input / grad: TC_DTYPE_* elements, element (s, c, t) at s * stride_s + c * stride_c +
+ *   t * stride_t ((B, C, T) tensors by their strides; a 2-D (T*B, C) matrix has stride_s = its row stride and stride_t =
+ *   B row strides).  grad is a block of grad_elems elements that holds every (s, c, t) at distinct places.
+ * "sampled_risk_grad_launches" counts the launches.  TC_ERR_INVALID_ARGUMENT, before any device call: a null pdf_dev,
+ * weight_dev, grad_output_dev, input or grad; S, K, max_frames or num_pdfs <= 0; an unknown dtype; a negative input
+ * stride, a gradient stride <= 0 or a gradient element beyond grad_elems; a misaligned pointer.  TC_ERR_UNSUPPORTED:
+ * K > 1024 (a thread compares its frame's K pdfs pairwise). */
+int tc_sampled_risk_grad(int32_t S, int32_t K, int32_t max_frames, int32_t num_pdfs, const int32_t *pdf_dev,
+                         const int32_t *seq_frames_dev /* nullable */, const double *weight_dev /* [S][K] */,
+                         const double *grad_output_dev /* [S] */, const void *input, int dtype, int64_t input_stride_s,
+                         int64_t input_stride_c, int64_t input_stride_t, void *grad, int64_t grad_stride_s,
+                         int64_t grad_stride_c, int64_t grad_stride_t, int64_t grad_elems, int device, void *stream);
+
 /* ---- the denominator graph's weights on caller-built supervisions ------------------------------------------------------
  * Every supervision Kaldi writes into an eg has been composed with the normalization FST of den.fst ([K]
  * AddWeightToSupervisionFst, DenominatorGraph::GetNormalizationFst; the end-to-end egs: --normalization-fst-scale), which
@@ -1152,7 +1214,9 @@ int tc_debug_set(const char *key, int value);
  * that kept the per-frame vectors in the workspace; "den_accuracy_dense_launches" and "den_accuracy_dense_grad_launches" =
  * those of the first two that came through tc_den_expected_accuracy_dense and tc_den_expected_accuracy_dense_grad;
  * "den_sample_launches" = tc_den_sample_paths calls that launched their kernel (not counted in "den_launches"), and
- * "den_sample_streamed_launches" those of them that formed the previous frame's alpha' from the workspace.
+ * "den_sample_streamed_launches" those of them that formed the previous frame's alpha' from the workspace;
+ * "path_edit_launches" = tc_paths_edit_distance calls that launched their kernel, "sampled_risk_grad_launches" = those of
+ * tc_sampled_risk_grad.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

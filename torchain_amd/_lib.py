@@ -227,6 +227,13 @@ def _load():
     L.tc_den_sample_paths_workspace_bytes.argtypes = [vp, i32, i32]
     L.tc_den_sample_paths.restype = C.c_int
     L.tc_den_sample_paths.argtypes = [vp, i32, vp, i64, i32, i64, vp, i32, f32, i32, vp, vp, vp, vp, i64, C.c_int, vp]
+    L.tc_paths_edit_distance_workspace_bytes.restype = i64
+    L.tc_paths_edit_distance_workspace_bytes.argtypes = [i32, i32, i32]
+    L.tc_paths_edit_distance.restype = C.c_int
+    L.tc_paths_edit_distance.argtypes = [i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i64, C.c_int, vp]
+    L.tc_sampled_risk_grad.restype = C.c_int
+    L.tc_sampled_risk_grad.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_int, i64, i64, i64, vp, i64, i64, i64, i64,
+                                       C.c_int, vp]
     L.tc_den_graph_arcs.restype = C.c_int
     L.tc_den_graph_arcs.argtypes = [vp, vp, vp, vp, vp]
     L.tc_den_compose.restype = C.c_int

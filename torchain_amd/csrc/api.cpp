@@ -737,6 +737,92 @@ int tc_den_sample_paths(tc_den_graph *g, int32_t S, const float *y, int64_t rows
   return launch_den_sample_paths(p, (hipStream_t)stream_v);
 }
 
+int64_t tc_paths_edit_distance_workspace_bytes(int32_t S, int32_t K, int32_t max_frames) {
+  if (S <= 0 || K <= 0 || max_frames <= 0) return TC_ERR_INVALID_ARGUMENT;
+  return path_edit_workspace_bytes(S, K, max_frames);
+}
+
+int tc_paths_edit_distance(int32_t S, int32_t K, const int32_t *pdf_dev, const int32_t *seq_frames_dev, int32_t max_frames,
+                           const int32_t *token_of_pdf_dev, const uint8_t *start_of_pdf_dev, int32_t P, const int32_t *ref_dev,
+                           const int32_t *ref_len_dev, int32_t max_ref, int32_t *dist_dev, int32_t *len_dev,
+                           int32_t *tokens_dev, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!pdf_dev || !token_of_pdf_dev || !dist_dev || !len_dev || S <= 0 || K <= 0 || max_frames <= 0 || P <= 0 || max_ref < 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  if (max_ref > 0 && (!ref_dev || !ref_len_dev)) return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)pdf_dev | (uintptr_t)seq_frames_dev | (uintptr_t)token_of_pdf_dev | (uintptr_t)ref_dev |
+        (uintptr_t)ref_len_dev | (uintptr_t)dist_dev | (uintptr_t)len_dev | (uintptr_t)tokens_dev) & 3) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  if (max_ref > kPathEditMaxRef || (int64_t)S * K > ((int64_t)1 << 31) - 1) return TC_ERR_UNSUPPORTED;
+  if (!tokens_dev && (!workspace || path_edit_workspace_bytes(S, K, max_frames) > workspace_bytes || !aligned16(workspace)))
+    return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  PathEditParams p;
+  p.pdf = pdf_dev;
+  p.seq_frames = seq_frames_dev;
+  p.token_of_pdf = token_of_pdf_dev;
+  p.start_of_pdf = start_of_pdf_dev;
+  p.ref = ref_dev;
+  p.ref_len = ref_len_dev;
+  p.dist = dist_dev;
+  p.len = len_dev;
+  p.tokens = tokens_dev ? tokens_dev : (int32_t *)workspace;
+  p.fill = tokens_dev ? 1 : 0;
+  p.paths = (int64_t)S * K;
+  p.K = K;
+  p.T = max_frames;
+  p.P = P;
+  p.max_ref = max_ref;
+  return launch_path_edit(p, (hipStream_t)stream_v);
+}
+
+int tc_sampled_risk_grad(int32_t S, int32_t K, int32_t max_frames, int32_t num_pdfs, const int32_t *pdf_dev,
+                         const int32_t *seq_frames_dev, const double *weight_dev, const double *grad_output_dev,
+                         const void *input, int dtype, int64_t input_stride_s, int64_t input_stride_c, int64_t input_stride_t,
+                         void *grad, int64_t grad_stride_s, int64_t grad_stride_c, int64_t grad_stride_t, int64_t grad_elems,
+                         int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!pdf_dev || !weight_dev || !grad_output_dev || !input || !grad || S <= 0 || K <= 0 || max_frames <= 0 || num_pdfs <= 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
+  const int elem = dtype == TC_DTYPE_F32 ? 4 : 2;
+  if (input_stride_s < 0 || input_stride_c < 0 || input_stride_t < 0 || grad_stride_s <= 0 || grad_stride_c <= 0 ||
+      grad_stride_t <= 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  // every element the kernel may store lies inside the block that is cleared
+  if (grad_elems <= 0 || grad_elems > INT64_MAX / 4) return TC_ERR_INVALID_ARGUMENT;
+  if ((__int128)(S - 1) * grad_stride_s + (__int128)(num_pdfs - 1) * grad_stride_c + (__int128)(max_frames - 1) * grad_stride_t >=
+      (__int128)grad_elems)
+    return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)pdf_dev | (uintptr_t)seq_frames_dev) & 3) != 0 || (((uintptr_t)weight_dev | (uintptr_t)grad_output_dev) & 7) != 0 ||
+      (((uintptr_t)input | (uintptr_t)grad) & (uintptr_t)(elem - 1)) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  if (K > kSampledRiskMaxSamples) return TC_ERR_UNSUPPORTED;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  hipStream_t stream = (hipStream_t)stream_v;
+  TC_HIP_CHECK(hipMemsetAsync(grad, 0, (size_t)grad_elems * elem, stream));
+  SampledRiskGradParams p;
+  p.pdf = pdf_dev;
+  p.seq_frames = seq_frames_dev;
+  p.weight = weight_dev;
+  p.grad_out = grad_output_dev;
+  p.input = input;
+  p.grad = grad;
+  p.in_s = input_stride_s;
+  p.in_c = input_stride_c;
+  p.in_t = input_stride_t;
+  p.g_s = grad_stride_s;
+  p.g_c = grad_stride_c;
+  p.g_t = grad_stride_t;
+  p.S = S;
+  p.K = K;
+  p.T = max_frames;
+  p.C = num_pdfs;
+  return launch_sampled_risk_grad(p, dtype, stream);
+}
+
 }  // extern "C"
 
 // deriv_scale = 1: the reference's outputs.  deriv_scale = -1: what its backward returns (tc_chain_objf_and_grad).

@@ -306,6 +306,38 @@ inline int64_t den_sample_workspace_bytes(int H, int S, int T) {
   return (((int64_t)S * den_sample_seq_floats(H, T) * 4) + 255) & ~(int64_t)255;
 }
 
+// Token sequences and edit distances of frame-level pdf paths (tc_paths_edit_distance, path_edit_kernels.hip)
+struct PathEditParams {
+  const int32_t *pdf;           // [paths][T]
+  const int32_t *seq_frames;    // [paths / K] nullable
+  const int32_t *token_of_pdf;  // [P]; negative: the pdf emits nothing
+  const uint8_t *start_of_pdf;  // [P] nullable: null selects collapse mode
+  const int32_t *ref;           // [paths / K][max_ref]; nullable when max_ref == 0
+  const int32_t *ref_len;       // [paths / K]; nullable when max_ref == 0
+  int32_t *dist, *len;          // [paths]
+  int32_t *tokens;              // [paths][T]: the caller's, or the workspace
+  int fill;                     // tokens is the caller's: -1 behind the hypothesis
+  int64_t paths;                // S * K
+  int K, T, P, max_ref;
+};
+constexpr int kPathEditWaves = 4;       // independent wavefronts a workgroup
+constexpr int kPathEditMaxRef = 4096;   // a wave's previous row and reference in LDS: 4 * 2 * 4096 * 4 bytes a workgroup
+inline size_t path_edit_lds_bytes(int max_ref) { return (size_t)kPathEditWaves * 2 * ((max_ref + 63) & ~63) * 4; }
+inline int64_t path_edit_workspace_bytes(int S, int K, int T) { return (((int64_t)S * K * T * 4) + 255) & ~(int64_t)255; }
+
+// The gradient of functions.sampled_risk_surrogate (tc_sampled_risk_grad, path_edit_kernels.hip); strides in elements
+struct SampledRiskGradParams {
+  const int32_t *pdf;         // [S][K][T]
+  const int32_t *seq_frames;  // [S] nullable
+  const double *weight;       // [S][K]
+  const double *grad_out;     // [S]
+  const void *input;
+  void *grad;
+  int64_t in_s, in_c, in_t, g_s, g_c, g_t;
+  int S, K, T, C;
+};
+constexpr int kSampledRiskMaxSamples = 1024;  // a thread compares its frame's K pdfs pairwise
+
 // LDS layout of the fused kernel, in floats: [P | A | ACC | GAMMA | ALPHA? | red | asum].  exp(y)
 // (P) starts at offset 0 and its region has the compile-time size PV * 4096 of the kernel
 // instantiation, so the gather source A (alpha' forward, beta backward) has a compile-time base.
@@ -693,6 +725,8 @@ int launch_den_accuracy_rows(const DenAccRowParams &p, bool dense, hipStream_t s
 int launch_den_accuracy_grad(const DenAccGradParams &p, bool dense, hipStream_t stream);
 int den_acc_tables(tc_den_graph *g, int device, DenAccDev *out);     // den_graph.cpp: made and uploaded on first use
 int launch_den_sample_paths(const DenSampleParams &p, hipStream_t stream);  // den_sample_kernels.hip
+int launch_path_edit(const PathEditParams &p, hipStream_t stream);      // path_edit_kernels.hip
+int launch_sampled_risk_grad(const SampledRiskGradParams &p, int dtype, hipStream_t stream);
 // dynamic LDS of num_e2e_kernel: two double score vectors, the frame's y per distinct pdf and one float per arc (max_arcs = 0:
 // of the kernels that keep no arc occupations on chip, num_e2e_large_kernel and num_e2e_best_path_kernel)
 inline size_t num_e2e_lds_bytes(int max_states, int max_arcs, int max_pdfs) {
@@ -834,7 +868,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -940,7 +940,164 @@ def den_sample_paths(input, den_graph, num_samples, frames=None, leaky_hmm_coeff
                                       max_workspace_bytes=max_workspace_bytes, workspace=workspace, n_batch=n_batch)
 
 
-def sampled_risk_surrogate(input, pdfs, risks, frames=None):
+def _int_vector(who, name, v, n, device, dtype=torch.int32):
+    """``v`` as a contiguous ``(n,)`` tensor of ``dtype`` on ``device`` (a tensor already there is not brought to the host)."""
+    t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)
+    if t.dim() != 1 or int(t.shape[0]) != n or t.is_floating_point() or t.is_complex():
+        raise ValueError("%s: %s must be %d integers, got shape %s of %s" % (who, name, n, tuple(t.shape), t.dtype))
+    return t.detach().to(device=device, dtype=dtype).contiguous()
+
+
+def _path_edit(who, pdfs, token_of_pdf, refs, ref_lengths, starts, frames, want_tokens):
+    if not isinstance(pdfs, torch.Tensor) or pdfs.dim() not in (2, 3) or pdfs.dtype not in (torch.int32, torch.int64):
+        raise ValueError("%s: pdfs must be an int32 or int64 tensor (B, K, Tmax) or (B, Tmax)" % who)
+    squeeze = pdfs.dim() == 2
+    p3 = pdfs.detach().unsqueeze(1) if squeeze else pdfs.detach()
+    B, K, T = (int(v) for v in p3.shape)
+    if B < 1 or K < 1 or T < 1:
+        raise ValueError("%s: pdfs of shape %s have an empty axis" % (who, tuple(pdfs.shape)))
+    device = pdfs.device
+    if p3.dtype == torch.int64:  # (a value beyond int32 stays outside 0 .. P - 1)
+        p3 = p3.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    p3 = p3.contiguous()
+    tok_map = token_of_pdf if isinstance(token_of_pdf, torch.Tensor) else torch.as_tensor(token_of_pdf)
+    if tok_map.dim() != 1 or int(tok_map.shape[0]) < 1:
+        raise ValueError("%s: token_of_pdf must be a vector of P >= 1 token ids" % who)
+    P = int(tok_map.shape[0])
+    tok_map = _int_vector(who, "token_of_pdf", tok_map, P, device)
+    st = None
+    if starts is not None:
+        st = starts if isinstance(starts, torch.Tensor) else torch.as_tensor(starts)
+        if st.dtype == torch.bool:
+            st = st.to(torch.uint8)
+        st = _int_vector(who, "starts", st, P, device, torch.uint8)
+    fr = None if frames is None else _int_vector(who, "frames", frames, B, device)
+    ref = ref_len = None
+    max_ref = 0
+    if refs is not None:
+        r = refs if isinstance(refs, torch.Tensor) else torch.as_tensor(refs)
+        if r.dim() != 2 or int(r.shape[0]) != B or r.is_floating_point() or r.is_complex():
+            raise ValueError("%s: refs must be (%d, max_ref) integers, got shape %s of %s" % (who, B, tuple(r.shape), r.dtype))
+        max_ref = int(r.shape[1])
+        if ref_lengths is None:  # (the one route that looks at values on the host)
+            neg = (r.detach() < 0).cpu()
+            if max_ref and bool((neg[:, :-1] & ~neg[:, 1:]).any()):
+                raise ValueError("%s: a reference has a token behind a negative entry; pass ref_lengths for other paddings" % who)
+            ref_len = (~neg).sum(dim=1).to(device=device, dtype=torch.int32)
+        else:
+            ref_len = _int_vector(who, "ref_lengths", ref_lengths, B, device)
+        ref = r.detach().to(device=device, dtype=torch.int32).contiguous()
+    elif ref_lengths is not None:
+        raise ValueError("%s: ref_lengths without refs" % who)
+    if max_ref > 4096:
+        raise ValueError("%s: references of up to 4096 tokens are supported, got max_ref = %d" % (who, max_ref))
+    if not pdfs.is_cuda:
+        raise ValueError("%s: pdfs must be on the GPU (there is no CPU path)" % who)
+    dist = torch.empty((B, K), dtype=torch.int32, device=device)
+    lens = torch.empty((B, K), dtype=torch.int32, device=device)
+    tokens = torch.empty((B, K, T), dtype=torch.int32, device=device) if want_tokens else None
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        ws = None if want_tokens else torch.empty(int(lib.tc_paths_edit_distance_workspace_bytes(B, K, T)), dtype=torch.uint8,
+                                                  device=device)
+        check(lib.tc_paths_edit_distance(B, K, _ptr(p3), _ptr(fr), T, _ptr(tok_map), _ptr(st), P,
+                                         _ptr(ref) if max_ref else None, _ptr(ref_len) if max_ref else None, max_ref,
+                                         _ptr(dist), _ptr(lens), _ptr(tokens), _ptr(ws), 0 if ws is None else ws.numel(),
+                                         device.index, stream), "tc_paths_edit_distance")
+    if squeeze:
+        dist, lens = dist[:, 0], lens[:, 0]
+        tokens = None if tokens is None else tokens[:, 0]
+    return dist, lens, tokens
+
+
+def path_edit_distance(pdfs, token_of_pdf, refs, ref_lengths=None, starts=None, frames=None, return_tokens=False):
+    """The token sequences of frame-level pdf paths and their edit distances to the references, on the device in one
+    launch (``tc_paths_edit_distance``): ``(dist, lengths)``, or with ``return_tokens`` ``(dist, lengths, tokens)``.
+
+    ``pdfs``: int32 or int64 ``(B, K, Tmax)`` -- ``den_sample_paths``' output -- or ``(B, Tmax)`` -- ``den_best_path``'s, the
+    outputs then lose the ``K`` axis; on the GPU.  ``token_of_pdf``: ``P`` ints, pdf -> token id, negative for a pdf that
+    emits nothing (silence).  With ``c_t = token_of_pdf[pdfs_t]``, frame ``t`` emits ``c_t`` iff ``c_t >= 0`` and
+
+    * ``starts is None`` (collapse): ``t == 0 or c_t != c_{t-1}``, whether or not frame ``t - 1`` emitted, so ``a SIL a``
+      gives ``a a`` and ``a a`` gives ``a``;
+    * ``starts`` (``P`` flags): ``starts[pdfs_t]`` -- the chain topology's forward pdf of a phone, as opposed to its
+      self-loop pdf; this keeps ``a a`` apart.
+
+    ``frames``: ``B`` lengths, ``None`` for ``Tmax`` each; frames beyond a length are not read.  ``refs``: ints ``(B,
+    max_ref)``, ``max_ref <= 4096``; ``ref_lengths``: ``B`` ints, or ``None`` for each row's count of leading non-negative
+    entries (a non-negative entry behind a negative one is a ``ValueError``).  That count is taken on the host: pass
+    ``ref_lengths`` -- and tensors on the device -- and the call makes no host synchronisation; lengths outside their range
+    are then clamped, not reported.  ``dist``, int32 ``(B, K)``: the unit-cost Levenshtein distance; ``lengths``: the
+    number of tokens; ``tokens``, int32 ``(B, K, Tmax)``: the tokens, then ``-1``.  A path with a pdf outside ``0 .. P - 1``
+    in its frames -- ``den_sample_paths``' ``-1`` of a failed sequence -- gets ``-1`` everywhere.  Integer arithmetic: the
+    results are exact.  A phone error rate of a free decoding is ``path_edit_distance(den_best_path(out, graph)[0],
+    phone_of_pdf, refs)[0].sum() / ref_tokens``.  No autograd."""
+    who = "path_edit_distance"
+    if refs is None:
+        raise ValueError("%s: refs is required (path_tokens gives the tokens alone)" % who)
+    if not isinstance(return_tokens, bool):
+        raise ValueError("%s: return_tokens must be a bool, got %r" % (who, return_tokens))
+    dist, lens, tokens = _path_edit(who, pdfs, token_of_pdf, refs, ref_lengths, starts, frames, return_tokens)
+    return (dist, lens, tokens) if return_tokens else (dist, lens)
+
+
+def path_tokens(pdfs, token_of_pdf, starts=None, frames=None):
+    """``(tokens, lengths)`` of frame-level pdf paths: ``path_edit_distance``'s launch without references (``max_ref = 0``),
+    with its arguments and its rule."""
+    dist, lens, tokens = _path_edit("path_tokens", pdfs, token_of_pdf, None, None, starts, frames, True)
+    return tokens, lens
+
+
+class _SampledRiskFused(Function):
+    """``sampled_risk_surrogate(..., fused=True)``: the value by the torch expression, the gradient by one memset and one
+    launch of ``tc_sampled_risk_grad``."""
+
+    @staticmethod
+    def forward(ctx, input, pdfs, risks, frames):
+        who = "sampled_risk_surrogate"
+        with torch.no_grad():
+            value = sampled_risk_surrogate(input, pdfs, risks, frames)  # (and every check of the arguments)
+        if not input.is_cuda:
+            raise ValueError("%s: fused=True needs the input on the GPU (there is no CPU path)" % who)
+        if input.dtype not in _STEP_DTYPES or (input.dim() == 2 and input.dtype != torch.float32):
+            raise ValueError("%s: fused=True takes (B, C, T) float32 / bfloat16 / float16 or 2-D float32, got %s %s"
+                             % (who, tuple(input.shape), input.dtype))
+        B, K, T = (int(v) for v in pdfs.shape)
+        device = input.device
+        r = torch.as_tensor(risks).detach().to(device=device, dtype=torch.float64)
+        ctx.weight = ((r - r.mean(dim=1, keepdim=True)) / (K - 1)).contiguous()
+        ctx.pdfs = pdfs.detach().to(device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+        ctx.frames = None if frames is None else _int_vector(who, "frames", frames, B, device)
+        ctx.save_for_backward(input)
+        return value
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (input,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        B, K, T = (int(v) for v in ctx.pdfs.shape)
+        device = input.device
+        go = grad_output.detach().to(device=device, dtype=torch.float64).contiguous()
+        grad = torch.empty(input.shape, dtype=input.dtype, device=device)
+        if input.dim() == 3:
+            P = int(input.shape[1])
+            in_strides = (input.stride(0), input.stride(1), input.stride(2))
+            g_strides = (grad.stride(0), grad.stride(1), grad.stride(2))
+        else:
+            P = int(input.shape[1])
+            in_strides = (input.stride(0), input.stride(1), B * input.stride(0))
+            g_strides = (grad.stride(0), grad.stride(1), B * grad.stride(0))
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            check(lib.tc_sampled_risk_grad(B, K, T, P, _ptr(ctx.pdfs), _ptr(ctx.frames), _ptr(ctx.weight), _ptr(go), _ptr(input),
+                                           _STEP_DTYPES[input.dtype], in_strides[0], in_strides[1], in_strides[2], _ptr(grad),
+                                           g_strides[0], g_strides[1], g_strides[2], grad.numel(), device.index, stream),
+                  "tc_sampled_risk_grad")
+        return grad, None, None, None
+
+
+def sampled_risk_surrogate(input, pdfs, risks, frames=None, fused=False):
     """A SURROGATE whose gradient in ``input`` is the unbiased sampling estimate of ``grad E[r(path)]``, the expected risk of
     the denominator graph's paths under ``input`` -- not an estimate of ``E[r]`` itself: its value means nothing.  Float64
     ``(B,)``, plain torch, differentiable in ``input``:
@@ -956,9 +1113,20 @@ def sampled_risk_surrogate(input, pdfs, risks, frames=None):
     ``pdfs >= 0``.  Training on a sequence-level risk, e.g. an edit distance to the transcript, is
 
         pdfs = den_sample_paths(out, graph, 8, generator=gen)
-        risks = torch.tensor([[edit_distance(phones_of(p), ref[b]) for p in pdfs[b].tolist()] for b in range(B)])
-        sampled_risk_surrogate(out, pdfs, risks).sum().backward()      # minimises the expected edit distance
+        risks, _ = path_edit_distance(pdfs, phone_of_pdf, refs, ref_lengths)   # on the device: no copy, no Python loop
+        sampled_risk_surrogate(out, pdfs, risks, fused=True).sum().backward()  # minimises the expected edit distance
+
+    ``fused=False`` (the default) leaves the gradient to autograd: a gather's backward, which scatters with atomics into a
+    dense gradient.  ``fused=True`` returns the same value through an ``autograd.Function`` whose backward is one memset and
+    one launch of ``tc_sampled_risk_grad``: per element the double sum over the samples, in sample order, rounded once to the
+    input's dtype -- no atomics, the same bits at every call (autograd's route rounds every sample's term to the input's
+    dtype and adds them in an order it does not fix).  It takes ``(B, C, T)`` float32 / bfloat16 / float16 by its strides
+    and 2-D float32, on the GPU; anything else is a ``ValueError``, not another route.
     """
+    if not isinstance(fused, bool):
+        raise ValueError("sampled_risk_surrogate: fused must be a bool, got %r" % (fused,))
+    if fused:
+        return _SampledRiskFused.apply(input, pdfs, risks, frames)
     if not isinstance(input, torch.Tensor) or input.dim() not in (2, 3) or not input.is_floating_point():
         raise ValueError("sampled_risk_surrogate: input must be a floating-point (B, C, T) or (T*B, C) tensor")
     if not isinstance(pdfs, torch.Tensor) or pdfs.dim() != 3 or pdfs.dtype not in (torch.int32, torch.int64):
