@@ -648,6 +648,68 @@ int tc_chain_step_log_softmax(tc_den_graph *graph, tc_supervision *supervision, 
                               int64_t workspace_bytes, int device, void *stream, int isolate_failures,
                               double *seq_results_dev, int xent_log_softmax);
 
+/* Boosted LF-MMI (bMMI; Povey et al. 2008, the lattice-free form of [K]'s discriminative --boost): tc_chain_step_log_softmax
+ * with an accuracy margin on the denominator.  Every denominator path's weight is multiplied by exp(-boost * A(path)), A the
+ * path's frame accuracy against a reference, so a competitor must be beaten by a margin that grows with its error.  Frame
+ * accuracy is additive over frames: the boost is a shift of the DENOMINATOR'S input alone.
+ *   a_t(j)    : exactly tc_den_expected_accuracy's.  Hard form: ref_pdfs_dev, device int32[S * T], entry s * T + t;
+ *               a = 1 iff 0 <= ref_t < P and class(j) == class(ref_t), else 0 (-1 or any out-of-range entry: the frame scores
+ *               nothing); pdf_class_dev NULL (identity) or device int32[P].  Dense form: accuracy, device float32 (T*S, P),
+ *               row t*S + s, rows accuracy_row_stride >= P floats apart, any finite values.  Exactly one of ref_pdfs_dev /
+ *               accuracy is given; pdf_class_dev goes with ref_pdfs_dev only.  Both are constants: no gradient flows into them.
+ *   y_b       : float32 with two roundings.  y32 the input widened exactly, b32 = boost:
+ *                   y_b = fl32(y32 - fl32(b32 * a))            (__fmul_rn, __fsub_rn: never one FMA)
+ *               The hard form is the dense form on the float32 indicator.
+ *   who sees it : the denominator alone runs on y_b, with its usual clamp of exp() at +-30 applied to y_b.  The numerator, the
+ *               l2 term and its gradient -l2 * weight * y, the out-of-range penalty, deriv_weights and the cross-entropy
+ *               branch act on the true y:
+ *                   objf = weight * (num_logprob(y) - den_logprob(y_b))
+ *                   grad = weight * (gamma_num(y) - gamma_den(y_b)) - l2 * weight * y, then penalty and row weights.
+ *               results_dev3, loss_dev1, xent_objf_dev and seq_results_dev keep their layout; den_logprob is the boosted
+ *               denominator's.  The objective is no longer bounded by 0: for a in [0, 1] and boost >= 0 on a composed
+ *               supervision it is bounded by weight * boost * sum_s T_s.
+ *   edges     : boost must be finite (negative allowed); a ragged handle's entries and rows of frames t >= T_s are never read
+ *               and its padding gradients are +0; a non-finite accuracy value in a sequence's valid frames behaves as a
+ *               non-finite network output there would (the soft failure of the minibatch, or of that sequence alone with
+ *               isolate_failures); grad == NULL is the boosted evaluation step.  kaldi_way == 0 with the xent branch active:
+ *               TC_ERR_INVALID_ARGUMENT, as xent_log_softmax.  TC_ERR_INVALID_ARGUMENT also for a boost that is not finite,
+ *               both or neither reference, classes without ref_pdfs_dev, pointers not 4-byte aligned, accuracy_row_stride < P.
+ *               Callers send boost == 0 to tc_chain_step_log_softmax: this entry runs its passes whatever the value.
+ *   how       : one streaming pass (boost_kernels.hip) forms y_b, frame-major float32, from the caller's tensor where it lies
+ *               -- in place of the plain copy of a (B, C, T) step, beside the gather / widening of the others -- in front of
+ *               the denominator.  The denominator kernels fold the l2 term of the matrix they read into their passes; with
+ *               l2_regularize != 0 two small launches put it back on the true y: sum(y^2) = sum(y_b^2) + sum(2 y_b d + d^2)
+ *               per sequence (doubles, fixed order) and grad -= l2_scale * d, d = fl32(b32 * a), over the elements with
+ *               d != 0 (S * T of them for a hard reference without classes).  tc_debug_counter("boost_launches") counts all.
+ * Workspace: tc_chain_step_boosted_workspace_bytes = tc_chain_step_log_softmax_workspace_bytes plus, for every layout but
+ * TC_LAYOUT_BCT, one more num_sequences * frames_per_sequence * P float32 matrix (rounded up to 256 bytes): a 2-D or
+ * channel-last step keeps the true y where the numerator reads it.  No host synchronisation, nothing allocated; the reference
+ * and the accuracy are read where they lie, so a captured step replays on their current values.  The split entries and the
+ * torch.library operator do not take the option. */
+int64_t tc_chain_step_boosted_workspace_bytes(const tc_den_graph *graph, int32_t num_sequences, int32_t frames_per_sequence,
+                                              int layout, int with_xent, int dtype);
+int tc_chain_step_boosted(tc_den_graph *graph, tc_supervision *supervision, const void *input, const void *xent_input,
+                          int layout, int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize,
+                          float leaky_hmm_coefficient, float xent_regularize, int kaldi_way, void *grad, void *xent_grad,
+                          float *results_dev3, float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
+                          float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
+                          void *stream, int isolate_failures, double *seq_results_dev, int xent_log_softmax, float boost,
+                          const int32_t *ref_pdfs_dev /* [S * T] or NULL */, const int32_t *pdf_class_dev /* nullable, [P] */,
+                          const float *accuracy /* (T*S, P) or NULL */, int64_t accuracy_row_stride);
+
+/* The boost pass alone: out2d[(t*S + s) * out_stride + c] = fl32(y32 - fl32(boost * a_t(c))), y32 element (s, c, t) of
+ * `input` widened -- TC_LAYOUT_ROWS (row t*S + s at row_stride elements), TC_LAYOUT_BCT (contiguous (S, C, T)) or
+ * TC_LAYOUT_CHANNEL_LAST (element at s * batch_stride + t * frame_stride + c), float32 / bfloat16 / float16.  a_t, boost and
+ * their checks are tc_chain_step_boosted's.  seq_frames_dev: NULL or device int32[S], the lengths T_s (held to 1 .. T): rows
+ * of frames t >= T_s read neither the reference nor the accuracy and receive the widened input.  16-byte accesses where
+ * every address allows them, scalar tails elsewhere; rows are addressed in 64 bits.  One launch, asynchronous on `stream`,
+ * counted in "boost_launches".  TC_ERR_UNSUPPORTED: a (B, C, T) shape beyond tc_to2d's grid. */
+int tc_boost_rows(const void *input, int dtype, int layout, int32_t S, int32_t C, int32_t T, int64_t row_stride,
+                  int64_t batch_stride, int64_t frame_stride, const int32_t *seq_frames_dev /* nullable */, float boost,
+                  const int32_t *ref_pdfs_dev /* [S * T] or NULL */, const int32_t *pdf_class_dev /* nullable, [C] */,
+                  const float *accuracy /* (T*S, C) or NULL */, int64_t accuracy_row_stride, float *out2d, int64_t out_stride,
+                  int device, void *stream);
+
 /* The benchmarked unit: [K] DenominatorComputation::Forward() + Backward(deriv_weight, deriv)
  * (direct use in the reference: src/chain-supervision-test.hpp:403-414).
  *   logprob_dev   : device double[1], sum over sequences of the denominator log-prob
@@ -1216,7 +1278,10 @@ int tc_debug_set(const char *key, int value);
  * "den_sample_launches" = tc_den_sample_paths calls that launched their kernel (not counted in "den_launches"), and
  * "den_sample_streamed_launches" those of them that formed the previous frame's alpha' from the workspace;
  * "path_edit_launches" = tc_paths_edit_distance calls that launched their kernel, "sampled_risk_grad_launches" = those of
- * tc_sampled_risk_grad.
+ * tc_sampled_risk_grad;
+ * "boost_launches" = launches of boost_kernels.hip: 1 a tc_boost_rows call; 1 a tc_chain_step_boosted call with
+ * l2_regularize == 0, 3 a training step and 2 an evaluation step with it (the pass, the sequences' sums, the gradient's
+ * fix-up); 0 for every other entry.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

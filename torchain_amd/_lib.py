@@ -169,6 +169,12 @@ def _load():
     L.tc_chain_step_log_softmax_workspace_bytes.argtypes = L.tc_chain_step_strided_workspace_bytes.argtypes
     L.tc_chain_step_log_softmax.restype = C.c_int
     L.tc_chain_step_log_softmax.argtypes = L.tc_chain_step_per_sequence.argtypes + [C.c_int]
+    L.tc_chain_step_boosted_workspace_bytes.restype = C.c_int64
+    L.tc_chain_step_boosted_workspace_bytes.argtypes = L.tc_chain_step_strided_workspace_bytes.argtypes
+    L.tc_chain_step_boosted.restype = C.c_int
+    L.tc_chain_step_boosted.argtypes = L.tc_chain_step_log_softmax.argtypes + [f32, vp, vp, vp, i64]
+    L.tc_boost_rows.restype = C.c_int
+    L.tc_boost_rows.argtypes = [vp, C.c_int, C.c_int, i32, i32, i32, i64, i64, i64, vp, f32, vp, vp, vp, i64, vp, i64, C.c_int, vp]
     L.tc_rows_gather.restype = C.c_int
     L.tc_rows_gather.argtypes = [vp, C.c_int, i32, i32, i32, i64, i64, vp, i64, C.c_int, vp]
     L.tc_rows_scatter.restype = C.c_int

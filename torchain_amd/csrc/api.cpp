@@ -849,6 +849,15 @@ struct ObjfStep {  // what only the one-call step passes: all unset for the two 
   // tc_chain_step_log_softmax: the row statistics of xent_out ([rows][2], launch_xent_row_stats); the numerator's
   // cross-entropy sums are then taken on the rows' log-softmax (NumParams::xent_lse)
   const float *xent_lse = nullptr;
+  // tc_chain_step_boosted: `y` is the denominator's private matrix y_b, scratch that this call fills in front of the
+  // denominator (boost_kernels.hip) from bct_input, or from the rows of boost_src (unit channel stride, element (s, c, t) at
+  // s * boost_sb + t * boost_st, of bct_dtype).  The numerator reads the true y: bct_input where it lies, else num_y.  The l2
+  // term is put back on the true y behind the denominator (the sequences' sums) and behind the soft-failure reset (deriv).
+  const BoostAcc *boost = nullptr;
+  const void *boost_src = nullptr;
+  int64_t boost_sb = 0, boost_st = 0;
+  const float *num_y = nullptr;
+  int64_t num_y_stride = 0;
 };
 
 static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int64_t rows, int32_t cols,
@@ -880,6 +889,15 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   if (rc != TC_OK) return rc;
   np.deriv_scale = deriv_scale;
   np.xent_scale = xent_scale;
+  if (o.boost && o.num_y) {
+    np.y = o.num_y;
+    np.y_stride = o.num_y_stride;
+  }
+  BoostAcc boost;
+  if (o.boost) {
+    boost = *o.boost;
+    boost.seq_frames = ragged ? np.seq_frames : nullptr;
+  }
   if (ragged) {
     dp.set_seq_frames(np.seq_frames);
     count_launch(kCntRagged);
@@ -899,6 +917,11 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
     np.elem = o.bct_dtype;  // (bct_input and a (B, C, T) xent_out: the caller's tensors, float32 or 16-bit)
   }
   auto fill_y = [&]() -> int {  // the frame-major copy the denominator reads
+    if (o.boost && o.bct_input)
+      return launch_boost_bct(o.bct_dtype, o.bct_input, const_cast<float *>(y), y_stride, sup->S, cols, sup->T, boost, stream);
+    if (o.boost)
+      return launch_boost_rows(o.bct_dtype, o.boost_src, o.boost_sb, o.boost_st, const_cast<float *>(y), y_stride, sup->S, sup->T,
+                               cols, boost, stream);
     return o.bct_input ? launch_to2d(o.bct_dtype, o.bct_input, const_cast<float *>(y), sup->S, cols, sup->T, y_stride, stream) : TC_OK;
   };
 
@@ -956,6 +979,11 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   }
   rc = supervision_mark_use(sup, device, stream);
   if (rc != TC_OK) return rc;
+  // (the boosted step: the denominator summed y_b^2; the l2 term is the true y's)
+  if (o.boost && l2_regularize != 0.0f) {
+    rc = launch_boost_l2_sum(y, y_stride, sup->S, sup->T, cols, boost, w.y2, stream);
+    if (rc != TC_OK) return rc;
+  }
   const double *xent_sums = (np.seq_xent || o.xent_sums_ready) && o.xent_objf_dev ? w.xent_lp : nullptr;
   if (o.isolate || o.seq_results)
     rc = launch_finalize_per_sequence(w.den_lp, w.num_lp, w.y2, w.ab, w.gs, sup->S, sup->T, wgt, l2_regularize, deriv != nullptr,
@@ -969,6 +997,9 @@ static int chain_objf(tc_den_graph *g, tc_supervision *sup, const float *y, int6
   // (a (B, C, T) xent tensor is rows * cols contiguous floats: cleared as such)
   rc = launch_zero_on_fail(w.fail, deriv, deriv_stride, xent, o.xent_bct ? (int64_t)cols : xent_stride, y, y_stride,
                            deriv_scale * (wgt * l2_regularize), rows, cols, stream);
+  // (the boosted step: the denominator, and the reset just now, wrote -l2_scale * y_b)
+  if (rc == TC_OK && o.boost && deriv && l2_regularize != 0.0f)
+    rc = launch_boost_l2_grad(deriv, deriv_stride, sup->S, sup->T, cols, boost, deriv_scale * (wgt * l2_regularize), stream);
   // ragged: +0 in the padding rows, which no kernel wrote (and the failure route just filled from y's padding)
   if (rc == TC_OK && ragged && !o.outputs_move_on) {
     if (deriv) rc = launch_zero_padding(deriv, 4, deriv_stride, (int64_t)sup->S * deriv_stride, 1, sup->S, sup->T, cols, np.seq_frames, stream);
@@ -1005,10 +1036,11 @@ struct StepWorkspace {
   char *chain, *trace;
   float *y2d, *g2d, *x2d, *xg;
   float *lse;  // tc_chain_step_log_softmax: xent_input's row statistics, [S * T][2] (behind everything the siblings carve)
+  float *yb;   // tc_chain_step_boosted: the denominator's matrix where y2d holds (or the caller's tensor is) the true y
   size_t chain_bytes, total;
 };
 StepWorkspace carve_step(char *base, const tc_den_graph *g, int S, int T, int P, bool three_d, bool xent,
-                         int dtype = TC_DTYPE_F32, bool log_softmax = false) {
+                         int dtype = TC_DTYPE_F32, bool log_softmax = false, bool boosted_rows = false) {
   StepWorkspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -1026,6 +1058,7 @@ StepWorkspace carve_step(char *base, const tc_den_graph *g, int S, int T, int P,
   w.x2d = copies && xent ? (float *)take(mat) : nullptr;
   w.xg = half && xent ? (float *)take(mat) : nullptr;
   w.lse = log_softmax && xent ? (float *)take((size_t)S * T * 2 * sizeof(float)) : nullptr;
+  w.yb = boosted_rows ? (float *)take(mat) : nullptr;
   w.total = off;
   return w;
 }
@@ -1136,12 +1169,14 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
                              float *loss_dev1, double *xent_objf_dev, const float *deriv_weights,
                              float out_of_range_regularize, int dtype, void *workspace, int64_t workspace_bytes, int device,
                              void *stream_v, int isolate_failures = 0, double *seq_results_dev = nullptr,
-                             int xent_log_softmax = 0) {
+                             int xent_log_softmax = 0, const BoostAcc *boost = nullptr) {
   if (!g || !sup || !input_v || !results_dev3 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
   // (with kaldi_way == 0 the whole objective is run again on xent_input: what a log-softmax in front of that means is
   // another question)
   if (xent_log_softmax && !kaldi_way) return TC_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)seq_results_dev & 7) != 0) return TC_ERR_INVALID_ARGUMENT;
+  // (the boosted step with kaldi_way == 0 and the xent branch: which of the two objective calls is boosted is another question)
+  if (boost && !kaldi_way && xent_input_v != nullptr && xent_regularize != 0.0f) return TC_ERR_INVALID_ARGUMENT;
   const bool cl = layout == TC_LAYOUT_CHANNEL_LAST;
   const int three_d = layout != TC_LAYOUT_ROWS;
   if (((uintptr_t)deriv_weights & 3) != 0) return TC_ERR_INVALID_ARGUMENT;
@@ -1177,7 +1212,10 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   // Kaldi's log-softmax at the end of the cross-entropy head, folded in (xent_softmax_kernels.hip): without the xent branch
   // the option does nothing
   const bool lsm = xent_log_softmax != 0 && use_xent;
-  const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype, lsm);
+  // (the boosted step's own matrix: a (B, C, T) step has y2d free for it; every other layout keeps the true y there or reads
+  // it in the caller's tensor.  Its workspace is sized with the row statistics whether the switch is on or not.)
+  const bool boosted_rows = boost != nullptr && layout != TC_LAYOUT_BCT;
+  const StepWorkspace w = carve_step((char *)workspace, g, S, T, P, three_d != 0, use_xent, dtype, lsm || boost != nullptr, boosted_rows);
   if (!workspace || (int64_t)w.total > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
   if (cl && !channel_last_strides_ok(S, T, P, sb, st)) return TC_ERR_INVALID_ARGUMENT;
   DeviceGuard guard(device);
@@ -1188,7 +1226,11 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   // here; what remains of the first is this library's own extra, the cross-entropy objective, which is defined on the
   // first call's xent_deriv: the numerator alone on `input` (no denominator, nothing written but the sequences' sums).
   const bool second_only = use_xent && !kaldi_way;
-  const StepIo io = step_io(w, layout, half, eval_only, second_only, use_xent, P, row_stride, input, xent_input, grad, xent_grad);
+  StepIo io = step_io(w, layout, half, eval_only, second_only, use_xent, P, row_stride, input, xent_input, grad, xent_grad);
+  if (boosted_rows) {  // the denominator's matrix; the numerator keeps io.num_in
+    io.y = w.yb;
+    io.y_stride = P;
+  }
   int rc = TC_OK;
 
   // ---- the way in
@@ -1249,6 +1291,16 @@ static int chain_step_layout(tc_den_graph *g, tc_supervision *sup, const void *i
   o.isolate = isolate_failures != 0;
   o.seq_results = seq_results_dev;
   o.xent_lse = lsm ? w.lse : nullptr;
+  if (boost) {
+    o.boost = boost;
+    if (boosted_rows) {
+      o.boost_src = input;
+      o.boost_sb = cl ? sb : row_stride;
+      o.boost_st = cl ? st : (int64_t)S * row_stride;
+      o.num_y = io.num_in;
+      o.num_y_stride = io.num_stride;
+    }
+  }
   rc = chain_objf(g, sup, io.y, rows, P, io.y_stride, results_dev3, io.gr, P, io.xg, P, l2_regularize, leaky, dscale, xscale,
                   w.chain, (int64_t)w.chain_bytes, device, stream_v, o);
   if (rc != TC_OK || eval_only) return rc;
@@ -1389,6 +1441,85 @@ int tc_chain_step_strided(tc_den_graph *g, tc_supervision *sup, const void *inpu
                                     leaky, xent_regularize, kaldi_way, grad_v, xent_grad_v, results_dev3, loss_dev1,
                                     xent_objf_dev, deriv_weights, out_of_range_regularize, dtype, workspace, workspace_bytes,
                                     device, stream_v, 0, nullptr);
+}
+
+// ---- boosted LF-MMI (boost_kernels.hip) -----------------------------------------------------------------------------
+// the two forms of a_t(j) as the entries take them: exactly one of (ref, accuracy); classes with the hard form only
+static bool boost_args_ok(float boost, const int32_t *ref, const int32_t *cls, const float *accuracy, int64_t accuracy_stride,
+                          int P) {
+  if (boost != boost || std::isinf(boost)) return false;
+  if ((ref != nullptr) == (accuracy != nullptr)) return false;
+  if (cls && !ref) return false;
+  if ((((uintptr_t)ref | (uintptr_t)cls | (uintptr_t)accuracy) & 3) != 0) return false;
+  return !accuracy || accuracy_stride >= P;
+}
+
+int64_t tc_chain_step_boosted_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T, int layout, int with_xent,
+                                              int dtype) {
+  if (layout != TC_LAYOUT_ROWS && layout != TC_LAYOUT_BCT && layout != TC_LAYOUT_CHANNEL_LAST) return TC_ERR_INVALID_ARGUMENT;
+  if (!g || S <= 0 || T <= 0 || !known_dtype(dtype)) return TC_ERR_INVALID_ARGUMENT;
+  return (int64_t)carve_step(nullptr, g, S, T, g->P, layout != TC_LAYOUT_ROWS, with_xent != 0, dtype, true, layout != TC_LAYOUT_BCT)
+      .total;
+}
+
+int tc_chain_step_boosted(tc_den_graph *g, tc_supervision *sup, const void *input_v, const void *xent_input_v, int layout,
+                          int64_t row_stride, int64_t batch_stride, int64_t frame_stride, float l2_regularize, float leaky,
+                          float xent_regularize, int kaldi_way, void *grad_v, void *xent_grad_v, float *results_dev3,
+                          float *loss_dev1, double *xent_objf_dev, const float *deriv_weights, float out_of_range_regularize,
+                          int dtype, void *workspace, int64_t workspace_bytes, int device, void *stream_v, int isolate_failures,
+                          double *seq_results_dev, int xent_log_softmax, float boost, const int32_t *ref_pdfs_dev,
+                          const int32_t *pdf_class_dev, const float *accuracy, int64_t accuracy_row_stride) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  if (!boost_args_ok(boost, ref_pdfs_dev, pdf_class_dev, accuracy, accuracy_row_stride, sup->P)) return TC_ERR_INVALID_ARGUMENT;
+  if (layout != TC_LAYOUT_ROWS && layout != TC_LAYOUT_BCT && layout != TC_LAYOUT_CHANNEL_LAST) return TC_ERR_INVALID_ARGUMENT;
+  const bool cl = layout == TC_LAYOUT_CHANNEL_LAST;
+  if (cl) {
+    if (!channel_last_strides_ok(sup->S, sup->T, sup->P, batch_stride, frame_stride)) return TC_ERR_INVALID_ARGUMENT;
+    const uintptr_t elem_mask = dtype == TC_DTYPE_F32 ? 3 : 1;
+    if ((((uintptr_t)input_v | (uintptr_t)xent_input_v | (uintptr_t)grad_v | (uintptr_t)xent_grad_v) & elem_mask) != 0)
+      return TC_ERR_INVALID_ARGUMENT;
+  }
+  BoostAcc a;
+  a.ref = ref_pdfs_dev;
+  a.cls = pdf_class_dev;
+  a.acc = accuracy;
+  a.acc_stride = accuracy_row_stride;
+  a.b = boost;
+  return chain_step_layout(g, sup, input_v, xent_input_v, layout, cl ? 0 : row_stride, cl ? batch_stride : 0,
+                           cl ? frame_stride : 0, l2_regularize, leaky, xent_regularize, kaldi_way, grad_v, xent_grad_v,
+                           results_dev3, loss_dev1, xent_objf_dev, deriv_weights, out_of_range_regularize, dtype, workspace,
+                           workspace_bytes, device, stream_v, isolate_failures, seq_results_dev, xent_log_softmax, &a);
+}
+
+int tc_boost_rows(const void *input, int dtype, int layout, int32_t S, int32_t Cn, int32_t T, int64_t row_stride,
+                  int64_t batch_stride, int64_t frame_stride, const int32_t *seq_frames_dev, float boost,
+                  const int32_t *ref_pdfs_dev, const int32_t *pdf_class_dev, const float *accuracy, int64_t accuracy_row_stride,
+                  float *out2d, int64_t out_stride, int device, void *stream_v) {
+  if (!input || !out2d || !known_dtype(dtype) || S <= 0 || Cn <= 0 || T <= 0 || out_stride < Cn) return TC_ERR_INVALID_ARGUMENT;
+  if (!boost_args_ok(boost, ref_pdfs_dev, pdf_class_dev, accuracy, accuracy_row_stride, Cn)) return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)input) & (dtype == TC_DTYPE_F32 ? 3 : 1)) != 0 || (((uintptr_t)out2d | (uintptr_t)seq_frames_dev) & 3) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  int64_t sb = batch_stride, st = frame_stride;
+  if (layout == TC_LAYOUT_ROWS) {
+    if (row_stride < Cn || row_stride > INT64_MAX / 4 / S) return TC_ERR_INVALID_ARGUMENT;
+    sb = row_stride;
+    st = (int64_t)S * row_stride;
+  } else if (layout != TC_LAYOUT_BCT && layout != TC_LAYOUT_CHANNEL_LAST) {
+    return TC_ERR_INVALID_ARGUMENT;
+  }
+  if (layout != TC_LAYOUT_BCT && !channel_last_strides_ok(S, T, Cn, sb, st)) return TC_ERR_INVALID_ARGUMENT;
+  if (layout == TC_LAYOUT_BCT && !layout_grid_ok(S, T)) return TC_ERR_UNSUPPORTED;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  BoostAcc a;
+  a.ref = ref_pdfs_dev;
+  a.cls = pdf_class_dev;
+  a.acc = accuracy;
+  a.acc_stride = accuracy_row_stride;
+  a.b = boost;
+  a.seq_frames = seq_frames_dev;
+  if (layout == TC_LAYOUT_BCT) return launch_boost_bct(dtype, input, out2d, out_stride, S, Cn, T, a, (hipStream_t)stream_v);
+  return launch_boost_rows(dtype, input, sb, st, out2d, out_stride, S, T, Cn, a, (hipStream_t)stream_v);
 }
 
 int tc_rows_gather(const void *in, int dtype, int32_t B, int32_t Cn, int32_t T, int64_t batch_stride, int64_t frame_stride,

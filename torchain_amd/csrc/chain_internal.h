@@ -853,6 +853,28 @@ int launch_xent_row_stats(int dtype, const void *x, int x_bct, int64_t x_stride,
 int launch_xent_softmax_grad(int dtype, const void *x, int x_bct, int64_t x_stride, float *g, int64_t g_stride, int S, int T,
                              int P, const float *stats, const int32_t *live_frames, hipStream_t stream);
 
+// boost_kernels.hip (tc_chain_step_boosted, tc_boost_rows): the denominator's private matrix y_b = fl32(y - fl32(b * a)) of
+// boosted LF-MMI, and the fix-up that keeps the l2 term on the true y.  BoostAcc is a_t(j) in one of its two forms -- the
+// hard reference (ref: [S * T], entry s * T + t; cls: nullable [P]) or the dense matrix (acc: row t*S + s, acc_stride floats
+// apart) -- with b = fl32(boost) and the lengths of a ragged batch (nullable): rows of frames >= seq_frames[s] read neither.
+struct BoostAcc {
+  const int32_t *ref = nullptr, *cls = nullptr;
+  const float *acc = nullptr;
+  int64_t acc_stride = 0;
+  float b = 0.0f;
+  const int32_t *seq_frames = nullptr;
+};
+// out[(t*S + s) * out_stride + c] = boosted(widen(x[s*sb + t*st + c])): rows with unit channel stride of `dtype`
+int launch_boost_rows(int dtype, const void *x, int64_t sb, int64_t st, float *out, int64_t out_stride, int S, int T, int cols,
+                      const BoostAcc &a, hipStream_t stream);
+// ... the same from a contiguous (B, C, T) tensor of `dtype` (layout_grid_ok's limits)
+int launch_boost_bct(int dtype, const void *in_bct, float *out, int64_t out_stride, int B, int Cn, int T, const BoostAcc &a,
+                     hipStream_t stream);
+// seq_y2[s] += sum(2 * y_b * d + d^2) and g -= l2_scale * d over the live elements with d = fl32(b * a) != 0
+int launch_boost_l2_sum(const float *yb, int64_t yb_stride, int S, int T, int P, const BoostAcc &a, double *seq_y2,
+                        hipStream_t stream);
+int launch_boost_l2_grad(float *g, int64_t g_stride, int S, int T, int P, const BoostAcc &a, float l2_scale, hipStream_t stream);
+
 extern thread_local int g_last_hip_error;
 
 // Diagnostic switches (tc_debug_set in the public header): process-wide, read when a graph is built.  They
@@ -868,7 +890,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

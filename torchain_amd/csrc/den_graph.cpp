@@ -466,7 +466,7 @@ int64_t tc_debug_counter(const char *key) {
   if (key && !strcmp(key, "pool_device_allocs")) return pool_counter(0);
   if (key && !strcmp(key, "pool_reuses")) return pool_counter(1);
   static const char *const names[kCntCount] = {"den_launches", "den_backward_launches", "num_launches", "num_backward_launches", "layout_launches",
-                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches", "den_sample_launches", "den_sample_streamed_launches", "path_edit_launches", "sampled_risk_grad_launches"};
+                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches", "den_sample_launches", "den_sample_streamed_launches", "path_edit_launches", "sampled_risk_grad_launches", "boost_launches"};
   for (int i = 0; key && i < kCntCount; ++i)
     if (!strcmp(key, names[i])) return g_launches[i].load(std::memory_order_relaxed);
   return -1;

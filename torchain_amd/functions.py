@@ -57,6 +57,24 @@ Same names, argument meaning, defaults and quirks as the reference:
   bits.  It replaces ``F.log_softmax(xe, dim=1)`` in front of the call, its backward and the activation that backward keeps
   (``tc_chain_step_log_softmax``).  Not a bool, or ``kaldi_way=False`` with it: ``ValueError`` before any
   library call.  Without the xent branch it does nothing.  ``torchain_amd/ops.py`` and the split entries do not take it.
+* ``boost=0.0, boost_ref=None, boost_pdf_class=None, boost_accuracy=None`` (keyword-only, through ``**options``): boosted
+  LF-MMI (bMMI).  Every denominator path's weight is multiplied by ``exp(-boost * A(path))``, ``A`` the path's frame
+  accuracy against a reference, so the model must beat a competitor by a margin that grows with its error.  The accuracy
+  ``a_t(j)`` is ``den_expected_accuracy``'s: the hard form ``boost_ref`` (int32 / int64 ``(B, Tmax)``, as ``best_path`` returns
+  it; ``-1`` or an out-of-range entry: the frame scores nothing) with an optional ``boost_pdf_class`` (int ``(P,)``, identity
+  when None), ``a = 1`` iff ``class(j) == class(ref_t)``; or the dense form ``boost_accuracy``, a float32 ``(Tmax*B, C)`` matrix,
+  row ``t*B + s``, unit column stride (``Supervision.posteriors``), any finite values, held constant.  The denominator alone
+  runs on ``y_b = fl32(y.float() - fl32(boost) * a)`` (two float32 roundings); the numerator, the l2 term and its gradient,
+  the penalty, ``deriv_weights`` and the cross-entropy branch act on the true ``y``: ``objf = w * (num_logprob(y) -
+  den_logprob(y_b))``, which is no longer bounded by 0 -- for ``a`` in [0, 1] and ``boost >= 0`` on a composed supervision it
+  is bounded by ``w * boost * sum(T_s)``.  ``results``, the loss, ``xent_objf`` and ``per_sequence`` keep their layout;
+  ``den_logprob`` is the boosted denominator's.  ``boost == 0.0``, or neither reference given, is the call without the option,
+  entry and bits.  Both references with ``boost != 0``, a ``boost`` that is not finite, wrong shapes / dtypes / devices, a
+  ``boost_accuracy`` that requires grad, and ``boost != 0`` with the xent branch and ``kaldi_way=False``: ``ValueError`` before
+  any library call.  Rows and entries of a ragged handle's padding frames are never read.  Under ``torch.no_grad()`` the
+  forward-only step is boosted too.  No host synchronisation: the tensors are read where they lie (an int64 ``boost_ref`` is
+  cast on the device), so the step stays capturable (``tc_chain_step_boosted``).  ``torchain_amd/ops.py``, the split entries and
+  ``chain_loss_data_parallel`` do not take it.
 """
 import ctypes as C
 import inspect
@@ -363,6 +381,59 @@ def _xent_options(options, kaldi_way):
     return flag
 
 
+def _boost_options(options, input, supervision, xent_active, kaldi_way):
+    """``boost``, ``boost_ref``, ``boost_pdf_class`` and ``boost_accuracy`` taken out of ``**options`` and checked on the host,
+    before any library call: None for the call without the option (``boost == 0.0``, or neither reference given), else
+    ``(boost, ref, pdf_class, accuracy)`` with exactly one of ``ref`` / ``accuracy``.  Everything else is a ``ValueError``."""
+    boost = options.pop("boost", 0.0)
+    ref, cls, acc = (options.pop(k, None) for k in ("boost_ref", "boost_pdf_class", "boost_accuracy"))
+    try:
+        b = float(boost)
+    except (TypeError, ValueError):
+        raise ValueError("boost must be a finite number, got %r" % (boost,)) from None
+    if isinstance(boost, bool) or b != b or b in (float("inf"), float("-inf")) or abs(b) > 3.0e38:
+        raise ValueError("boost must be a finite number, got %r" % (boost,))
+    if ref is None and cls is None and acc is None:
+        return None  # (the call without the option: nothing else is looked at)
+    if isinstance(supervision, io.Supervision):
+        S, T, P = supervision.n_batch, supervision.n_frame, supervision.n_pdf
+    else:  # (a raw handle: its three sizes are plain accessors of the host-side structure)
+        S, T, P = (lib.tc_supervision_num_sequence(supervision), lib.tc_supervision_num_frame(supervision),
+                   lib.tc_supervision_num_pdf(supervision))
+    ints = (torch.int32, torch.int64)
+
+    def tensor(t, name):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a tensor, got %s" % (name, type(t).__name__))
+        if t.device != input.device:
+            raise ValueError("%s must be on the input's device %s, got %s" % (name, input.device, t.device))
+
+    if ref is not None:
+        tensor(ref, "boost_ref")
+        if ref.dtype not in ints or tuple(ref.shape) != (S, T):
+            raise ValueError("boost_ref must be an int32 or int64 (B, Tmax) = %s tensor, got %s %s" % ((S, T), ref.dtype, tuple(ref.shape)))
+    if cls is not None:
+        tensor(cls, "boost_pdf_class")
+        if cls.dtype not in ints or tuple(cls.shape) != (P,):
+            raise ValueError("boost_pdf_class must be an int32 or int64 (P,) = %s tensor, got %s %s" % ((P,), cls.dtype, tuple(cls.shape)))
+        if ref is None:
+            raise ValueError("boost_pdf_class goes with boost_ref (the dense boost_accuracy has no classes)")
+    if acc is not None:
+        tensor(acc, "boost_accuracy")
+        if acc.dtype != torch.float32 or tuple(acc.shape) != (S * T, P) or acc.stride(1) != 1 or acc.stride(0) < P:
+            raise ValueError("boost_accuracy must be a float32 (Tmax*B, C) = %s matrix with unit column stride, got %s %s, strides %s"
+                             % ((S * T, P), acc.dtype, tuple(acc.shape), tuple(acc.stride())))
+        if acc.requires_grad:
+            raise ValueError("boost_accuracy is a constant: a tensor that requires grad is refused (detach it)")
+    if b == 0.0 or (ref is None and acc is None):
+        return None
+    if ref is not None and acc is not None:
+        raise ValueError("give exactly one of boost_ref and boost_accuracy")
+    if xent_active and not kaldi_way:
+        raise ValueError("boost needs kaldi_way=True with the xent branch: with kaldi_way=False the objective is run on xent_input")
+    return b, ref, cls, acc
+
+
 def _penalized(g, y, c):
     """The library's penalised gradient with torch ops in the library's order (``tc_chain_step_penalized``): ``g + t`` where
     ``p != 0`` and ``g`` itself elsewhere, ``t = fl32(2c) * p``, ``p`` the part of ``y`` beyond ``+-OUTPUT_LIMIT`` (0 for NaN and
@@ -415,11 +486,12 @@ class _ChainStep(Function):
     @staticmethod
     def forward(ctx, input, xent_input, results, den_graph, supervision,
                 l2_regularize, leaky_hmm_coefficient, xent_regularize=0.0, kaldi_way=False, deriv_weights=None,
-                out_of_range_regularize=0.0, per_sequence=False, isolate=False, xent_log_softmax=False):
+                out_of_range_regularize=0.0, per_sequence=False, isolate=False, xent_log_softmax=False, boost=None):
         out, grad, xgrad = _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
                                      leaky_hmm_coefficient, xent_regularize, kaldi_way, want_grad=True,
                                      deriv_weights=deriv_weights, out_of_range_regularize=out_of_range_regularize,
-                                     per_sequence=per_sequence, isolate=isolate, xent_log_softmax=xent_log_softmax)
+                                     per_sequence=per_sequence, isolate=isolate, xent_log_softmax=xent_log_softmax,
+                                     boost=boost)
         ctx.grads = (grad, xgrad)
         if results._defer_host_copy:
             return input.new_zeros(1)
@@ -427,13 +499,14 @@ class _ChainStep(Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return (ctx.grads[0], ctx.grads[1]) + (None,) * 12
+        return (ctx.grads[0], ctx.grads[1]) + (None,) * 13
 
 
 def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
               xent_regularize, kaldi_way, want_grad, deriv_weights=None, out_of_range_regularize=0.0, per_sequence=False,
-              isolate=False, xent_log_softmax=False):
-    """``per_sequence`` / ``isolate`` (``_failure_options``): the same step through ``tc_chain_step_per_sequence``, which also
+              isolate=False, xent_log_softmax=False, boost=None):
+    """``boost`` (``_boost_options``, not None): the step through ``tc_chain_step_boosted``, which takes every other option.
+    ``per_sequence`` / ``isolate`` (``_failure_options``): the same step through ``tc_chain_step_per_sequence``, which also
     fills the sequences' own values, allocated next to ``out``.  ``xent_log_softmax`` (``_xent_options``) with the xent branch
     active: that step through ``tc_chain_step_log_softmax``, whose workspace also holds the row statistics.  Otherwise:
     One ``tc_chain_step_strided``, in the layout ``classify_layout`` finds (a time-major view as the 2-D rows it is;
@@ -478,13 +551,18 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         key = (S, T, layout != TC_LAYOUT_ROWS, use_xent, dtype)  # (a channel-last step has the (B, C, T) step's workspace)
         if log_softmax:
             key += ("log_softmax",)
+        if boost is not None:
+            key += ("boost",)
         sizes = den_graph.__dict__.setdefault("_step_bytes", {}) if isinstance(den_graph, io.DenominatorGraph) else {}
         nbytes = sizes.get(key)
         if nbytes is None:
             sizer = lib.tc_chain_step_log_softmax_workspace_bytes if log_softmax else lib.tc_chain_step_strided_workspace_bytes
+            if boost is not None:
+                sizer = lib.tc_chain_step_boosted_workspace_bytes
             nbytes = sizer(den_ptr, S, T, layout, int(use_xent), dtype)
             if nbytes < 0:
-                check(int(nbytes), "tc_chain_step_log_softmax_workspace_bytes" if log_softmax else "tc_chain_step_strided_workspace_bytes")
+                check(int(nbytes), "tc_chain_step_boosted_workspace_bytes" if boost is not None else
+                      "tc_chain_step_log_softmax_workspace_bytes" if log_softmax else "tc_chain_step_strided_workspace_bytes")
             sizes[key] = nbytes
         capturing = torch.cuda.is_current_stream_capturing()
         # (inside a graph capture the workspace comes from the graph's own pool and lives as long as the graph does)
@@ -503,7 +581,17 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         seq = None
         if per_sequence or isolate:
             seq = torch.empty((S, 6), dtype=torch.float64, device=device)
-        if log_softmax:
+        keeps = ()
+        if boost is not None:
+            # (read where they lie; an int64 or strided reference is cast / packed by a device op in front of the call)
+            b, ref, cls, acc = boost
+            ref = ref.detach().to(torch.int32).contiguous() if ref is not None else None
+            cls = cls.detach().to(torch.int32).contiguous() if cls is not None else None
+            keeps = (ref, cls, acc)
+            check(lib.tc_chain_step_boosted(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail, int(bool(isolate)),
+                                            _ptr(seq), int(log_softmax), b, _ptr(ref), _ptr(cls), _ptr(acc),
+                                            acc.stride(0) if acc is not None else 0), "tc_chain_step_boosted")
+        elif log_softmax:
             check(lib.tc_chain_step_log_softmax(*args, _ptr(w), float(out_of_range_regularize), dtype, *tail, int(bool(isolate)),
                                                 _ptr(seq), 1), "tc_chain_step_log_softmax")
         elif per_sequence or isolate:
@@ -516,7 +604,7 @@ def _run_step(input, xent_input, results, den_graph, supervision, l2_regularize,
         results._stale = True
         results._ready = None
         if capturing:
-            results._graph_keeps = (ws, w)  # replays write through it; read the values after a replay with ``invalidate()``
+            results._graph_keeps = (ws, w) + keeps  # replays write through it; read the values after a replay with ``invalidate()``
         else:
             results._ready = torch.cuda.Event()
             results._ready.record(cur)
@@ -735,12 +823,14 @@ def chain_loss(input, den_graph, supervision,
                l2_regularize=0.0, leaky_hmm_coefficient=1e-5,
                xent_regularize=0.0, xent_input=None, kaldi_way=False, *, deriv_weights=None, **options):
     """``options``, keyword-only (the module docstring): ``out_of_range_regularize=0.0`` (``_options``), ``per_sequence=False``
-    and ``on_failure="minibatch"`` (``_failure_options``), ``xent_log_softmax=False`` (``_xent_options``)."""
+    and ``on_failure="minibatch"`` (``_failure_options``), ``xent_log_softmax=False`` (``_xent_options``), ``boost=0.0``,
+    ``boost_ref=None``, ``boost_pdf_class=None`` and ``boost_accuracy=None`` (``_boost_options``)."""
     per_sequence, isolate = _failure_options(options)
     log_softmax = _xent_options(options, kaldi_way)
+    boost = _boost_options(options, input, supervision, xent_input is not None and xent_regularize != 0.0, kaldi_way)
     return _chain_loss_into(ChainResults(), input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient,
                             xent_regularize, xent_input, kaldi_way, deriv_weights, _options(options), per_sequence, isolate,
-                            log_softmax)
+                            log_softmax, boost)
 
 
 # What introspection reports stays the reference's signature (torchain/functions.py:128-130), the drop-in surface callers
@@ -752,7 +842,7 @@ chain_loss.__signature__ = inspect.signature(chain_loss).replace(
 
 def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
                      xent_input, kaldi_way, deriv_weights=None, out_of_range_regularize=0.0, per_sequence=False, isolate=False,
-                     xent_log_softmax=False):
+                     xent_log_softmax=False, boost=None):
     """``chain_loss`` with the ``ChainResults`` given (parallel.chain_loss_data_parallel passes one that defers the
     host copy of the three floats until after its all-reduce): check the options, plan, one call."""
     deriv_weights = _deriv_weights(deriv_weights, _rows_of(input))
@@ -761,14 +851,14 @@ def _chain_loss_into(results, input, den_graph, supervision, l2_regularize, leak
     x, xe = _step_inputs(input, xent_input, want_grad)
     if want_grad:
         loss = _ChainStep.apply(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
-                                kaldi_way, deriv_weights, c, per_sequence, isolate, xent_log_softmax)
+                                kaldi_way, deriv_weights, c, per_sequence, isolate, xent_log_softmax, boost)
         return loss, results
     # Evaluation (the recipe's validation loop runs under torch.no_grad(), example/chime5/train.py:150-171): the forward
     # recursions only; deriv_weights and the penalty are checked above and not used.  The reference has no such check
     # (functions.py:74,82) and pays for a training step.
     out, _, _ = _run_step(x, xe, results, den_graph, supervision, l2_regularize, leaky_hmm_coefficient, xent_regularize,
                           kaldi_way, want_grad=False, per_sequence=per_sequence, isolate=isolate,
-                          xent_log_softmax=xent_log_softmax)
+                          xent_log_softmax=xent_log_softmax, boost=boost)
     # (the loss of an up-cast dtype the step does not take keeps that dtype)
     like = x if input.dtype in _STEP_DTYPES else input
     return (like.new_zeros(1) if results._defer_host_copy else out[3:4].to(like.dtype)), results
