@@ -992,6 +992,53 @@ int tc_den_sample_paths(tc_den_graph *g, int32_t S, const float *nnet_output, in
                         int32_t *pdf_dev /* [S][K][T] */, int32_t *state_dev /* nullable, [S][K][T+1][2]: pre, post */,
                         void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* ---- arc and entry occupations of the denominator graph (den_arc_post_kernels.hip) ------------------------------------------
+ * tc_den_arc_posteriors gives the occupations of the graph's own parameters under the model that tc_den_forward_backward
+ * sums over (p_t(j) = exp(clamp(y_t(j), +-30)), the initial probabilities pi, every state final, the leaky-HMM coefficient
+ * c).  Per sequence s of T_s frames, in the scaled recursions of den_arc_post_kernels.hip's header:
+ *     occ_s(a) = sum_{t<T_s} alpha'_t(src_a) f_t(a) beta_{t+1}(dst_a)             = d log Z_s / d log w_a (pi held fixed)
+ *     ent_s(h) = pi(h) [beta_0(h) + c sum_{t<=T_s} asum_t beta'_t(h)]             = d log Z_s / d log pi(h)
+ *     leaks_s  = c sum_{t<=T_s} asum_t sum_h pi(h) beta'_t(h) = sum_h ent_s(h) - 1 = d log Z_s / d log c
+ * so sum_a occ_s(a) = T_s.  ARC ORDER: element a of arc_total and of a row of per_seq_arcs is arc a of tc_den_graph_arcs
+ * -- callers index their parameters with it.  States are the FST's.
+ *   nnet_output   : device float32 (T*S, P), row t*S + s, rows row_stride >= num_cols floats apart; num_rows = S *
+ *                   max_frames.  Rows of padding frames are not read.
+ *   seq_frames_dev: S device int32 lengths in 1 .. max_frames, or null (max_frames each).  Lengths work on graphs of every
+ *                   size, the streamed class included: this entry reads no training table and refuses no graph.
+ *   arc_total     : device double[A], sum_s occ_s(a); entry_total: device double[H], sum_s ent_s(h): double sums of the
+ *                   float32 partial rows in sequence order, one thread an element, so they do not depend on the launch.
+ *                   Both null: no reduction (tc_den_arc_posteriors_reduce does it later, e.g. over the rows of several calls).
+ *   logprob_dev   : device double[S], log Z_s.  leaks_dev (nullable): device double[S].
+ *   per_seq_arcs  : nullable, device float32 (S, A) contiguous; per_seq_entries: nullable, device float32 (S, H).  The
+ *                   partial rows; without them they are kept in the workspace.
+ *   workspace     : tc_den_arc_posteriors_workspace_bytes(g, S, max_frames); 16-byte aligned.
+ * Arithmetic: vectors by state and pdf are float32 where stored, sums over arcs and states are doubles rounded once, the
+ * accumulators over the frames are float32 updated as (float)((double)acc + term).  Every order is fixed and nothing is
+ * atomic: a sequence's row, log Z and leak count depend on its own rows of nnet_output, the graph and c alone.
+ * A sequence with a NaN or +-inf in its valid frames gets +0 rows in both partials, NaN in logprob_dev and leaks_dev; the
+ * others keep their bits.
+ * Two launches (forward-backward, one workgroup of 16 wavefronts a sequence; the reduction), asynchronous on `stream`, no
+ * host synchronisation.  The tables are the entry's own, uploaded on the graph's first call on the device; the training
+ * tables are neither read nor written (a training step gives the same bits before and after).  A thread keeps its arcs'
+ * accumulators in registers while the schedule gives it at most 64 arcs; beyond, they are floats of the workspace, with
+ * the same bits ("den_arc_post_streamed_launches" counts those launches; tc_debug_set("force_den_arc_post_streamed", 1)
+ * sends every graph there, and the value 3 also moves the per-state vectors from LDS to the workspace, where they are once
+ * 16 * Hs + 4 * Ps + 1024 > 163840 bytes).  "den_arc_post_launches" counts the calls.
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null graph, nnet_output or logprob_dev; exactly one of the totals
+ * null; S or max_frames <= 0; num_rows != S * max_frames; num_cols != the graph's pdfs; row_stride < num_cols; a negative or
+ * non-finite coefficient; a misaligned pointer (4 bytes; 8 for doubles).  TC_ERR_WORKSPACE: a null, short or misaligned
+ * workspace.  TC_ERR_UNSUPPORTED: 2^29 states or more. */
+int64_t tc_den_arc_posteriors_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T);
+int tc_den_arc_posteriors(tc_den_graph *g, int32_t S, const float *nnet_output, int64_t num_rows, int32_t num_cols,
+                          int64_t row_stride, const int32_t *seq_frames_dev /* nullable */, int32_t max_frames,
+                          float leaky_hmm_coefficient, double *arc_total /* [A] */, double *entry_total /* [H] */,
+                          double *logprob_dev /* [S] */, double *leaks_dev /* nullable, [S] */,
+                          void *per_seq_arcs /* nullable, float32 (S, A) */, void *per_seq_entries /* nullable, float32 (S, H) */,
+                          void *workspace, int64_t workspace_bytes, int device, void *stream);
+/* the totals of S partial rows, in row order (what tc_den_arc_posteriors runs last) */
+int tc_den_arc_posteriors_reduce(int32_t S, int64_t num_arcs, int32_t num_states, const void *per_seq_arcs,
+                                 const void *per_seq_entries, double *arc_total, double *entry_total, int device, void *stream);
+
 /* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
  * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token
  * sequences and scores each against its sequence's reference by the unit-cost Levenshtein distance: the risk of a

@@ -737,6 +737,70 @@ int tc_den_sample_paths(tc_den_graph *g, int32_t S, const float *y, int64_t rows
   return launch_den_sample_paths(p, (hipStream_t)stream_v);
 }
 
+int64_t tc_den_arc_posteriors_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {
+  if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
+  return den_arc_workspace_bytes(g->H, g->P, g->A, den_arc_table_rows(den_arc_schedule_rows(g)), S, T);
+}
+
+int tc_den_arc_posteriors(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                          const int32_t *seq_frames_dev, int32_t max_frames, float leaky, double *arc_total,
+                          double *entry_total, double *logprob_dev, double *leaks_dev, void *per_seq_arcs,
+                          void *per_seq_entries, void *workspace, int64_t workspace_bytes, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!g || !y || !logprob_dev || S <= 0 || max_frames <= 0 || !arc_total != !entry_total) return TC_ERR_INVALID_ARGUMENT;
+  if (rows != (int64_t)S * max_frames || cols != g->P || y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!(leaky >= 0.0f) || !(leaky <= FLT_MAX)) return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)y | (uintptr_t)seq_frames_dev | (uintptr_t)per_seq_arcs | (uintptr_t)per_seq_entries) & 3) != 0 ||
+      (((uintptr_t)arc_total | (uintptr_t)entry_total | (uintptr_t)logprob_dev | (uintptr_t)leaks_dev) & 7) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  if ((uint32_t)g->H >= kDenArcValid) return TC_ERR_UNSUPPORTED;  // (a slot keeps its state beside three flags)
+  const int table_rows = den_arc_table_rows(den_arc_schedule_rows(g));
+  if (!workspace || den_arc_workspace_bytes(g->H, g->P, g->A, table_rows, S, max_frames) > workspace_bytes || !aligned16(workspace))
+    return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  DenArcParams p;
+  int rc = den_arc_tables(g, device, &p.t);
+  if (rc != TC_OK) return rc;
+  p.y = y;
+  p.y_stride = y_stride;
+  p.S = S;
+  p.T = max_frames;
+  p.H = g->H;
+  p.P = g->P;
+  p.Hs = (int)den_acc_round4(g->H);
+  p.Ps = (int)den_acc_round4(g->P);
+  p.A = g->A;
+  p.leaky = leaky;
+  p.seq_frames = seq_frames_dev;
+  // the partials the caller does not take lie behind the sequences' rows of the workspace
+  float *spare = (float *)workspace + (int64_t)S * den_arc_seq_floats(g->H, g->P, max_frames, table_rows);
+  p.part_arcs = per_seq_arcs ? (float *)per_seq_arcs : spare;
+  p.part_entries = per_seq_entries ? (float *)per_seq_entries : spare + (int64_t)S * den_acc_round4((int)g->A);
+  p.logprob = logprob_dev;
+  p.leaks = leaks_dev;
+  p.workspace = (char *)workspace;
+  const int forced = debug_value(kDbgForceDenArcPostStreamed);
+  p.resident = den_arc_resident(g->H, g->P) && !(forced & 2);
+  p.in_registers = p.t.tier != 0 && !forced;
+  rc = launch_den_arc_post(p, (hipStream_t)stream_v);
+  if (rc != TC_OK || !arc_total) return rc;
+  return launch_den_arc_reduce(p.part_arcs, p.part_entries, S, g->A, g->H, arc_total, entry_total, (hipStream_t)stream_v);
+}
+
+int tc_den_arc_posteriors_reduce(int32_t S, int64_t num_arcs, int32_t num_states, const void *per_seq_arcs,
+                                 const void *per_seq_entries, double *arc_total, double *entry_total, int device,
+                                 void *stream_v) {
+  if (S <= 0 || num_arcs < 0 || num_states <= 0 || !per_seq_arcs || !per_seq_entries || !arc_total || !entry_total)
+    return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)per_seq_arcs | (uintptr_t)per_seq_entries) & 3) != 0 || (((uintptr_t)arc_total | (uintptr_t)entry_total) & 7) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  return launch_den_arc_reduce((const float *)per_seq_arcs, (const float *)per_seq_entries, S, num_arcs, num_states, arc_total,
+                               entry_total, (hipStream_t)stream_v);
+}
+
 int64_t tc_paths_edit_distance_workspace_bytes(int32_t S, int32_t K, int32_t max_frames) {
   if (S <= 0 || K <= 0 || max_frames <= 0) return TC_ERR_INVALID_ARGUMENT;
   return path_edit_workspace_bytes(S, K, max_frames);

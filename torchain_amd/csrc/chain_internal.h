@@ -282,6 +282,73 @@ inline int64_t den_acc_grad_workspace_bytes(int H, int P, int S, int T) {
   return (((int64_t)S * den_acc_seq_floats(H, P, T) * 4) + 255) & ~(int64_t)255;
 }
 
+// Arc and entry occupations of the graph (tc_den_arc_posteriors, den_arc_post_kernels.hip): the by-destination CSR for the
+// forward pass and, for the backward pass, a SLOT SCHEDULE of the by-source walk made once on the host (den_arc_tables).
+// State h belongs to thread h % 1024 (wave (h % 1024) / 64, lane h % 64) and is taken in pass h / 1024.  Within a pass a
+// wave first walks its rows of at most kDenArcLongRow arcs, lane = row, arc j of the row in slot j of the phase; then each
+// longer row by itself, arc 64 * j + lane of the row in slot j of its phase.  A thread's slots are numbered through the
+// passes, the shorter waves are padded with empty slots, and slot k of thread tid is entry k * 1024 + tid of `slots`: the
+// arc of a slot belongs to that thread for the whole sequence, and `slot_arc` is its index in tc_den_graph_arcs' order
+// (-1: an empty slot).  `rows` is the schedule's slot count rounded up to its register tier.
+constexpr int kDenArcThreads = 1024;
+constexpr int kDenArcLongRow = 128;
+constexpr int kDenArcMaxTier = 64;                // slots a thread keeps in registers at most
+constexpr uint32_t kDenArcValid = 1u << 29;       // the slot holds an arc
+constexpr uint32_t kDenArcRowEnd = 1u << 30;      // the last slot of the lane's own row: store beta'(src)
+constexpr uint32_t kDenArcWaveEnd = 1u << 31;     // the last slot of a row the wave walks together (set in all 64 lanes)
+constexpr uint32_t kDenArcSrcMask = kDenArcValid - 1;
+struct DenArcSlot {  // 16 bytes, one load
+  int32_t dst, pdf;
+  float w;
+  uint32_t meta;  // the row's state | flags
+};
+struct DenArcDev {
+  const int32_t *in_begin = nullptr;     // [H + 1]
+  const DenAccArc *in_arcs = nullptr;    // [A]: source, pdf, w by destination state
+  const DenArcSlot *slots = nullptr;     // [rows][1024]
+  const int32_t *slot_arc = nullptr;     // [rows][1024]
+  const float *pi = nullptr;             // [H]
+  int rows = 0, tier = 0;                // tier: 8, 16, 32, 64, or 0 when rows exceed kDenArcMaxTier
+  void *blob = nullptr;
+};
+struct DenArcParams {
+  DenArcDev t;
+  const float *y;
+  int64_t y_stride;
+  int S, T, H, P, Hs, Ps;  // T: the longest sequence's frames; Hs, Ps: H, P rounded up to 4
+  int64_t A;
+  float leaky;
+  const int32_t *seq_frames;  // [S] nullable
+  float *part_arcs;           // (S, A): occ_s(a) in tc_den_graph_arcs' order
+  float *part_entries;        // (S, H)
+  double *logprob, *leaks;    // [S]; leaks nullable
+  char *workspace;            // per sequence den_arc_seq_floats
+  int resident;               // the per-state vectors and exp(y) / asum in LDS (den_arc_resident), else in the workspace
+  int in_registers;           // the arc accumulators in registers (t.tier != 0), else in the sequence's workspace row
+};
+// floats of the per-frame vectors: beta of two frames, alpha'_t, the entry accumulators by state, and exp(y) / asum by pdf
+__host__ __device__ inline int64_t den_arc_frame_floats(int H, int P) { return 4 * den_acc_round4(H) + den_acc_round4(P); }
+constexpr int kDenArcSmallLds = 1024;  // the block reductions' slots, rounded up
+inline bool den_arc_resident(int H, int P) { return 4 * den_arc_frame_floats(H, P) + kDenArcSmallLds <= (int64_t)160 * 1024; }
+// per sequence, in floats: alpha'_0..T, 1 / asum_0..T, asum_0..T, room for the per-frame vectors and for `rows` slots a thread
+__host__ __device__ inline int64_t den_arc_seq_floats(int H, int P, int T, int rows) {
+  return (int64_t)(T + 1) * den_acc_round4(H) + 2 * den_acc_round4(T + 1) + den_arc_frame_floats(H, P) +
+         (int64_t)rows * kDenArcThreads;
+}
+// ... and behind the S sequences the (S, A) and (S, H) partials, used when the caller gives none
+inline int64_t den_arc_workspace_bytes(int H, int P, int64_t A, int rows, int S, int T) {
+  const int64_t floats = (int64_t)S * (den_arc_seq_floats(H, P, T, rows) + den_acc_round4((int)A) + den_acc_round4(H));
+  return (floats * 4 + 255) & ~(int64_t)255;
+}
+int den_arc_schedule_rows(const tc_den_graph *g);  // den_graph.cpp: the slot count of the schedule, before tiering (host only)
+// the register tier of a schedule of `rows` slots a thread (0: beyond the largest), and the rows of its table: the tier's
+inline int den_arc_tier(int rows) {
+  for (int t = 8; t <= kDenArcMaxTier; t *= 2)
+    if (rows <= t) return t;
+  return 0;
+}
+inline int den_arc_table_rows(int rows) { return den_arc_tier(rows) ? den_arc_tier(rows) : rows; }
+
 // Paths drawn from the graph's path posterior (tc_den_sample_paths, den_sample_kernels.hip): the by-destination CSR of
 // DenAccDev (den_acc_tables) and nothing else of the graph.
 struct DenSampleParams {
@@ -484,6 +551,10 @@ struct tc_den_graph {
   std::map<int, tc::DenBestDev> best_dev;
   // ... and tc_den_expected_accuracy_grad's (den_accuracy_kernels.hip, den_acc_tables), kept the same way
   std::map<int, tc::DenAccDev> acc_dev;
+  // ... and tc_den_arc_posteriors' (den_arc_post_kernels.hip, den_arc_tables); arc_rows: the schedule's slot count (-1: not
+  // counted yet)
+  std::map<int, tc::DenArcDev> arc_dev;
+  int arc_rows = -1;
 };
 
 // ---- numerator -----------------------------------------------------------------------------------
@@ -725,6 +796,10 @@ int launch_den_accuracy_rows(const DenAccRowParams &p, bool dense, hipStream_t s
 int launch_den_accuracy_grad(const DenAccGradParams &p, bool dense, hipStream_t stream);
 int den_acc_tables(tc_den_graph *g, int device, DenAccDev *out);     // den_graph.cpp: made and uploaded on first use
 int launch_den_sample_paths(const DenSampleParams &p, hipStream_t stream);  // den_sample_kernels.hip
+int launch_den_arc_post(const DenArcParams &p, hipStream_t stream);     // den_arc_post_kernels.hip
+int launch_den_arc_reduce(const float *part_arcs, const float *part_entries, int S, int64_t A, int H, double *arc_total,
+                          double *entry_total, hipStream_t stream);
+int den_arc_tables(tc_den_graph *g, int device, DenArcDev *out);     // den_graph.cpp: made and uploaded on first use
 int launch_path_edit(const PathEditParams &p, hipStream_t stream);      // path_edit_kernels.hip
 int launch_sampled_risk_grad(const SampledRiskGradParams &p, int dtype, hipStream_t stream);
 // dynamic LDS of num_e2e_kernel: two double score vectors, the frame's y per distinct pdf and one float per arc (max_arcs = 0:
@@ -881,7 +956,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -890,7 +965,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

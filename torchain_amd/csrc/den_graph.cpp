@@ -426,7 +426,7 @@ extern "C" {
 int tc_debug_set(const char *key, int value) {
   static const char *const names[kDbgCount] = {"force_general", "force_streamed", "no_split", "no_pdf_banks",
                                                "no_bank_search", "sched_trace", "no_phase_split", "no_num_overlap", "no_pair",
-                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout", "force_den_accuracy_streamed", "force_den_sample_streamed"};
+                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout", "force_den_accuracy_streamed", "force_den_sample_streamed", "force_den_arc_post_streamed"};
   if (!key) return TC_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < kDbgCount; ++i)
     if (!strcmp(key, names[i])) {
@@ -466,7 +466,7 @@ int64_t tc_debug_counter(const char *key) {
   if (key && !strcmp(key, "pool_device_allocs")) return pool_counter(0);
   if (key && !strcmp(key, "pool_reuses")) return pool_counter(1);
   static const char *const names[kCntCount] = {"den_launches", "den_backward_launches", "num_launches", "num_backward_launches", "layout_launches",
-                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches", "den_sample_launches", "den_sample_streamed_launches", "path_edit_launches", "sampled_risk_grad_launches", "boost_launches"};
+                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches", "den_sample_launches", "den_sample_streamed_launches", "path_edit_launches", "sampled_risk_grad_launches", "boost_launches", "den_arc_post_launches", "den_arc_post_streamed_launches"};
   for (int i = 0; key && i < kCntCount; ++i)
     if (!strcmp(key, names[i])) return g_launches[i].load(std::memory_order_relaxed);
   return -1;
@@ -665,6 +665,14 @@ void tc_den_graph_free(tc_den_graph *g) {
     }
   }
   for (auto &kv : g->acc_dev) {
+    int cur = 0;
+    if (kv.second.blob && hipGetDevice(&cur) == hipSuccess) {
+      (void)hipSetDevice(kv.first);
+      (void)hipFree(kv.second.blob);
+      (void)hipSetDevice(cur);
+    }
+  }
+  for (auto &kv : g->arc_dev) {
     int cur = 0;
     if (kv.second.blob && hipGetDevice(&cur) == hipSuccess) {
       (void)hipSetDevice(kv.first);
@@ -1205,6 +1213,125 @@ int tc::den_acc_tables(tc_den_graph *g, int device, DenAccDev *out) {
   d.pi = (const float *)(blob + off[6]);
   d.blob = blob;
   g->acc_dev[device] = d;
+  *out = d;
+  return TC_OK;
+}
+
+// tc_den_arc_posteriors' slot schedule (chain_internal.h: DenArcDev).  One routine counts and fills, so the two agree:
+// it returns the schedule's slot count and, with `slots` given (at least that many slots a thread, empty), fills them.
+namespace {
+int den_arc_schedule(const tc_den_graph *g, tc::DenArcSlot *slots, int32_t *slot_arc) {
+  using namespace tc;
+  const int H = g->H;
+  const int64_t A = g->A;
+  std::vector<int32_t> begin(H + 1, 0), order((size_t)std::max<int64_t>(A, 1));
+  for (int64_t a = 0; a < A; ++a) ++begin[g->arc_src[a] + 1];
+  for (int h = 0; h < H; ++h) begin[h + 1] += begin[h];
+  {
+    std::vector<int32_t> fill(begin.begin(), begin.end() - 1);
+    for (int64_t a = 0; a < A; ++a) order[fill[g->arc_src[a]]++] = (int32_t)a;
+  }
+  auto put = [&](int k, int tid, int64_t i, uint32_t meta) {  // arc `i` of the by-source order (-1: none) into slot k
+    if (!slots) return;
+    const size_t at = (size_t)k * kDenArcThreads + tid;
+    if (i >= 0) {
+      const int32_t a = order[i];
+      slots[at] = DenArcSlot{g->arc_dst[a], g->arc_pdf[a], g->arc_prob[a], meta | kDenArcValid};
+      slot_arc[at] = a;
+    } else {
+      slots[at].meta = meta;
+    }
+  };
+  int most = 0;
+  for (int wave = 0; wave < kDenArcThreads / 64; ++wave) {
+    int k = 0;
+    for (int base = wave * 64; base < H; base += kDenArcThreads) {
+      int shorts = 0;
+      for (int lane = 0; lane < 64 && base + lane < H; ++lane) {
+        const int r = base + lane, deg = begin[r + 1] - begin[r];
+        if (deg > kDenArcLongRow) continue;
+        shorts = std::max(shorts, std::max(deg, 1));
+        for (int j = 0; j < deg; ++j) put(k + j, wave * 64 + lane, begin[r] + j, (uint32_t)r | (j == deg - 1 ? kDenArcRowEnd : 0u));
+        if (deg == 0) put(k, wave * 64 + lane, -1, (uint32_t)r | kDenArcRowEnd);
+      }
+      k += shorts;
+      for (int lane = 0; lane < 64 && base + lane < H; ++lane) {
+        const int r = base + lane, deg = begin[r + 1] - begin[r];
+        if (deg <= kDenArcLongRow) continue;
+        const int n = (deg + 63) / 64;
+        for (int j = 0; j < n; ++j)
+          for (int l = 0; l < 64; ++l)
+            put(k + j, wave * 64 + l, j * 64 + l < deg ? (int64_t)begin[r] + j * 64 + l : -1,
+                (uint32_t)r | (j == n - 1 ? kDenArcWaveEnd : 0u));
+        k += n;
+      }
+    }
+    most = std::max(most, k);
+  }
+  return most;
+}
+}  // namespace
+
+int tc::den_arc_schedule_rows(const tc_den_graph *cg) {
+  tc_den_graph *g = const_cast<tc_den_graph *>(cg);
+  std::lock_guard<std::mutex> lock(g->mu);
+  if (g->arc_rows < 0) g->arc_rows = den_arc_schedule(g, nullptr, nullptr);
+  return g->arc_rows;
+}
+
+// tc_den_arc_posteriors' tables: the by-destination CSR, the slot schedule and pi.  Built and uploaded on the first call per
+// device, into a blob of their own; g->dev, g->best_dev and g->acc_dev are neither read nor written.
+int tc::den_arc_tables(tc_den_graph *g, int device, DenArcDev *out) {
+  const int rows = den_arc_schedule_rows(g);
+  std::lock_guard<std::mutex> lock(g->mu);
+  auto it = g->arc_dev.find(device);
+  if (it != g->arc_dev.end()) {
+    *out = it->second;
+    return TC_OK;
+  }
+  const int H = g->H;
+  const int64_t A = g->A;
+  const int tier = den_arc_tier(rows), table_rows = den_arc_table_rows(rows);
+  std::vector<int32_t> in_begin(H + 1, 0);
+  for (int64_t a = 0; a < A; ++a) ++in_begin[g->arc_dst[a] + 1];
+  for (int h = 0; h < H; ++h) in_begin[h + 1] += in_begin[h];
+  const size_t An = (size_t)std::max<int64_t>(A, 1);
+  std::vector<DenAccArc> in_arcs(An, DenAccArc{0, 0, 0.f});
+  {
+    std::vector<int32_t> fill(in_begin.begin(), in_begin.end() - 1);
+    for (int64_t a = 0; a < A; ++a) in_arcs[fill[g->arc_dst[a]]++] = DenAccArc{g->arc_src[a], g->arc_pdf[a], g->arc_prob[a]};
+  }
+  const size_t n_slots = (size_t)table_rows * kDenArcThreads;
+  std::vector<DenArcSlot> slots(n_slots, DenArcSlot{0, 0, 0.f, 0u});
+  std::vector<int32_t> slot_arc(n_slots, -1);
+  den_arc_schedule(g, slots.data(), slot_arc.data());
+  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const void *src[5] = {in_begin.data(), in_arcs.data(), slots.data(), slot_arc.data(), g->initial_probs.data()};
+  const size_t bytes[5] = {in_begin.size() * 4, An * sizeof(DenAccArc), n_slots * sizeof(DenArcSlot), n_slots * 4, (size_t)H * 4};
+  size_t off[6] = {0};
+  for (int i = 0; i < 5; ++i) off[i + 1] = off[i] + align(bytes[i]);
+  int prev = 0;
+  TC_HIP_CHECK(hipGetDevice(&prev));
+  TC_HIP_CHECK(hipSetDevice(device));
+  char *blob = nullptr;
+  hipError_t e = hipMalloc((void **)&blob, off[5]);
+  for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemcpy(blob + off[i], src[i], bytes[i], hipMemcpyHostToDevice);
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (blob) (void)hipFree(blob);
+    g_last_hip_error = (int)e;
+    return TC_ERR_HIP;
+  }
+  DenArcDev d;
+  d.in_begin = (const int32_t *)(blob + off[0]);
+  d.in_arcs = (const DenAccArc *)(blob + off[1]);
+  d.slots = (const DenArcSlot *)(blob + off[2]);
+  d.slot_arc = (const int32_t *)(blob + off[3]);
+  d.pi = (const float *)(blob + off[4]);
+  d.rows = table_rows;
+  d.tier = tier;
+  d.blob = blob;
+  g->arc_dev[device] = d;
   *out = d;
   return TC_OK;
 }

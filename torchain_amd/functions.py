@@ -1030,6 +1030,33 @@ def den_sample_paths(input, den_graph, num_samples, frames=None, leaky_hmm_coeff
                                       max_workspace_bytes=max_workspace_bytes, workspace=workspace, n_batch=n_batch)
 
 
+def den_arc_posteriors(input, den_graph, frames=None, leaky_hmm_coefficient=1e-5, per_sequence=False,
+                       max_workspace_bytes=1 << 30, n_batch=None):
+    """The expected counts of ``den_graph``'s own parameters under ``input``: ``post.arcs`` float64 ``(A,)`` in the order of
+    ``den_graph.arcs()``, ``post.entries`` float64 ``(H,)``, ``post.leaks`` and ``post.logprob`` float64 ``(B,)``, and with
+    ``per_sequence`` the float32 rows ``post.per_seq_arcs`` ``(B, A)`` and ``post.per_seq_entries`` ``(B, H)``
+    (``io.DenominatorGraph.arc_posteriors`` states the arguments; ``tc_den_arc_posteriors``).  ``post.arcs`` is
+    ``d sum_b log Z_b / d log w``, so no autograd is involved here; two uses:
+
+    A trainable graph, ``log_w(theta)`` a float64 ``(A,)`` tensor in the order of ``den_graph.arcs()`` whose exponentials
+    the graph was built from -- the denominator's share of the LF-MMI gradient, with the objective's ``weight``::
+
+        post = den_arc_posteriors(out, graph)
+        log_w(theta).backward(gradient=-weight * post.arcs)
+
+    Re-estimating the phone LM (EM; accumulate ``post.arcs`` over an epoch first)::
+
+        src, dst, pdf, prob = graph.arcs()
+        total = torch.zeros(graph.num_states, dtype=torch.float64).index_add_(0, torch.as_tensor(src).long(), post.arcs.cpu())
+        new_prob = post.arcs.cpu() / total[torch.as_tensor(src).long()]    # then rebuild: DenominatorGraph(fst, n_pdf)
+    """
+    if not isinstance(den_graph, io.DenominatorGraph):
+        raise TypeError("den_arc_posteriors takes an io.DenominatorGraph, got %s" % type(den_graph).__name__)
+    with torch.no_grad():
+        return den_graph.arc_posteriors(input, frames=frames, leaky_hmm_coefficient=leaky_hmm_coefficient,
+                                        per_sequence=per_sequence, max_workspace_bytes=max_workspace_bytes, n_batch=n_batch)
+
+
 def _int_vector(who, name, v, n, device, dtype=torch.int32):
     """``v`` as a contiguous ``(n,)`` tensor of ``dtype`` on ``device`` (a tensor already there is not brought to the host)."""
     t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)

@@ -6,6 +6,7 @@ wrap the C-ABI handles of libtorchain_hip.so instead of heap Kaldi objects.  The
 of the reference (``Example``, ``RandExample``, ``open_example``, ``print_key_length``, ``io.py:60-175``) are
 here too, on top of ``torchain_amd.egs`` (a Kaldi-free parser of the ``<Nnet3ChainEg>`` formats).
 """
+import collections
 import ctypes as C
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -652,6 +653,75 @@ class DenominatorGraph:
                                               C.c_void_p(ws.data_ptr()), ws.numel(), device.index, stream),
                       "tc_den_sample_paths")
         return (pdfs, states) if return_states else pdfs
+
+    def arc_posteriors(self, nnet_output, frames=None, leaky_hmm_coefficient=1e-5, per_sequence=False,
+                       max_workspace_bytes=1 << 30, n_batch=None):
+        """The occupations of this graph's own parameters under ``nnet_output`` (``tc_den_arc_posteriors``): how often each arc
+        is taken and each state is entered from the start or through the leaky-HMM jump, in expectation over the paths of the
+        denominator's own model (outputs clamped to +-30, the graph's initial probabilities ``pi``, every state final).
+        Returns an ``ArcPosteriors`` on the input's device:
+
+        ``arcs``     float64 ``(A,)``: ``sum_b d log Z_b / d log w_a`` at fixed ``pi``, IN THE ORDER OF ``arcs()``;
+        ``entries``  float64 ``(H,)``: ``sum_b d log Z_b / d log pi(h)``;
+        ``leaks``    float64 ``(B,)``: the expected leaky-HMM jumps of each sequence, ``d log Z_b / d log c``;
+        ``logprob``  float64 ``(B,)``: ``log Z_b``;
+        ``per_seq_arcs``, ``per_seq_entries``: with ``per_sequence`` the float32 ``(B, A)`` and ``(B, H)`` rows the totals
+        are the double sums of, in sequence order; else ``None``.
+
+        ``arcs.sum()`` is the number of frames and ``entries.sum() == B + leaks.sum()``.  A sequence with a NaN or an infinity
+        in its valid frames gets +0 rows and NaN in ``leaks`` and ``logprob``; the others keep their bits.  A sequence's row
+        depends on its own frames alone, and the totals on the rows alone.
+
+        ``nnet_output``, ``frames`` and ``n_batch`` are ``best_path``'s: contiguous ``(B, C, T)`` float32 / bfloat16 / float16
+        or 2-D float32 ``(T*B, C)`` (row ``t*B + b``, read in place); anything else is copied into such a matrix first
+        (``tc_rows_gather``).  Beyond ``max_workspace_bytes`` consecutive groups of sequences run one after the other and
+        one reduction over all the rows follows: the single call's bits.  Asynchronous on the current stream; no autograd."""
+        who = "arc_posteriors"
+        x, B, T, lengths = self._accuracy_arguments(who, nnet_output, frames, n_batch)
+        P, H, A, device = self.n_pdf, self.num_states, self.num_arcs, x.device
+        leaky = float(leaky_hmm_coefficient)
+        if not (0.0 <= leaky < float("inf")):
+            raise ValueError("%s: the leaky-HMM coefficient must be finite and >= 0, got %r" % (who, leaky))
+        need = lambda n: int(lib.tc_den_arc_posteriors_workspace_bytes(self.ptr, n, T))  # noqa: E731  (host arithmetic only)
+        cap, group = int(max_workspace_bytes), B
+        if need(B) > cap:
+            if need(1) > cap:
+                raise ValueError("%s: one sequence needs %d bytes of workspace, %d are allowed" % (who, need(1), cap))
+            group = max(1, min(B, cap // need(1)))
+            while need(group) > cap:
+                group -= 1
+            while group < B and need(group + 1) <= cap:  # (the sizes are rounded up: as many sequences as fit)
+                group += 1
+        fr = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            y2d = self._accuracy_rows(x, B, T, stream)
+            arcs = torch.empty((A,), dtype=torch.float64, device=device)
+            entries = torch.empty((H,), dtype=torch.float64, device=device)
+            leaks = torch.empty((B,), dtype=torch.float64, device=device)
+            logprob = torch.empty((B,), dtype=torch.float64, device=device)
+            keep = per_sequence or group != B  # (the rows of every group, for the one reduction)
+            rows_a = torch.empty((B, A), dtype=torch.float32, device=device) if keep else None
+            rows_e = torch.empty((B, H), dtype=torch.float32, device=device) if keep else None
+            ws = torch.empty(need(group), dtype=torch.uint8, device=device)
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+            for s0 in range(0, B, group):
+                n = min(group, B - s0)
+                yg = _group_rows(y2d, s0, n, B, T)
+                check(lib.tc_den_arc_posteriors(self.ptr, n, ptr(yg), n * T, P, yg.stride(0),
+                                                None if fr is None else ptr(fr[s0:s0 + n]), T, leaky,
+                                                ptr(arcs) if n == B else None, ptr(entries) if n == B else None,
+                                                ptr(logprob[s0:s0 + n]), ptr(leaks[s0:s0 + n]),
+                                                None if rows_a is None else ptr(rows_a[s0:s0 + n]),
+                                                None if rows_e is None else ptr(rows_e[s0:s0 + n]), ptr(ws), ws.numel(),
+                                                device.index, stream), "tc_den_arc_posteriors")
+            if group != B:
+                check(lib.tc_den_arc_posteriors_reduce(B, A, H, ptr(rows_a), ptr(rows_e), ptr(arcs), ptr(entries), device.index,
+                                                       stream), "tc_den_arc_posteriors_reduce")
+        return ArcPosteriors(arcs, entries, leaks, logprob, rows_a if per_sequence else None, rows_e if per_sequence else None)
+
+
+ArcPosteriors = collections.namedtuple("ArcPosteriors", "arcs entries leaks logprob per_seq_arcs per_seq_entries")
 
 
 def _group_rows(m, s0, n, B, T):
