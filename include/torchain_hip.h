@@ -1039,6 +1039,55 @@ int tc_den_arc_posteriors(tc_den_graph *g, int32_t S, const float *nnet_output, 
 int tc_den_arc_posteriors_reduce(int32_t S, int64_t num_arcs, int32_t num_states, const void *per_seq_arcs,
                                  const void *per_seq_entries, double *arc_total, double *entry_total, int device, void *stream);
 
+/* ---- entropy of the denominator graph's path posterior (den_entropy_kernels.hip) ---------------------------------------------
+ * tc_den_path_entropy gives, per sequence s of T_s frames, the entropy of the posterior over the LATENT paths of the model
+ * that tc_den_sample_paths draws from (p_t(j) = exp(yh_t(j)), yh = clamp(y, +-30); the initial probabilities pi; every state
+ * final; the leaky-HMM coefficient c) and, with `grad`, its gradient.  A path holds (pre_t, post_t) at every level and an arc
+ * at every frame, W(path) = pi(pre_0) prod_{t<=T} lambda_t prod_{t<T} w_a p_t(pdf_a) with lambda_t = 1 without a leak and
+ * c pi(post_t) after one, Z_s = sum W, and
+ *     entropy_s = log Z_s - E_s[log W],      logprob_s = log Z_s.
+ * The entropy is over latent paths, not over pdf sequences.  Terms with pi(h) = 0 or c = 0 do not occur: no log 0 is formed.
+ * Recursions (Kaldi's scaling; f_t(a) = w_a exp(yh_t(pdf_a)) / asum_t, r_t(a) = log w_a + yh_t(pdf_a) - k_t, l(h) = log c pi(h)):
+ *     alpha_0 = pi, A_0 = pi log pi;  d_t = sum_h A_t(h) / asum_t;  alpha'_t = alpha_t + c pi asum_t
+ *     A'_t(h) = A_t(h) - d_t alpha_t(h) + c pi(h) [sum_g (A_t(g) - d_t alpha_t(g)) + asum_t l(h)]
+ *     alpha_{t+1}(g) = sum_{a: h->g} alpha'_t(h) f_t(a);  A_{t+1}(g) = sum_{a: h->g} [A'_t(h) + alpha'_t(h) r_t(a)] f_t(a)
+ *     E[log W] = sum_{t<=T} d_t + sum_{t<T} k_t + sum_h A'_T(h) / Z                      (in double)
+ *     beta'_T = 1 / Z, B'_T = 0;  beta_t = beta'_t + c sum_h pi(h) beta'_t(h);  B_t = B'_t + c sum_h pi(h) [B'_t(h) + l(h) beta'_t(h)]
+ *     beta'_t(h) = sum_{a: h->g} f_t(a) beta_{t+1}(g);  B'_t(h) = sum_{a: h->g} f_t(a) [B_{t+1}(g) + r_t(a) beta_{t+1}(g)]
+ *     d entropy / d yh_t(j) = -Cov(log W, [j at t]), from A', alpha', beta, B of the arcs of pdf j (the kernel's header).
+ * The centring constants d_t, k_t come from the forward pass itself (the prefix's log-weight is centred on its mean under
+ * the forward distribution at every level); the gradient does not depend on them.  The derivative is taken with respect
+ * to the CLAMPED output: an element outside +-30 gets the same expression, as in tc_den_expected_accuracy_grad.
+ *   nnet_output   : device float32 (T*S, P), row t*S + s, rows row_stride >= num_cols floats apart; num_rows = S *
+ *                   max_frames.  Rows of padding frames are not read.
+ *   seq_frames_dev: S device int32 lengths in 1 .. max_frames, or null (max_frames each).  Every graph is served.
+ *   entropy_dev, logprob_dev: device double[S].
+ *   grad          : nullable.  Device float32 (T*S, P), rows grad_stride >= num_cols floats apart: row t*S + s receives
+ *                   seq_scale_dev[s] (device float32[S]; null: 1) times d entropy_s / d yh_t, one store per element; +0 for a
+ *                   pdf without arcs and in padding frames.  Null: the value alone, a forward pass (seq_scale_dev null too).
+ *   workspace     : tc_den_path_entropy_workspace_bytes(g, S, max_frames, grad != null); 16-byte aligned.
+ * Arithmetic: vectors by state are float32 where stored, every sum over arcs or states is a double rounded once; log w and
+ * log pi are doubles taken on the host.  Every order is fixed and nothing is atomic: a sequence's outputs depend on its own
+ * rows of nnet_output, the graph and c alone.
+ * A sequence with a NaN or +-inf in its valid frames gets NaN in entropy_dev and logprob_dev and +0 in every row of grad;
+ * the others keep their bits.
+ * One launch (one workgroup of 16 wavefronts a sequence), asynchronous on `stream`, no host synchronisation.  The tables are
+ * those of tc_den_expected_accuracy_grad and a table of logarithms, uploaded on the graph's first call on the device; the
+ * training tables are neither read nor written.  The four per-state vectors and the frame's yh are in LDS while
+ * 16 * Hs + 4 * Ps + 1024 <= 163840 bytes (Hs, Ps: states and pdfs rounded up to 4), otherwise in the workspace with the
+ * same bits ("den_entropy_streamed_launches" counts those launches; tc_debug_set("force_den_entropy_streamed", 1) sends
+ * every graph there).  "den_entropy_launches" counts the calls.
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null graph, nnet_output, entropy_dev or logprob_dev; S or max_frames
+ * <= 0; num_rows != S * max_frames; num_cols != the graph's pdfs; row_stride < num_cols; grad with grad_stride < num_cols;
+ * seq_scale_dev without grad; a negative or non-finite coefficient; a misaligned pointer (4 bytes; 8 for doubles).
+ * TC_ERR_WORKSPACE: a null, short or misaligned workspace. */
+int64_t tc_den_path_entropy_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T, int32_t with_grad);
+int tc_den_path_entropy(tc_den_graph *g, int32_t S, const float *nnet_output, int64_t num_rows, int32_t num_cols,
+                        int64_t row_stride, const int32_t *seq_frames_dev /* nullable */, int32_t max_frames,
+                        float leaky_hmm_coefficient, double *entropy_dev /* [S] */, double *logprob_dev /* [S] */,
+                        float *grad /* nullable */, int64_t grad_stride, const float *seq_scale_dev /* nullable, [S] */,
+                        void *workspace, int64_t workspace_bytes, int device, void *stream);
+
 /* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
  * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token
  * sequences and scores each against its sequence's reference by the unit-cost Levenshtein distance: the risk of a
@@ -1287,6 +1336,8 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *                     bits.  Read at every such call)
  *   "force_den_sample_streamed" (1: tc_den_sample_paths forms the previous frame's alpha' from the workspace's row for
  *                     every graph, as it does for those beyond the LDS form; same bits.  Read at every such call)
+ *   "force_den_entropy_streamed" (1: tc_den_path_entropy keeps its per-frame vectors in the workspace for every graph, as it
+ *                     does for those beyond the LDS form; same bits.  Read at every such call)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -1328,7 +1379,9 @@ int tc_debug_set(const char *key, int value);
  * tc_sampled_risk_grad;
  * "boost_launches" = launches of boost_kernels.hip: 1 a tc_boost_rows call; 1 a tc_chain_step_boosted call with
  * l2_regularize == 0, 3 a training step and 2 an evaluation step with it (the pass, the sequences' sums, the gradient's
- * fix-up); 0 for every other entry.
+ * fix-up); 0 for every other entry;
+ * "den_entropy_launches" = tc_den_path_entropy calls that launched their kernel (not counted in "den_launches"), and
+ * "den_entropy_streamed_launches" those of them that kept the per-frame vectors in the workspace.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -239,6 +239,10 @@ def _load():
     L.tc_den_arc_posteriors.argtypes = [vp, i32, vp, i64, i32, i64, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, vp]
     L.tc_den_arc_posteriors_reduce.restype = C.c_int
     L.tc_den_arc_posteriors_reduce.argtypes = [i32, i64, i32, vp, vp, vp, vp, C.c_int, vp]
+    L.tc_den_path_entropy_workspace_bytes.restype = i64
+    L.tc_den_path_entropy_workspace_bytes.argtypes = [vp, i32, i32, i32]
+    L.tc_den_path_entropy.restype = C.c_int
+    L.tc_den_path_entropy.argtypes = [vp, i32, vp, i64, i32, i64, vp, i32, f32, vp, vp, vp, i64, vp, vp, i64, C.c_int, vp]
     L.tc_paths_edit_distance_workspace_bytes.restype = i64
     L.tc_paths_edit_distance_workspace_bytes.argtypes = [i32, i32, i32]
     L.tc_paths_edit_distance.restype = C.c_int

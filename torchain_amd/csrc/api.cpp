@@ -801,6 +801,51 @@ int tc_den_arc_posteriors_reduce(int32_t S, int64_t num_arcs, int32_t num_states
                                entry_total, (hipStream_t)stream_v);
 }
 
+int64_t tc_den_path_entropy_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T, int32_t with_grad) {
+  if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
+  return den_ent_workspace_bytes(g->H, g->P, S, T, with_grad != 0);
+}
+
+int tc_den_path_entropy(tc_den_graph *g, int32_t S, const float *y, int64_t rows, int32_t cols, int64_t y_stride,
+                        const int32_t *seq_frames_dev, int32_t max_frames, float leaky, double *entropy_dev,
+                        double *logprob_dev, float *grad, int64_t grad_stride, const float *seq_scale_dev, void *workspace,
+                        int64_t workspace_bytes, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!g || !y || !entropy_dev || !logprob_dev || S <= 0 || max_frames <= 0) return TC_ERR_INVALID_ARGUMENT;
+  if (rows != (int64_t)S * max_frames || cols != g->P || y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (grad ? grad_stride < cols : seq_scale_dev != nullptr) return TC_ERR_INVALID_ARGUMENT;
+  if (!(leaky >= 0.0f) || !(leaky <= FLT_MAX)) return TC_ERR_INVALID_ARGUMENT;
+  if ((((uintptr_t)y | (uintptr_t)seq_frames_dev | (uintptr_t)grad | (uintptr_t)seq_scale_dev) & 3) != 0 ||
+      (((uintptr_t)entropy_dev | (uintptr_t)logprob_dev) & 7) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  if (!workspace || den_ent_workspace_bytes(g->H, g->P, S, max_frames, grad != nullptr) > workspace_bytes || !aligned16(workspace))
+    return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  DenEntParams p;
+  const int rc = den_entropy_tables(g, device, &p.t);
+  if (rc != TC_OK) return rc;
+  p.y = y;
+  p.y_stride = y_stride;
+  p.S = S;
+  p.T = max_frames;
+  p.H = g->H;
+  p.P = g->P;
+  p.Hs = (int)den_acc_round4(g->H);
+  p.Ps = (int)den_acc_round4(g->P);
+  p.leaky = leaky;
+  p.log_leaky = leaky > 0.0f ? std::log((double)leaky) : 0.0;
+  p.seq_frames = seq_frames_dev;
+  p.entropy = entropy_dev;
+  p.logprob = logprob_dev;
+  p.seq_scale = seq_scale_dev;
+  p.grad = grad;
+  p.grad_stride = grad_stride;
+  p.workspace = (char *)workspace;
+  p.resident = den_ent_resident(g->H, g->P) && !debug_flag(kDbgForceDenEntropyStreamed);
+  return launch_den_entropy(p, (hipStream_t)stream_v);
+}
+
 int64_t tc_paths_edit_distance_workspace_bytes(int32_t S, int32_t K, int32_t max_frames) {
   if (S <= 0 || K <= 0 || max_frames <= 0) return TC_ERR_INVALID_ARGUMENT;
   return path_edit_workspace_bytes(S, K, max_frames);

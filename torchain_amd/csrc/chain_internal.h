@@ -373,6 +373,45 @@ inline int64_t den_sample_workspace_bytes(int H, int S, int T) {
   return (((int64_t)S * den_sample_seq_floats(H, T) * 4) + 255) & ~(int64_t)255;
 }
 
+// The entropy of the graph's path posterior and its gradient (tc_den_path_entropy, den_entropy_kernels.hip): the three CSRs
+// of DenAccDev (den_acc_tables) and, beside them, the logarithms the rewards are made of as doubles taken once on the host
+// (den_entropy_tables): log w of every arc in each CSR's order and log pi of every state (0 where pi(h) = 0: never read).
+struct DenEntDev {
+  DenAccDev t;
+  const double *in_logw = nullptr, *out_logw = nullptr, *pdf_logw = nullptr;  // [A], arc i of in_arcs, out_arcs, pdf_arcs
+  const double *log_pi = nullptr;                                             // [H]
+  void *blob = nullptr;
+};
+struct DenEntParams {
+  DenEntDev t;
+  const float *y;
+  int64_t y_stride;
+  int S, T, H, P, Hs, Ps;  // T: the longest sequence's frames; Hs, Ps: H, P rounded up to 4
+  float leaky;
+  double log_leaky;            // log c (0 when c = 0: every term it is in is multiplied by c)
+  const int32_t *seq_frames;   // [S] nullable
+  double *entropy, *logprob;   // [S]
+  const float *seq_scale;      // [S] nullable: 1
+  float *grad;                 // nullable: the value alone
+  int64_t grad_stride;
+  char *workspace;  // den_ent_workspace_bytes: per sequence [k_0..T-1 | alpha' | A' | 1 / asum] (with grad) and the streamed vectors
+  int resident;     // the per-frame vectors in LDS (den_ent_resident), else in the workspace
+};
+// floats of the per-frame vectors: two pairs of state vectors (forward: alpha, A and alpha', A'; backward: beta, B of frame
+// t + 1 and alpha', A' of frame t, which beta', B' of frame t then take over) and the frame's clamped y by pdf
+__host__ __device__ inline int64_t den_ent_frame_floats(int H, int P) { return 4 * den_acc_round4(H) + den_acc_round4(P); }
+constexpr int kDenEntSmallLds = 1024;  // the block reductions' slots, rounded up
+inline bool den_ent_resident(int H, int P) { return 4 * den_ent_frame_floats(H, P) + kDenEntSmallLds <= (int64_t)160 * 1024; }
+// per sequence, in floats (a multiple of 4, so the doubles in front stay aligned): with a gradient the frames' centring
+// constants as T + 1 doubles, alpha'_0..T, A'_0..T and 1 / asum_0..T; always room for the per-frame vectors
+__host__ __device__ inline int64_t den_ent_seq_floats(int H, int P, int T, bool grad) {
+  const int64_t hist = grad ? 2 * den_acc_round4(T + 1) + 2 * (int64_t)(T + 1) * den_acc_round4(H) + den_acc_round4(T + 1) : 0;
+  return hist + den_ent_frame_floats(H, P);
+}
+inline int64_t den_ent_workspace_bytes(int H, int P, int S, int T, bool grad) {
+  return (((int64_t)S * den_ent_seq_floats(H, P, T, grad) * 4) + 255) & ~(int64_t)255;
+}
+
 // Token sequences and edit distances of frame-level pdf paths (tc_paths_edit_distance, path_edit_kernels.hip)
 struct PathEditParams {
   const int32_t *pdf;           // [paths][T]
@@ -555,6 +594,8 @@ struct tc_den_graph {
   // counted yet)
   std::map<int, tc::DenArcDev> arc_dev;
   int arc_rows = -1;
+  // ... and tc_den_path_entropy's logarithms (den_entropy_kernels.hip, den_entropy_tables), beside acc_dev's CSRs
+  std::map<int, tc::DenEntDev> ent_dev;
 };
 
 // ---- numerator -----------------------------------------------------------------------------------
@@ -800,6 +841,8 @@ int launch_den_arc_post(const DenArcParams &p, hipStream_t stream);     // den_a
 int launch_den_arc_reduce(const float *part_arcs, const float *part_entries, int S, int64_t A, int H, double *arc_total,
                           double *entry_total, hipStream_t stream);
 int den_arc_tables(tc_den_graph *g, int device, DenArcDev *out);     // den_graph.cpp: made and uploaded on first use
+int launch_den_entropy(const DenEntParams &p, hipStream_t stream);      // den_entropy_kernels.hip
+int den_entropy_tables(tc_den_graph *g, int device, DenEntDev *out);  // den_graph.cpp: made and uploaded on first use
 int launch_path_edit(const PathEditParams &p, hipStream_t stream);      // path_edit_kernels.hip
 int launch_sampled_risk_grad(const SampledRiskGradParams &p, int dtype, hipStream_t stream);
 // dynamic LDS of num_e2e_kernel: two double score vectors, the frame's y per distinct pdf and one float per arc (max_arcs = 0:
@@ -956,7 +999,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -965,7 +1008,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

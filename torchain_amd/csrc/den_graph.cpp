@@ -426,7 +426,7 @@ extern "C" {
 int tc_debug_set(const char *key, int value) {
   static const char *const names[kDbgCount] = {"force_general", "force_streamed", "no_split", "no_pdf_banks",
                                                "no_bank_search", "sched_trace", "no_phase_split", "no_num_overlap", "no_pair",
-                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout", "force_den_accuracy_streamed", "force_den_sample_streamed", "force_den_arc_post_streamed"};
+                                               "force_pair", "no_tune", "no_mitm", "force_mitm", "slab_wide", "slab_narrow", "exp_per_frame", "old_arrange", "no_planes", "old_general", "phantom_pdf0", "no_pdf_search", "no_split_source", "planes_meet_at", "force_num_windowed", "force_den_best_path_streamed", "force_num_e2e_large", "no_full_layout", "force_den_accuracy_streamed", "force_den_sample_streamed", "force_den_arc_post_streamed", "force_den_entropy_streamed"};
   if (!key) return TC_ERR_INVALID_ARGUMENT;
   for (int i = 0; i < kDbgCount; ++i)
     if (!strcmp(key, names[i])) {
@@ -466,7 +466,7 @@ int64_t tc_debug_counter(const char *key) {
   if (key && !strcmp(key, "pool_device_allocs")) return pool_counter(0);
   if (key && !strcmp(key, "pool_reuses")) return pool_counter(1);
   static const char *const names[kCntCount] = {"den_launches", "den_backward_launches", "num_launches", "num_backward_launches", "layout_launches",
-                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches", "den_sample_launches", "den_sample_streamed_launches", "path_edit_launches", "sampled_risk_grad_launches", "boost_launches", "den_arc_post_launches", "den_arc_post_streamed_launches"};
+                                              "den_long_utterance_launches", "num_e2e_staged_launches", "num_windowed_launches", "channel_last_steps", "ragged_steps", "ragged_two_cu_launches", "best_path_launches", "den_best_path_launches", "den_best_path_streamed_launches", "xent_log_softmax_launches", "num_e2e_large_launches", "tied_full_layout_launches", "den_accuracy_launches", "den_accuracy_grad_launches", "den_accuracy_grad_streamed_launches", "den_accuracy_dense_launches", "den_accuracy_dense_grad_launches", "den_sample_launches", "den_sample_streamed_launches", "path_edit_launches", "sampled_risk_grad_launches", "boost_launches", "den_arc_post_launches", "den_arc_post_streamed_launches", "den_entropy_launches", "den_entropy_streamed_launches"};
   for (int i = 0; key && i < kCntCount; ++i)
     if (!strcmp(key, names[i])) return g_launches[i].load(std::memory_order_relaxed);
   return -1;
@@ -673,6 +673,14 @@ void tc_den_graph_free(tc_den_graph *g) {
     }
   }
   for (auto &kv : g->arc_dev) {
+    int cur = 0;
+    if (kv.second.blob && hipGetDevice(&cur) == hipSuccess) {
+      (void)hipSetDevice(kv.first);
+      (void)hipFree(kv.second.blob);
+      (void)hipSetDevice(cur);
+    }
+  }
+  for (auto &kv : g->ent_dev) {
     int cur = 0;
     if (kv.second.blob && hipGetDevice(&cur) == hipSuccess) {
       (void)hipSetDevice(kv.first);
@@ -1332,6 +1340,69 @@ int tc::den_arc_tables(tc_den_graph *g, int device, DenArcDev *out) {
   d.tier = tier;
   d.blob = blob;
   g->arc_dev[device] = d;
+  *out = d;
+  return TC_OK;
+}
+
+// tc_den_path_entropy's tables: den_acc_tables' CSRs and, in a blob of their own, log w of every arc in the order of each of
+// the three CSRs and log pi of every state, as doubles (the rewards of the expectation semiring; pi(h) = 0 gives 0, which
+// nothing reads).  Built and uploaded on the first call per device.
+int tc::den_entropy_tables(tc_den_graph *g, int device, DenEntDev *out) {
+  DenAccDev acc;
+  const int rc = den_acc_tables(g, device, &acc);
+  if (rc != TC_OK) return rc;
+  std::lock_guard<std::mutex> lock(g->mu);
+  auto it = g->ent_dev.find(device);
+  if (it != g->ent_dev.end()) {
+    *out = it->second;
+    return TC_OK;
+  }
+  const int H = g->H, P = g->P;
+  const int64_t A = g->A;
+  const size_t An = (size_t)std::max<int64_t>(A, 1);
+  // [in | out | pdf | log pi]; a row's arcs in the order of the graph's arc list, as den_acc_tables fills them
+  std::vector<double> table(3 * An + (size_t)H, 0.0);
+  {
+    std::vector<int64_t> fi(H + 1, 0), fo(H + 1, 0), fp(P + 1, 0);
+    for (int64_t a = 0; a < A; ++a) {
+      ++fi[g->arc_dst[a] + 1];
+      ++fo[g->arc_src[a] + 1];
+      ++fp[g->arc_pdf[a] + 1];
+    }
+    for (int h = 0; h < H; ++h) {
+      fi[h + 1] += fi[h];
+      fo[h + 1] += fo[h];
+    }
+    for (int j = 0; j < P; ++j) fp[j + 1] += fp[j];
+    for (int64_t a = 0; a < A; ++a) {
+      const double lw = std::log((double)g->arc_prob[a]);
+      table[fi[g->arc_dst[a]]++] = lw;
+      table[An + fo[g->arc_src[a]]++] = lw;
+      table[2 * An + fp[g->arc_pdf[a]]++] = lw;
+    }
+    for (int h = 0; h < H; ++h)
+      if (g->initial_probs[h] > 0.f) table[3 * An + h] = std::log((double)g->initial_probs[h]);
+  }
+  int prev = 0;
+  TC_HIP_CHECK(hipGetDevice(&prev));
+  TC_HIP_CHECK(hipSetDevice(device));
+  double *blob = nullptr;
+  hipError_t e = hipMalloc((void **)&blob, table.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(blob, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice);
+  (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    if (blob) (void)hipFree(blob);
+    g_last_hip_error = (int)e;
+    return TC_ERR_HIP;
+  }
+  DenEntDev d;
+  d.t = acc;
+  d.in_logw = blob;
+  d.out_logw = blob + An;
+  d.pdf_logw = blob + 2 * An;
+  d.log_pi = blob + 3 * An;
+  d.blob = blob;
+  g->ent_dev[device] = d;
   *out = d;
   return TC_OK;
 }

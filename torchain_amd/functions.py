@@ -1057,6 +1057,47 @@ def den_arc_posteriors(input, den_graph, frames=None, leaky_hmm_coefficient=1e-5
                                         per_sequence=per_sequence, max_workspace_bytes=max_workspace_bytes, n_batch=n_batch)
 
 
+class _DenPathEntropy(torch.autograd.Function):
+    """``den_path_entropy``: forward is one ``tc_den_path_entropy`` launch per group -- the forward pass alone, or with
+    ``want_grad`` the whole kernel, whose gradient is kept; backward scales each sequence's rows by ``grad_output``."""
+
+    @staticmethod
+    def forward(ctx, input, den_graph, frames, leaky_hmm_coefficient, n_batch, max_workspace_bytes, want_grad):
+        st = den_graph._path_entropy("den_path_entropy", input, frames, leaky_hmm_coefficient, n_batch, max_workspace_bytes,
+                                     want_grad)
+        if want_grad:
+            ctx.grad, ctx.shape, ctx.like = st["grad"], (st["T"], st["B"]), (input.dim(), input.dtype)
+        ctx.mark_non_differentiable(st["logprob"])
+        return st["entropy"], st["logprob"]
+
+    @staticmethod
+    def backward(ctx, grad_entropy, _grad_logprob):
+        (T, B), (dim, dtype) = ctx.shape, ctx.like
+        scale = grad_entropy.detach().to(device=ctx.grad.device, dtype=torch.float32)
+        grad = (ctx.grad.view(T, B, -1) * scale.view(1, B, 1)).view(T * B, -1)
+        if dim == 3:  # (T*B, C) rows t*B + b -> (B, C, T); not a hot path
+            grad = grad.view(T, B, -1).permute(1, 2, 0).contiguous()
+        return (grad.to(dtype),) + (None,) * 6
+
+
+def den_path_entropy(input, den_graph, frames=None, leaky_hmm_coefficient=1e-5, n_batch=None, max_workspace_bytes=8 << 30):
+    """The entropy of ``den_graph``'s path posterior under ``input`` and its log-likelihood: ``(entropy, logprob)``, float64
+    ``(B,)`` each, ``entropy`` differentiable in ``input`` (``io.DenominatorGraph.path_entropy`` states the quantity and the
+    arguments; ``tc_den_path_entropy``).  No transcript is involved.  Minimise ``entropy.sum()`` on untranscribed audio
+    (conditional-entropy minimisation, the lattice-free form of semi-supervised NCE); add ``-eps * entropy.sum()`` to a
+    sequence loss against peaky posteriors; or read ``entropy / frames`` as a confidence.
+
+    Under ``no_grad``, or when ``input`` requires no gradient, only the forward pass runs.  Otherwise the one launch also
+    leaves ``d entropy[b] / d input`` (with respect to the clamped outputs), and backward multiplies sequence ``b``'s rows by
+    ``grad_output[b]``.  The gradient has the input's shape and dtype (float32 arithmetic, rounded once); padding frames and
+    a sequence with a NaN or an infinity in its valid frames get 0.  Beyond ``max_workspace_bytes`` consecutive groups of
+    sequences run, with the single call's bits; ``ValueError`` only where one sequence alone does not fit."""
+    if not isinstance(den_graph, io.DenominatorGraph):
+        raise TypeError("den_path_entropy takes an io.DenominatorGraph, got %s" % type(den_graph).__name__)
+    want_grad = torch.is_grad_enabled() and isinstance(input, torch.Tensor) and input.requires_grad
+    return _DenPathEntropy.apply(input, den_graph, frames, leaky_hmm_coefficient, n_batch, max_workspace_bytes, want_grad)
+
+
 def _int_vector(who, name, v, n, device, dtype=torch.int32):
     """``v`` as a contiguous ``(n,)`` tensor of ``dtype`` on ``device`` (a tensor already there is not brought to the host)."""
     t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)

@@ -720,6 +720,64 @@ class DenominatorGraph:
                                                        stream), "tc_den_arc_posteriors_reduce")
         return ArcPosteriors(arcs, entries, leaks, logprob, rows_a if per_sequence else None, rows_e if per_sequence else None)
 
+    def path_entropy(self, nnet_output, frames=None, leaky_hmm_coefficient=1e-5, n_batch=None, max_workspace_bytes=1 << 30):
+        """How uncertain this graph's path posterior is under ``nnet_output`` (``tc_den_path_entropy``): ``(entropy, logprob)``,
+        float64 ``(B,)`` each, ``entropy[b] = -sum_paths P(path | y_b) log P(path | y_b) = log Z_b - E_b[log W]`` and
+        ``logprob[b] = log Z_b``, over the latent paths of the denominator's own model -- outputs clamped to +-30, the graph's
+        initial probabilities, every state final, the leaky-HMM transitions; the model ``sample_paths`` draws from.  It
+        needs no transcript: the criterion for untranscribed audio (conditional-entropy minimisation), a regulariser against
+        peaky posteriors, a per-utterance confidence.  A sequence with a NaN or an infinity in its valid frames gets NaN in
+        both; the others keep their bits.
+
+        ``nnet_output``, ``frames`` and ``n_batch`` are ``best_path``'s: contiguous ``(B, C, T)`` float32 / bfloat16 / float16
+        or 2-D float32 ``(T*B, C)`` (row ``t*B + b``, read in place); anything else is copied into such a matrix first
+        (``tc_rows_gather``).  One launch of the forward pass alone; beyond ``max_workspace_bytes`` consecutive groups of
+        sequences run one after the other with the bits of one call.  Asynchronous on the current stream; no autograd:
+        ``functions.den_path_entropy`` is the differentiable entry."""
+        st = self._path_entropy("path_entropy", nnet_output, frames, leaky_hmm_coefficient, n_batch, max_workspace_bytes, False)
+        return st["entropy"], st["logprob"]
+
+    def _path_entropy(self, who, nnet_output, frames, leaky, n_batch, max_workspace_bytes, want_grad):
+        """The checks, the 2-D float32 matrix and ``tc_den_path_entropy`` on every group of sequences.  ``want_grad``: the
+        launches also leave ``grad``, float32 ``(T*B, C)``, row ``t*B + b`` the derivative of ``entropy[b]`` (+0 in padding
+        rows and in a failed sequence's)."""
+        x, B, T, lengths = self._accuracy_arguments(who, nnet_output, frames, n_batch)
+        P, device = self.n_pdf, x.device
+        leaky = float(leaky)
+        if not (0.0 <= leaky < float("inf")):
+            raise ValueError("%s: the leaky-HMM coefficient must be finite and >= 0, got %r" % (who, leaky))
+        need = lambda n: int(lib.tc_den_path_entropy_workspace_bytes(self.ptr, n, T, int(want_grad)))  # noqa: E731  (host only)
+        cap, group = int(max_workspace_bytes), B
+        if need(B) > cap:
+            if need(1) > cap:
+                raise ValueError("%s: one sequence of %d frames needs %d bytes of workspace, %d are allowed"
+                                 % (who, T, need(1), cap))
+            group = max(1, min(B, cap // need(1)))
+            while need(group) > cap:
+                group -= 1
+            while group < B and need(group + 1) <= cap:  # (the sizes are rounded up: as many sequences as fit)
+                group += 1
+        fr = None if lengths is None else torch.from_numpy(np.ascontiguousarray(lengths, dtype=np.int32)).to(device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            y2d = self._accuracy_rows(x, B, T, stream)
+            entropy = torch.empty((B,), dtype=torch.float64, device=device)
+            logprob = torch.empty((B,), dtype=torch.float64, device=device)
+            grad = torch.empty((T * B, P), dtype=torch.float32, device=device) if want_grad else None
+            ws = torch.empty(need(group), dtype=torch.uint8, device=device)
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+            for s0 in range(0, B, group):
+                n = min(group, B - s0)
+                yg = _group_rows(y2d, s0, n, B, T)
+                gg = grad if n == B or grad is None else torch.empty((T * n, P), dtype=torch.float32, device=device)
+                check(lib.tc_den_path_entropy(self.ptr, n, ptr(yg), n * T, P, yg.stride(0),
+                                              None if fr is None else ptr(fr[s0:s0 + n]), T, leaky, ptr(entropy[s0:s0 + n]),
+                                              ptr(logprob[s0:s0 + n]), ptr(gg), P, None, ptr(ws), ws.numel(), device.index,
+                                              stream), "tc_den_path_entropy")
+                if gg is not grad:
+                    grad.view(T, B, P)[:, s0:s0 + n].copy_(gg.view(T, n, P))
+        return {"entropy": entropy, "logprob": logprob, "grad": grad, "B": B, "T": T}
+
 
 ArcPosteriors = collections.namedtuple("ArcPosteriors", "arcs entries leaks logprob per_seq_arcs per_seq_entries")
 
