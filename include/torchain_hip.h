@@ -1088,6 +1088,55 @@ int tc_den_path_entropy(tc_den_graph *g, int32_t S, const float *nnet_output, in
                         float *grad /* nullable */, int64_t grad_stride, const float *seq_scale_dev /* nullable, [S] */,
                         void *workspace, int64_t workspace_bytes, int device, void *stream);
 
+/* ---- entropy of an end-to-end supervision's alignment posterior (num_entropy_kernels.hip) ------------------------------------
+ * tc_supervision_path_entropy gives, per sequence s of an END-TO-END handle, the entropy of the numerator's posterior over
+ * the paths of exactly T_s arcs from the sequence's start state to a final state (parallel arcs make distinct paths), and
+ * with `grad` its gradient: the maximum-entropy regulariser of flat-start training, and per utterance the ambiguity of its
+ * alignment.  With log W(path) = sum_t (y_t(pdf_t) - cost_t) - final cost (y unclamped, as in the numerator) and Z_s = sum W:
+ *     entropy_s = log Z_s - E_s[log W],      logprob_s = log Z_s      (the supervision's weight does not enter)
+ *     d entropy_s / d y_t(j) = -(E_s[log W 1(pdf j at t)] - E_s[log W] gamma_t(j)).
+ * Recursions: the numerator's forward-backward in the expectation semiring, in the log domain and in mean form.  Beside
+ * log alpha_t(j) a state carries Abar_t(j), the posterior mean of the prefix's log W over the prefixes that reach it:
+ *     share(a) = exp(log alpha_t(i) + r_a - log alpha_{t+1}(j)),  r_a = y_t(pdf_a) - cost_a   (arc a: i -> j)
+ *     Abar_{t+1}(j) = sum over in-arcs of share(a) (Abar_t(i) + r_a);   (log beta_t(i), Bbar_t(i)) likewise over out-arcs,
+ *     log beta_T = Bbar_T = -final cost;   E[log W] = the softmax-weighted mean of Abar_T(i) - final(i) over the final states;
+ *     grad(t, j) = -sum over arcs of pdf j of occ_t(a) (Abar_t(i) + r_a + Bbar_{t+1}(dst) - E[log W]).
+ * Means are doubles; a share or an occupation is the float32 exp of a double difference, as in the numerator; y + (-cost)
+ * is one float32 sum.  No centring pass is needed: a mean is of the size of log W whatever the weights are.
+ *   nnet_output, dtype, layout_bct, num_rows, num_cols, row_stride : as tc_supervision_best_path's.
+ *   entropy_dev, logprob_dev : device double[S].
+ *   grad        : nullable.  In the input's layout and dtype: float32 rows of grad_stride >= num_cols floats (row t*S + s),
+ *                 or the contiguous (S, P, T) tensor of `dtype` (grad_stride is not read).  Every element is written once
+ *                 with a value: grad_output_dev[s] (device double[S]; null: 1) times the derivative, +0 in padding frames,
+ *                 at pdfs the sequence has no arc of, and in every frame of a failed sequence.  Null: the value alone, a
+ *                 forward pass that writes no history (grad_output_dev null too).
+ *   workspace   : tc_supervision_path_entropy_workspace_bytes(supervision, grad != null) bytes, 16-byte aligned: the history
+ *                 (log alpha_t, Abar_t), 16 bytes a (frame, state), and the per-arc terms when they do not fit LDS.  0 bytes
+ *                 for the value alone (workspace may then be null).  The supervision's pool slot holds the tables only: its
+ *                 scratch is not touched, and a training step on the handle gives the same bits before and after this call.
+ * A sequence with no path of T_s arcs gets logprob -inf, entropy NaN and a +0 gradient.  A sequence with a NaN or +-inf at
+ * one of its own (frame, pdf) pairs -- its valid frames, the pdfs of its arcs: nothing else is read -- gets NaN in both and a
+ * +0 gradient.  The other sequences keep their bits; every sum has a fixed order and nothing is atomic, so a sequence's
+ * outputs do not depend on its batch.
+ * One launch, one workgroup of 256 threads a sequence; threads own states and distinct pdfs as in the numerator.  LDS, laid
+ * out per sequence: 32 * ceil4(states) + 4 * ceil4(distinct pdfs) bytes, plus 4 * ceil4(arcs) when the handle's largest
+ * counts leave room (otherwise the per-arc terms live in the workspace), plus 2048.  Every handle of
+ * tc_supervision_create_e2e and _e2e_ragged fits (at most 102400 + 2048 bytes).  A handle of _e2e_any is served when every
+ * sequence meets 32 * ceil4(states) + 4 * ceil4(distinct pdfs) + 2048 <= 163840 (about 5000 states with few pdfs).
+ * TC_ERR_UNSUPPORTED, before any launch (the workspace query returns it too): a regular (time-unfolded) supervision; an
+ * end-to-end sequence beyond that bound.  TC_ERR_INVALID_ARGUMENT, before any device call: a null supervision, nnet_output,
+ * entropy_dev or logprob_dev; num_rows or num_cols that are not the handle's; an unknown dtype; a 2-D call with a 16-bit
+ * dtype, row_stride < num_cols or grad with grad_stride < num_cols; grad_output_dev without grad; a misaligned pointer (the
+ * element's size; 8 for doubles).  TC_ERR_WORKSPACE: a short, misaligned or (when bytes are needed) null workspace.
+ * Asynchronous on `stream`, no allocation once the supervision is staged, no host synchronisation.
+ * tc_debug_counter("num_entropy_launches") counts the launches ("num_launches" does not move). */
+int64_t tc_supervision_path_entropy_workspace_bytes(const tc_supervision *supervision, int32_t with_grad);
+int tc_supervision_path_entropy(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
+                                int64_t num_rows, int32_t num_cols, int64_t row_stride, double *entropy_dev /* [S] */,
+                                double *logprob_dev /* [S] */, void *grad /* nullable */, int64_t grad_stride,
+                                const double *grad_output_dev /* nullable, [S] */, void *workspace, int64_t workspace_bytes,
+                                int device, void *stream);
+
 /* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
  * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token
  * sequences and scores each against its sequence's reference by the unit-cost Levenshtein distance: the risk of a
@@ -1381,7 +1430,8 @@ int tc_debug_set(const char *key, int value);
  * l2_regularize == 0, 3 a training step and 2 an evaluation step with it (the pass, the sequences' sums, the gradient's
  * fix-up); 0 for every other entry;
  * "den_entropy_launches" = tc_den_path_entropy calls that launched their kernel (not counted in "den_launches"), and
- * "den_entropy_streamed_launches" those of them that kept the per-frame vectors in the workspace.
+ * "den_entropy_streamed_launches" those of them that kept the per-frame vectors in the workspace;
+ * "num_entropy_launches" = tc_supervision_path_entropy calls that launched their kernel (not counted in "num_launches").
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -866,6 +866,40 @@ inline size_t e2e_seq_lds_bytes(int max_states, int max_pdfs) {
   const size_t both = num_e2e_lds_bytes(max_states, 0, max_pdfs), rule = (size_t)kLdsLimitBytes - 2048;
   return both < rule ? both : rule;
 }
+// The entropy of an end-to-end supervision's path posterior and its gradient (tc_supervision_path_entropy,
+// num_entropy_kernels.hip).  `n` carries what the numerator's launches carry (tables, y, its layout and element type, S, T, P,
+// the lengths of a ragged handle); the pool slot's scratch (E2eDev::alpha_hist, NumDev::stage) is neither read nor written.
+struct NumEntParams {
+  NumParams n;
+  double *entropy, *logprob;   // [S]
+  void *grad;                  // nullable: the value alone.  Laid out as y is: float32 rows of grad_stride, or (S, P, T) of n.elem
+  int64_t grad_stride;
+  const double *grad_output;   // [S] nullable: 1
+  // num_ent_workspace_bytes (with a gradient only): per sequence the history (log alpha_t, Abar_t), t = 0 .. T - 1, two doubles
+  // a (frame, state) at 2 * T * state_off[s] doubles; behind all of them, when terms_in_lds == 0, one float per arc at arc_off[s]
+  double *hist;
+  float *terms;
+  int terms_in_lds;
+};
+// LDS of num_entropy_kernel, laid out per sequence: (log alpha, Abar) or (log beta, Bbar) of two adjacent levels -- four
+// double vectors of ceil4(states) -- the frame's y per distinct pdf and, when they fit beside those, one float per arc.
+// kNumEntStaticLds covers the block reductions' slots.  A sequence is served while num_ent_fits: 32 * ceil4(states) +
+// 4 * ceil4(distinct pdfs) + 2048 <= 163840 bytes (about 5000 states with few pdfs; 2048 states beside 24064 pdfs).
+constexpr int kNumEntStaticLds = 2048;
+inline size_t num_ent_lds_bytes(int states, int arcs, int pdfs) {
+  return (size_t)32 * ((states + 3) & ~3) + (size_t)4 * (((pdfs + 3) & ~3) + ((arcs + 3) & ~3));
+}
+inline bool num_ent_fits(int states, int pdfs) { return num_ent_lds_bytes(states, 0, pdfs) + kNumEntStaticLds <= (size_t)kLdsLimitBytes; }
+inline bool num_ent_terms_in_lds(int max_states, int max_arcs, int max_pdfs) {
+  return num_ent_lds_bytes(max_states, max_arcs, max_pdfs) + kNumEntStaticLds <= (size_t)kLdsLimitBytes;
+}
+inline int64_t num_ent_hist_bytes(int64_t total_states, int T) { return ((int64_t)16 * T * total_states + 255) & ~(int64_t)255; }
+inline int64_t num_ent_workspace_bytes(int64_t total_states, int64_t total_arcs, int T, bool terms_in_lds, bool grad) {
+  if (!grad) return 0;
+  return num_ent_hist_bytes(total_states, T) + (terms_in_lds ? 0 : ((total_arcs * 4 + 255) & ~(int64_t)255));
+}
+int launch_num_entropy(const NumEntParams &p, hipStream_t stream);  // num_entropy_kernels.hip
+
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
 // the denominator leaves CUs idle (api.cpp).
@@ -1008,7 +1042,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

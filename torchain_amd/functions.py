@@ -1098,6 +1098,45 @@ def den_path_entropy(input, den_graph, frames=None, leaky_hmm_coefficient=1e-5, 
     return _DenPathEntropy.apply(input, den_graph, frames, leaky_hmm_coefficient, n_batch, max_workspace_bytes, want_grad)
 
 
+class _NumPathEntropy(torch.autograd.Function):
+    """``num_path_entropy``: forward is ``tc_supervision_path_entropy``'s forward pass alone.  Backward is the whole kernel
+    with ``grad_output`` handed to it: the forward pass is run again instead of keeping its history, so no ``(B, C, T)``
+    buffer lives between the two, and every gradient element is formed, scaled and stored once."""
+
+    @staticmethod
+    def forward(ctx, input, supervision):
+        entropy, logprob, _ = supervision._path_entropy("num_path_entropy", input)
+        ctx.input, ctx.supervision = input.detach(), supervision
+        ctx.mark_non_differentiable(logprob)
+        return entropy, logprob
+
+    @staticmethod
+    def backward(ctx, grad_entropy, _grad_logprob):
+        grad = ctx.supervision._path_entropy("num_path_entropy", ctx.input, grad_output=grad_entropy, workspace=_workspace)[2]
+        return grad.to(ctx.input.dtype).view(ctx.input.shape), None
+
+
+def num_path_entropy(input, supervision):
+    """The entropy of an end-to-end ``supervision``'s alignment posterior under ``input`` and the numerator's log-likelihood:
+    ``(entropy, logprob)``, float64 ``(B,)`` each, ``entropy`` differentiable in ``input`` (``io.Supervision.path_entropy``
+    states the quantity; ``tc_supervision_path_entropy``).  Add ``-eps * entropy.sum()`` to a flat-start ``chain_loss``
+    against an early collapse onto one alignment (maximum-entropy regularisation, Liu et al. 2018); read ``entropy`` per
+    utterance as the ambiguity of its alignment; with ``den_path_entropy`` it gives both halves of a conditional-entropy
+    criterion.  ``input`` is what ``chain_loss`` takes: 2-D float32 ``(T*B, C)`` and contiguous ``(B, C, T)`` in float32,
+    bfloat16 or float16 are read where they lie.
+
+    Under ``no_grad``, or when ``input`` requires no gradient, only the forward pass runs.  Otherwise backward is one more
+    launch, which leaves ``grad_output[b] * d entropy[b] / d input`` in the input's shape and dtype (double means, float32
+    terms, rounded once); padding frames, pdfs a sequence has no arc of, and a sequence without a path or with a NaN or an
+    infinity among its outputs get 0.  ``logprob`` is not differentiable (``chain_loss`` is the entry for that)."""
+    if not isinstance(supervision, io.Supervision):
+        raise TypeError("num_path_entropy takes an io.Supervision, got %s" % type(supervision).__name__)
+    if torch.is_grad_enabled() and isinstance(input, torch.Tensor) and input.requires_grad:
+        return _NumPathEntropy.apply(input, supervision)
+    with torch.no_grad():
+        return supervision.path_entropy(input)
+
+
 def _int_vector(who, name, v, n, device, dtype=torch.int32):
     """``v`` as a contiguous ``(n,)`` tensor of ``dtype`` on ``device`` (a tensor already there is not brought to the host)."""
     t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)

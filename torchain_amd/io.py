@@ -1100,6 +1100,62 @@ class Supervision:
                   "tc_supervision_best_path")
         return pdfs, scores
 
+    def path_entropy(self, nnet_output):
+        """How ambiguous every sequence's alignment is under ``nnet_output`` (``tc_supervision_path_entropy``): ``(entropy,
+        logprob)``, float64 ``(B,)`` each on the input's device.  END-TO-END handles only (``from_e2e_fsts``, the
+        ``<End2End>`` egs), uniform and ragged; a regular handle raises ``TorchainHipError`` (unsupported), as does an
+        end-to-end sequence of more than about 5000 states.
+
+        The paths of sequence ``b`` are the arc sequences of exactly ``T_b`` arcs from its FST's start state to a final state,
+        ``log W = sum_t (y_t(pdf_t) - cost_t) - final cost``, ``logprob[b] = log Z_b = log sum W`` (the numerator's, without the
+        supervision's weight) and ``entropy[b] = log Z_b - E_b[log W]``: 0 when one alignment carries all the mass, ``T log m``
+        when ``m`` equally good arcs compete at every frame.  A sequence without a path of its length gets ``(NaN, -inf)``, one
+        with a NaN or an infinity among the outputs it reads ``(NaN, NaN)``; the others keep their bits.
+
+        ``nnet_output`` is ``best_path``'s.  No autograd here -- ``functions.num_path_entropy`` is the differentiable entry --
+        and only the kernel's forward pass runs.  The handle's pool slot is not written: a ``chain_loss`` on the handle is not
+        affected."""
+        return self._path_entropy("path_entropy", nnet_output)[:2]
+
+    def _path_entropy(self, who, nnet_output, grad_output=None, workspace=None):
+        """The checks and one ``tc_supervision_path_entropy`` launch: ``(entropy, logprob, grad)``.  With ``grad_output``
+        (float64 ``(B,)``) the launch also writes ``grad_output[b] * d entropy[b] / d y`` in the prepared input's layout and
+        dtype, its history in ``workspace(device, stream, nbytes)``; without it ``grad`` is ``None`` and no workspace is needed."""
+        x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("%s: nnet_output must be a CUDA tensor (only the HIP implementation is available)" % who)
+        S, T, P = self.n_batch, self.n_frame, self.n_pdf
+        want = (S, P, T) if x.dim() == 3 else (S * T, P)
+        if x.dim() not in (2, 3) or tuple(x.shape) != want:
+            raise ValueError("%s: nnet output of shape %s does not match the supervision (%s expected)" % (who, tuple(x.shape), want))
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dtype not in dtypes or (x.dim() == 2 and x.dtype != torch.float32):
+            x = x.float()
+        if (x.dim() == 3 and not x.is_contiguous()) or (x.dim() == 2 and (x.stride(1) != 1 or x.stride(0) < P)):
+            x = x.contiguous()
+        device = x.device
+        want_grad = grad_output is not None
+        need = int(lib.tc_supervision_path_entropy_workspace_bytes(self.ptr, int(want_grad)))  # (host arithmetic only)
+        check(min(need, 0), "tc_supervision_path_entropy_workspace_bytes")
+        entropy = torch.empty((S,), dtype=torch.float64, device=device)
+        logprob = torch.empty((S,), dtype=torch.float64, device=device)
+        grad = scale = ws = None
+        with torch.cuda.device(device):
+            cur = torch.cuda.current_stream(device).cuda_stream
+            if want_grad:
+                grad = torch.empty_like(x, memory_format=torch.contiguous_format)  # (the kernel writes every element)
+                scale = grad_output.detach().to(device=device, dtype=torch.float64).contiguous()
+                if tuple(scale.shape) != (S,):
+                    raise ValueError("%s: grad_output of shape %s is not (%d,)" % (who, tuple(scale.shape), S))
+                ws = workspace(device, cur, max(need, 256))
+            check(lib.tc_supervision_path_entropy(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
+                                                  x.stride(0) if x.dim() == 2 else 0, C.c_void_p(entropy.data_ptr()),
+                                                  C.c_void_p(logprob.data_ptr()), C.c_void_p(grad.data_ptr()) if want_grad else None,
+                                                  P, C.c_void_p(scale.data_ptr()) if want_grad else None,
+                                                  C.c_void_p(ws.data_ptr()) if want_grad else None, ws.numel() if want_grad else 0,
+                                                  device.index, C.c_void_p(cur)), "tc_supervision_path_entropy")
+        return entropy, logprob, grad
+
     def posteriors(self, nnet_output, pdf_class=None):
         """The numerator's occupation posteriors ``gamma_num_t(j)`` under ``nnet_output``, dense float32 ``(T*B, C)`` (row
         ``t*B + b``) on the input's device: what Kaldi's chain-sMBR scores the denominator's paths against
