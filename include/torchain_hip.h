@@ -1137,6 +1137,39 @@ int tc_supervision_path_entropy(tc_supervision *supervision, const void *nnet_ou
                                 const double *grad_output_dev /* nullable, [S] */, void *workspace, int64_t workspace_bytes,
                                 int device, void *stream);
 
+/* ---- the same for a regular supervision: a level-windowed kernel (num_entropy_regular_kernels.hip) -----------------------------
+ * tc_supervision_path_entropy_regular gives tc_supervision_path_entropy's three outputs for a REGULAR (time-unfolded)
+ * handle, uniform or ragged: the paths of sequence s are the start-to-final paths of its acceptor, each T_s arcs long,
+ * log W = sum_t (y_t(pdf_t) + logw_t) - final cost with the regular numerator's operand (y unclamped, y + logw one float32
+ * sum), logprob_s = log Z_s, entropy_s and its gradient as stated above.  Lattice-derived supervisions put many competing
+ * alignments into one acceptor: the entropy is the confidence of such an utterance, and the numerator half of a
+ * conditional-entropy criterion.
+ * The acceptor has one level per frame, so every state is visited once per direction: one workgroup of 256 threads a
+ * sequence keeps two adjacent levels of (log alpha, Abar) -- backward (log beta, Bbar) -- in LDS and walks the tables of the
+ * level-windowed numerator.  log alpha, log beta and log Z are formed by the numerator's own device functions on its
+ * operands in its order: logprob has the numerator's bits.  Means are doubles, a share or an occupation the float32 exp of a
+ * double difference; each unique (frame, pdf) entry sums its arcs' float32 terms in table order and is stored once.
+ *   arguments  : tc_supervision_path_entropy's, one for one, and the same checks in front of the first device call.
+ *   workspace  : tc_supervision_path_entropy_regular_workspace_bytes(supervision, grad != null) bytes, 16-byte aligned: the
+ *                history (log alpha, Abar), 16 bytes a STATE of the handle -- a state lives in one level.  0 bytes for the
+ *                value alone.  The supervision's pool slot holds the tables only and is not written.
+ * Failed sequences (no path: (NaN, -inf); a NaN or +-inf among the y the sequence reads: (NaN, NaN)), the +0 of padding
+ * frames, of pdfs without an arc in a frame and of failed sequences, and the independence of a sequence's bits from its
+ * batch -- alone, in a uniform merged handle, in a ragged one -- are tc_supervision_path_entropy's.
+ * Size rule, with L, U, A the handle's widest level in states, in unique entries of a frame and in arcs leaving it
+ * (tc_supervision_stats: max_level_states, max_frame_uniq, max_level_arcs):
+ *     48 * ceil2(L) + 4 * ceil4(U) + 4 * ceil4(A) + 2048 <= 163840,
+ * the same for a value-only call.  TC_ERR_UNSUPPORTED, before any launch (the workspace query returns it too): a handle
+ * beyond the rule; an end-to-end handle (tc_supervision_path_entropy is theirs).  TC_ERR_INVALID_ARGUMENT and TC_ERR_WORKSPACE
+ * as tc_supervision_path_entropy.  Asynchronous on `stream`, no allocation once the supervision is staged, no host
+ * synchronisation.  tc_debug_counter("num_entropy_regular_launches") counts the launches. */
+int64_t tc_supervision_path_entropy_regular_workspace_bytes(const tc_supervision *supervision, int32_t with_grad);
+int tc_supervision_path_entropy_regular(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
+                                        int64_t num_rows, int32_t num_cols, int64_t row_stride, double *entropy_dev /* [S] */,
+                                        double *logprob_dev /* [S] */, void *grad /* nullable */, int64_t grad_stride,
+                                        const double *grad_output_dev /* nullable, [S] */, void *workspace,
+                                        int64_t workspace_bytes, int device, void *stream);
+
 /* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
  * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token
  * sequences and scores each against its sequence's reference by the unit-cost Levenshtein distance: the risk of a
@@ -1431,7 +1464,8 @@ int tc_debug_set(const char *key, int value);
  * fix-up); 0 for every other entry;
  * "den_entropy_launches" = tc_den_path_entropy calls that launched their kernel (not counted in "den_launches"), and
  * "den_entropy_streamed_launches" those of them that kept the per-frame vectors in the workspace;
- * "num_entropy_launches" = tc_supervision_path_entropy calls that launched their kernel (not counted in "num_launches").
+ * "num_entropy_launches" = tc_supervision_path_entropy calls that launched their kernel (not counted in "num_launches"), and
+ * "num_entropy_regular_launches" = those of tc_supervision_path_entropy_regular.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

@@ -213,6 +213,10 @@ def _load():
     L.tc_supervision_path_entropy_workspace_bytes.argtypes = [vp, i32]
     L.tc_supervision_path_entropy.restype = C.c_int
     L.tc_supervision_path_entropy.argtypes = [vp, vp, C.c_int, C.c_int, i64, i32, i64, vp, vp, vp, i64, vp, vp, i64, C.c_int, vp]
+    L.tc_supervision_path_entropy_regular_workspace_bytes.restype = i64
+    L.tc_supervision_path_entropy_regular_workspace_bytes.argtypes = [vp, i32]
+    L.tc_supervision_path_entropy_regular.restype = C.c_int
+    L.tc_supervision_path_entropy_regular.argtypes = L.tc_supervision_path_entropy.argtypes
     L.tc_den_best_path_workspace_bytes.restype = i64
     L.tc_den_best_path_workspace_bytes.argtypes = [vp, i32, i32]
     L.tc_den_best_path.restype = C.c_int

@@ -508,6 +508,23 @@ int tc_supervision_best_path(tc_supervision *sup, const void *y, int dtype, int 
   return supervision_mark_use(sup, device, stream);
 }
 
+// the argument checks of tc_supervision_path_entropy and tc_supervision_path_entropy_regular: host arithmetic only
+static int path_entropy_args(const tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows, int32_t cols,
+                             int64_t y_stride, const double *entropy_dev, const double *logprob_dev, const void *grad,
+                             int64_t grad_stride, const double *grad_output_dev) {
+  if (!sup || !y || !entropy_dev || !logprob_dev) return TC_ERR_INVALID_ARGUMENT;
+  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && dtype != TC_DTYPE_F32) return TC_ERR_INVALID_ARGUMENT;  // (2-D tensors are float32, as NumParams::y)
+  if ((int64_t)sup->S * sup->T != rows || sup->P != cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && (y_stride < cols || (grad && grad_stride < cols))) return TC_ERR_INVALID_ARGUMENT;
+  if (!grad && grad_output_dev) return TC_ERR_INVALID_ARGUMENT;
+  const uintptr_t elem_mask = dtype == TC_DTYPE_F32 ? 3 : 1;
+  if ((((uintptr_t)y | (uintptr_t)grad) & elem_mask) != 0 ||
+      (((uintptr_t)entropy_dev | (uintptr_t)logprob_dev | (uintptr_t)grad_output_dev) & 7) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  return TC_OK;
+}
+
 // tc_supervision_path_entropy's size rule (num_entropy_kernels.hip): end-to-end handles whose every sequence keeps its four
 // per-state vectors and its frame's y in LDS
 static int num_entropy_rule(const tc_supervision *sup, bool *terms_in_lds) {
@@ -532,18 +549,11 @@ int tc_supervision_path_entropy(tc_supervision *sup, const void *y, int dtype, i
                                 const double *grad_output_dev, void *workspace, int64_t workspace_bytes, int device,
                                 void *stream_v) {
   // (every argument check in front of the first device call)
-  if (!sup || !y || !entropy_dev || !logprob_dev) return TC_ERR_INVALID_ARGUMENT;
-  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
-  if (!layout_bct && dtype != TC_DTYPE_F32) return TC_ERR_INVALID_ARGUMENT;  // (2-D tensors are float32, as NumParams::y)
-  if ((int64_t)sup->S * sup->T != rows || sup->P != cols) return TC_ERR_INVALID_ARGUMENT;
-  if (!layout_bct && (y_stride < cols || (grad && grad_stride < cols))) return TC_ERR_INVALID_ARGUMENT;
-  if (!grad && grad_output_dev) return TC_ERR_INVALID_ARGUMENT;
-  const uintptr_t elem_mask = dtype == TC_DTYPE_F32 ? 3 : 1;
-  if ((((uintptr_t)y | (uintptr_t)grad) & elem_mask) != 0 ||
-      (((uintptr_t)entropy_dev | (uintptr_t)logprob_dev | (uintptr_t)grad_output_dev) & 7) != 0)
-    return TC_ERR_INVALID_ARGUMENT;
+  int rc = path_entropy_args(sup, y, dtype, layout_bct, rows, cols, y_stride, entropy_dev, logprob_dev, grad, grad_stride,
+                             grad_output_dev);
+  if (rc != TC_OK) return rc;
   bool terms_in_lds = false;
-  int rc = num_entropy_rule(sup, &terms_in_lds);
+  rc = num_entropy_rule(sup, &terms_in_lds);
   if (rc != TC_OK) return rc;
   const E2eTables &e = sup->e2e_tab;
   const int64_t need = num_ent_workspace_bytes(e.total_states, e.arc_off[sup->S], sup->T, terms_in_lds, grad != nullptr);
@@ -567,6 +577,56 @@ int tc_supervision_path_entropy(tc_supervision *sup, const void *y, int dtype, i
   p.terms = grad && !terms_in_lds ? (float *)((char *)workspace + num_ent_hist_bytes(e.total_states, sup->T)) : nullptr;
   p.terms_in_lds = terms_in_lds ? 1 : 0;
   rc = launch_num_entropy(p, stream);
+  if (rc != TC_OK) return rc;
+  return supervision_mark_use(sup, device, stream);
+}
+
+// tc_supervision_path_entropy_regular's size rule (num_entropy_regular_kernels.hip): regular handles whose widest level
+// keeps three pairs of doubles a state, the frame's y and the terms of the arcs leaving it in LDS
+static int num_entropy_regular_rule(const tc_supervision *sup) {
+  if (sup->e2e) return TC_ERR_UNSUPPORTED;
+  const NumTables &tb = sup->tab;
+  return num_ent_regular_fits(tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq) ? TC_OK : TC_ERR_UNSUPPORTED;
+}
+
+int64_t tc_supervision_path_entropy_regular_workspace_bytes(const tc_supervision *sup, int32_t with_grad) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  const int rc = num_entropy_regular_rule(sup);
+  if (rc != TC_OK) return rc;
+  return num_ent_regular_workspace_bytes(sup->tab.seq_state_off[sup->S], with_grad != 0);
+}
+
+int tc_supervision_path_entropy_regular(tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows,
+                                        int32_t cols, int64_t y_stride, double *entropy_dev, double *logprob_dev, void *grad,
+                                        int64_t grad_stride, const double *grad_output_dev, void *workspace,
+                                        int64_t workspace_bytes, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  int rc = path_entropy_args(sup, y, dtype, layout_bct, rows, cols, y_stride, entropy_dev, logprob_dev, grad, grad_stride,
+                             grad_output_dev);
+  if (rc != TC_OK) return rc;
+  rc = num_entropy_regular_rule(sup);
+  if (rc != TC_OK) return rc;
+  const int64_t need = num_ent_regular_workspace_bytes(sup->tab.seq_state_off[sup->S], grad != nullptr);
+  if (need > 0 && (!workspace || need > workspace_bytes || !aligned16(workspace))) return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  hipStream_t stream = (hipStream_t)stream_v;
+  NumEntParams p;
+  // (a (B, C, T) tensor has no row stride: fill_num_params is given the dense one)
+  rc = fill_num_params(sup, device, stream, (const float *)y, rows, cols, layout_bct ? (int64_t)cols : y_stride, nullptr, 0,
+                       nullptr, 0, nullptr, &p.n);
+  if (rc != TC_OK) return rc;
+  p.n.y_bct = layout_bct ? 1 : 0;
+  p.n.elem = dtype;
+  p.entropy = entropy_dev;
+  p.logprob = logprob_dev;
+  p.grad = grad;
+  p.grad_stride = grad_stride;
+  p.grad_output = grad_output_dev;
+  p.hist = grad ? (double *)workspace : nullptr;
+  p.terms = nullptr;
+  p.terms_in_lds = 1;
+  rc = launch_num_entropy_regular(p, stream);
   if (rc != TC_OK) return rc;
   return supervision_mark_use(sup, device, stream);
 }

@@ -899,6 +899,22 @@ inline int64_t num_ent_workspace_bytes(int64_t total_states, int64_t total_arcs,
   return num_ent_hist_bytes(total_states, T) + (terms_in_lds ? 0 : ((total_arcs * 4 + 255) & ~(int64_t)255));
 }
 int launch_num_entropy(const NumEntParams &p, hipStream_t stream);  // num_entropy_kernels.hip
+// The same quantity for a REGULAR supervision (tc_supervision_path_entropy_regular, num_entropy_regular_kernels.hip), which
+// takes NumEntParams too: `hist` is one pair (log alpha, Abar) per state of the handle, at seq_state_off[s] pairs, `terms` is
+// not read.  LDS, sized by the batch's widest level (L states, A arcs leaving it, U unique entries of a frame): two ping-pong
+// levels of two doubles, with a gradient the level's history pair and one float per arc leaving it, and the frame's y.  The
+// size rule is the gradient's whatever the call asks for: 48 * ceil2(L) + 4 * ceil4(U) + 4 * ceil4(A) + 2048 <= 163840.
+inline size_t num_ent_regular_lds_bytes(int32_t level_states, int32_t level_arcs, int32_t frame_uniq, bool grad) {
+  return (size_t)((level_states + 1) & ~1) * (grad ? 48 : 32) + (size_t)((frame_uniq + 3) & ~3) * 4 +
+         (grad ? (size_t)((level_arcs + 3) & ~3) * 4 : 0);
+}
+inline bool num_ent_regular_fits(int32_t level_states, int32_t level_arcs, int32_t frame_uniq) {
+  return num_ent_regular_lds_bytes(level_states, level_arcs, frame_uniq, true) + kNumEntStaticLds <= (size_t)kLdsLimitBytes;
+}
+inline int64_t num_ent_regular_workspace_bytes(int64_t total_states, bool grad) {
+  return grad ? ((int64_t)16 * total_states + 255) & ~(int64_t)255 : 0;
+}
+int launch_num_entropy_regular(const NumEntParams &p, hipStream_t stream);  // num_entropy_regular_kernels.hip
 
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
@@ -1042,7 +1058,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

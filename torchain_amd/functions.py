@@ -1099,7 +1099,7 @@ def den_path_entropy(input, den_graph, frames=None, leaky_hmm_coefficient=1e-5, 
 
 
 class _NumPathEntropy(torch.autograd.Function):
-    """``num_path_entropy``: forward is ``tc_supervision_path_entropy``'s forward pass alone.  Backward is the whole kernel
+    """``num_path_entropy``: forward is the forward pass alone of ``tc_supervision_path_entropy`` (``_regular`` for a regular handle).  Backward is the whole kernel
     with ``grad_output`` handed to it: the forward pass is run again instead of keeping its history, so no ``(B, C, T)``
     buffer lives between the two, and every gradient element is formed, scaled and stored once."""
 
@@ -1117,12 +1117,13 @@ class _NumPathEntropy(torch.autograd.Function):
 
 
 def num_path_entropy(input, supervision):
-    """The entropy of an end-to-end ``supervision``'s alignment posterior under ``input`` and the numerator's log-likelihood:
+    """The entropy of a ``supervision``'s alignment posterior under ``input`` and the numerator's log-likelihood:
     ``(entropy, logprob)``, float64 ``(B,)`` each, ``entropy`` differentiable in ``input`` (``io.Supervision.path_entropy``
-    states the quantity; ``tc_supervision_path_entropy``).  Add ``-eps * entropy.sum()`` to a flat-start ``chain_loss``
-    against an early collapse onto one alignment (maximum-entropy regularisation, Liu et al. 2018); read ``entropy`` per
-    utterance as the ambiguity of its alignment; with ``den_path_entropy`` it gives both halves of a conditional-entropy
-    criterion.  ``input`` is what ``chain_loss`` takes: 2-D float32 ``(T*B, C)`` and contiguous ``(B, C, T)`` in float32,
+    states the quantity and which kernel serves which handle: regular and end-to-end ones, uniform and ragged).  Add ``-eps *
+    entropy.sum()`` to a ``chain_loss`` against an early collapse onto one alignment -- flat-start training, or supervisions
+    with a tolerance around phone boundaries (maximum-entropy regularisation, Liu et al. 2018); read ``entropy`` per
+    utterance as the ambiguity of its alignment, the confidence by which lattice-derived supervisions of semi-supervised
+    training are weighted; with ``den_path_entropy`` it gives both halves of a conditional-entropy criterion.  ``input`` is what ``chain_loss`` takes: 2-D float32 ``(T*B, C)`` and contiguous ``(B, C, T)`` in float32,
     bfloat16 or float16 are read where they lie.
 
     Under ``no_grad``, or when ``input`` requires no gradient, only the forward pass runs.  Otherwise backward is one more

@@ -1101,10 +1101,13 @@ class Supervision:
         return pdfs, scores
 
     def path_entropy(self, nnet_output):
-        """How ambiguous every sequence's alignment is under ``nnet_output`` (``tc_supervision_path_entropy``): ``(entropy,
-        logprob)``, float64 ``(B,)`` each on the input's device.  END-TO-END handles only (``from_e2e_fsts``, the
-        ``<End2End>`` egs), uniform and ragged; a regular handle raises ``TorchainHipError`` (unsupported), as does an
-        end-to-end sequence of more than about 5000 states.
+        """How ambiguous every sequence's alignment is under ``nnet_output``: ``(entropy, logprob)``, float64 ``(B,)`` each
+        on the input's device.  Every handle, uniform and ragged: end-to-end ones (``from_e2e_fsts``, the ``<End2End>`` egs)
+        through ``tc_supervision_path_entropy``, which walks the FST's whole state set every frame; regular, time-unfolded
+        ones (``from_fst``, ``from_fsts``, ``from_sequences``, ``from_alignments``, the egs readers) through
+        ``tc_supervision_path_entropy_regular``, which walks level by level and visits every state once per direction.
+        ``TorchainHipError`` (unsupported): an end-to-end sequence of more than about 5000 states; a regular handle whose
+        widest level breaks ``48 * max_level_states + 4 * max_frame_uniq + 4 * max_level_arcs + 2048 <= 163840`` (``stats()``).
 
         The paths of sequence ``b`` are the arc sequences of exactly ``T_b`` arcs from its FST's start state to a final state,
         ``log W = sum_t (y_t(pdf_t) - cost_t) - final cost``, ``logprob[b] = log Z_b = log sum W`` (the numerator's, without the
@@ -1118,7 +1121,8 @@ class Supervision:
         return self._path_entropy("path_entropy", nnet_output)[:2]
 
     def _path_entropy(self, who, nnet_output, grad_output=None, workspace=None):
-        """The checks and one ``tc_supervision_path_entropy`` launch: ``(entropy, logprob, grad)``.  With ``grad_output``
+        """The checks and one launch of the handle's kind's entry (``tc_supervision_path_entropy`` for an end-to-end handle,
+        ``tc_supervision_path_entropy_regular`` for a regular one): ``(entropy, logprob, grad)``.  With ``grad_output``
         (float64 ``(B,)``) the launch also writes ``grad_output[b] * d entropy[b] / d y`` in the prepared input's layout and
         dtype, its history in ``workspace(device, stream, nbytes)``; without it ``grad`` is ``None`` and no workspace is needed."""
         x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
@@ -1135,8 +1139,10 @@ class Supervision:
             x = x.contiguous()
         device = x.device
         want_grad = grad_output is not None
-        need = int(lib.tc_supervision_path_entropy_workspace_bytes(self.ptr, int(want_grad)))  # (host arithmetic only)
-        check(min(need, 0), "tc_supervision_path_entropy_workspace_bytes")
+        name = "tc_supervision_path_entropy" if self.is_e2e else "tc_supervision_path_entropy_regular"
+        entry = getattr(lib, name)
+        need = int(getattr(lib, name + "_workspace_bytes")(self.ptr, int(want_grad)))  # (host arithmetic only)
+        check(min(need, 0), name + "_workspace_bytes")
         entropy = torch.empty((S,), dtype=torch.float64, device=device)
         logprob = torch.empty((S,), dtype=torch.float64, device=device)
         grad = scale = ws = None
@@ -1148,12 +1154,11 @@ class Supervision:
                 if tuple(scale.shape) != (S,):
                     raise ValueError("%s: grad_output of shape %s is not (%d,)" % (who, tuple(scale.shape), S))
                 ws = workspace(device, cur, max(need, 256))
-            check(lib.tc_supervision_path_entropy(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
-                                                  x.stride(0) if x.dim() == 2 else 0, C.c_void_p(entropy.data_ptr()),
-                                                  C.c_void_p(logprob.data_ptr()), C.c_void_p(grad.data_ptr()) if want_grad else None,
-                                                  P, C.c_void_p(scale.data_ptr()) if want_grad else None,
-                                                  C.c_void_p(ws.data_ptr()) if want_grad else None, ws.numel() if want_grad else 0,
-                                                  device.index, C.c_void_p(cur)), "tc_supervision_path_entropy")
+            check(entry(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
+                        x.stride(0) if x.dim() == 2 else 0, C.c_void_p(entropy.data_ptr()), C.c_void_p(logprob.data_ptr()),
+                        C.c_void_p(grad.data_ptr()) if want_grad else None, P, C.c_void_p(scale.data_ptr()) if want_grad else None,
+                        C.c_void_p(ws.data_ptr()) if want_grad else None, ws.numel() if want_grad else 0, device.index,
+                        C.c_void_p(cur)), name)
         return entropy, logprob, grad
 
     def posteriors(self, nnet_output, pdf_class=None):
