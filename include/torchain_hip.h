@@ -1112,7 +1112,9 @@ int tc_den_path_entropy(tc_den_graph *g, int32_t S, const float *nnet_output, in
  *                 forward pass that writes no history (grad_output_dev null too).
  *   workspace   : tc_supervision_path_entropy_workspace_bytes(supervision, grad != null) bytes, 16-byte aligned: the history
  *                 (log alpha_t, Abar_t), 16 bytes a (frame, state), and the per-arc terms when they do not fit LDS.  0 bytes
- *                 for the value alone (workspace may then be null).  The supervision's pool slot holds the tables only: its
+ *                 for the value alone (workspace may then be null) on the resident kernel; the large kernel (below) adds
+ *                 16 bytes a state to either figure and always keeps the terms there, so ask before a value call too.
+ *                 The supervision's pool slot holds the tables only: its
  *                 scratch is not touched, and a training step on the handle gives the same bits before and after this call.
  * A sequence with no path of T_s arcs gets logprob -inf, entropy NaN and a +0 gradient.  A sequence with a NaN or +-inf at
  * one of its own (frame, pdf) pairs -- its valid frames, the pdfs of its arcs: nothing else is read -- gets NaN in both and a
@@ -1122,15 +1124,23 @@ int tc_den_path_entropy(tc_den_graph *g, int32_t S, const float *nnet_output, in
  * out per sequence: 32 * ceil4(states) + 4 * ceil4(distinct pdfs) bytes, plus 4 * ceil4(arcs) when the handle's largest
  * counts leave room (otherwise the per-arc terms live in the workspace), plus 2048.  Every handle of
  * tc_supervision_create_e2e and _e2e_ragged fits (at most 102400 + 2048 bytes).  A handle of _e2e_any is served when every
- * sequence meets 32 * ceil4(states) + 4 * ceil4(distinct pdfs) + 2048 <= 163840 (about 5000 states with few pdfs).
- * TC_ERR_UNSUPPORTED, before any launch (the workspace query returns it too): a regular (time-unfolded) supervision; an
- * end-to-end sequence beyond that bound.  TC_ERR_INVALID_ARGUMENT, before any device call: a null supervision, nnet_output,
+ * sequence meets 32 * ceil4(states) + 4 * ceil4(distinct pdfs) + 2048 <= 163840 (about 5000 states with few pdfs) by that
+ * kernel.  A handle with a sequence beyond it takes num_entropy_large_kernels.hip for the whole batch: log alpha (log beta)
+ * of two levels and the frame's y in LDS, 16 * ceil4(states) + 4 * ceil4(distinct pdfs) + 2048 <= 163840 -- the rule of
+ * tc_supervision_create_e2e_any itself, so every handle that can be built is served -- and the means in the workspace: Abar
+ * in the history's rows (two ping-pong rows for the value alone), Bbar in two ping-pong rows.  Same arithmetic in the same
+ * orders: on a handle that fits both, the resident kernel's bits ("force_num_entropy_large").
+ * tc_supervision_path_entropy_kernel says which one a handle takes: 0 resident, 1 large (as the switch stands at the call).
+ * TC_ERR_UNSUPPORTED, before any launch (the workspace query and the kernel query return it too): a regular (time-unfolded)
+ * supervision.  TC_ERR_INVALID_ARGUMENT, before any device call: a null supervision, nnet_output,
  * entropy_dev or logprob_dev; num_rows or num_cols that are not the handle's; an unknown dtype; a 2-D call with a 16-bit
  * dtype, row_stride < num_cols or grad with grad_stride < num_cols; grad_output_dev without grad; a misaligned pointer (the
  * element's size; 8 for doubles).  TC_ERR_WORKSPACE: a short, misaligned or (when bytes are needed) null workspace.
  * Asynchronous on `stream`, no allocation once the supervision is staged, no host synchronisation.
- * tc_debug_counter("num_entropy_launches") counts the launches ("num_launches" does not move). */
+ * tc_debug_counter("num_entropy_launches") counts the resident kernel's launches, "num_entropy_large_launches" the large
+ * kernel's ("num_launches" does not move). */
 int64_t tc_supervision_path_entropy_workspace_bytes(const tc_supervision *supervision, int32_t with_grad);
+int tc_supervision_path_entropy_kernel(const tc_supervision *supervision);
 int tc_supervision_path_entropy(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
                                 int64_t num_rows, int32_t num_cols, int64_t row_stride, double *entropy_dev /* [S] */,
                                 double *logprob_dev /* [S] */, void *grad /* nullable */, int64_t grad_stride,
@@ -1420,6 +1430,9 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *                     every graph, as it does for those beyond the LDS form; same bits.  Read at every such call)
  *   "force_den_entropy_streamed" (1: tc_den_path_entropy keeps its per-frame vectors in the workspace for every graph, as it
  *                     does for those beyond the LDS form; same bits.  Read at every such call)
+ *   "force_num_entropy_large" (1: end-to-end supervisions that fit the resident entropy kernel take
+ *                     num_entropy_large_kernels.hip, which otherwise serves those that do not fit; same bits.  Read at every
+ *                     tc_supervision_path_entropy call and by its workspace and kernel queries)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -1464,7 +1477,8 @@ int tc_debug_set(const char *key, int value);
  * fix-up); 0 for every other entry;
  * "den_entropy_launches" = tc_den_path_entropy calls that launched their kernel (not counted in "den_launches"), and
  * "den_entropy_streamed_launches" those of them that kept the per-frame vectors in the workspace;
- * "num_entropy_launches" = tc_supervision_path_entropy calls that launched their kernel (not counted in "num_launches"), and
+ * "num_entropy_launches" = tc_supervision_path_entropy calls that launched the resident kernel (not counted in
+ * "num_launches"), "num_entropy_large_launches" = those that launched num_entropy_large_kernels.hip (counted in neither), and
  * "num_entropy_regular_launches" = those of tc_supervision_path_entropy_regular.
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);

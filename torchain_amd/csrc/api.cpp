@@ -525,23 +525,43 @@ static int path_entropy_args(const tc_supervision *sup, const void *y, int dtype
   return TC_OK;
 }
 
-// tc_supervision_path_entropy's size rule (num_entropy_kernels.hip): end-to-end handles whose every sequence keeps its four
-// per-state vectors and its frame's y in LDS
-static int num_entropy_rule(const tc_supervision *sup, bool *terms_in_lds) {
+// tc_supervision_path_entropy's size rule, per handle.  Every sequence keeps its four per-state vectors and its frame's y in
+// LDS: the resident kernel (num_entropy_kernels.hip), *large = false.  Otherwise, or with "force_num_entropy_large", every
+// sequence meets the any-size numerator's rule: num_entropy_large_kernels.hip for the whole batch, *large = true.
+static int num_entropy_rule(const tc_supervision *sup, bool *large, bool *terms_in_lds) {
   if (!sup->e2e) return TC_ERR_UNSUPPORTED;
   const E2eTables &e = sup->e2e_tab;
-  for (int s = 0; s < sup->S; ++s)
-    if (!num_ent_fits(e.state_off[s + 1] - e.state_off[s], e.pdf_off[s + 1] - e.pdf_off[s])) return TC_ERR_UNSUPPORTED;
-  *terms_in_lds = num_ent_terms_in_lds(e.max_states, e.max_arcs, e.max_pdfs);
+  bool resident = !debug_flag(kDbgForceNumEntropyLarge), fits_large = true;
+  for (int s = 0; s < sup->S; ++s) {
+    const int states = e.state_off[s + 1] - e.state_off[s], pdfs = e.pdf_off[s + 1] - e.pdf_off[s];
+    resident = resident && num_ent_fits(states, pdfs);
+    fits_large = fits_large && num_ent_large_fits(states, pdfs);
+  }
+  if (!resident && !fits_large) return TC_ERR_UNSUPPORTED;
+  *large = !resident;
+  *terms_in_lds = resident && num_ent_terms_in_lds(e.max_states, e.max_arcs, e.max_pdfs);
   return TC_OK;
+}
+
+static int64_t num_entropy_need(const tc_supervision *sup, bool large, bool terms_in_lds, bool grad) {
+  const E2eTables &e = sup->e2e_tab;
+  return large ? num_ent_large_workspace_bytes(e.total_states, e.arc_off[sup->S], sup->T, grad)
+               : num_ent_workspace_bytes(e.total_states, e.arc_off[sup->S], sup->T, terms_in_lds, grad);
 }
 
 int64_t tc_supervision_path_entropy_workspace_bytes(const tc_supervision *sup, int32_t with_grad) {
   if (!sup) return TC_ERR_INVALID_ARGUMENT;
-  bool terms_in_lds = false;
-  const int rc = num_entropy_rule(sup, &terms_in_lds);
+  bool large = false, terms_in_lds = false;
+  const int rc = num_entropy_rule(sup, &large, &terms_in_lds);
   if (rc != TC_OK) return rc;
-  return num_ent_workspace_bytes(sup->e2e_tab.total_states, sup->e2e_tab.arc_off[sup->S], sup->T, terms_in_lds, with_grad != 0);
+  return num_entropy_need(sup, large, terms_in_lds, with_grad != 0);
+}
+
+int tc_supervision_path_entropy_kernel(const tc_supervision *sup) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  bool large = false, terms_in_lds = false;
+  const int rc = num_entropy_rule(sup, &large, &terms_in_lds);
+  return rc != TC_OK ? rc : large ? 1 : 0;
 }
 
 int tc_supervision_path_entropy(tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows, int32_t cols,
@@ -552,11 +572,11 @@ int tc_supervision_path_entropy(tc_supervision *sup, const void *y, int dtype, i
   int rc = path_entropy_args(sup, y, dtype, layout_bct, rows, cols, y_stride, entropy_dev, logprob_dev, grad, grad_stride,
                              grad_output_dev);
   if (rc != TC_OK) return rc;
-  bool terms_in_lds = false;
-  rc = num_entropy_rule(sup, &terms_in_lds);
+  bool large = false, terms_in_lds = false;
+  rc = num_entropy_rule(sup, &large, &terms_in_lds);
   if (rc != TC_OK) return rc;
   const E2eTables &e = sup->e2e_tab;
-  const int64_t need = num_ent_workspace_bytes(e.total_states, e.arc_off[sup->S], sup->T, terms_in_lds, grad != nullptr);
+  const int64_t need = num_entropy_need(sup, large, terms_in_lds, grad != nullptr);
   if (need > 0 && (!workspace || need > workspace_bytes || !aligned16(workspace))) return TC_ERR_WORKSPACE;
   DeviceGuard guard(device);
   if (!guard.ok) return TC_ERR_HIP;
@@ -576,7 +596,13 @@ int tc_supervision_path_entropy(tc_supervision *sup, const void *y, int dtype, i
   p.hist = grad ? (double *)workspace : nullptr;
   p.terms = grad && !terms_in_lds ? (float *)((char *)workspace + num_ent_hist_bytes(e.total_states, sup->T)) : nullptr;
   p.terms_in_lds = terms_in_lds ? 1 : 0;
-  rc = launch_num_entropy(p, stream);
+  p.means = nullptr;
+  if (large) {  // [history] [mean rows] [terms]
+    char *at = (char *)workspace + (grad ? num_ent_hist_bytes(e.total_states, sup->T) : 0);
+    p.means = (double *)at;
+    p.terms = grad ? (float *)(at + num_ent_means_bytes(e.total_states)) : nullptr;
+  }
+  rc = large ? launch_num_entropy_large(p, stream) : launch_num_entropy(p, stream);
   if (rc != TC_OK) return rc;
   return supervision_mark_use(sup, device, stream);
 }
@@ -626,6 +652,7 @@ int tc_supervision_path_entropy_regular(tc_supervision *sup, const void *y, int 
   p.hist = grad ? (double *)workspace : nullptr;
   p.terms = nullptr;
   p.terms_in_lds = 1;
+  p.means = nullptr;
   rc = launch_num_entropy_regular(p, stream);
   if (rc != TC_OK) return rc;
   return supervision_mark_use(sup, device, stream);

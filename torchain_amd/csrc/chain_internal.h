@@ -880,6 +880,9 @@ struct NumEntParams {
   double *hist;
   float *terms;
   int terms_in_lds;
+  // num_entropy_large_kernel alone (null for the others): two rows of means per sequence, doubles, at 2 * state_off[s] doubles
+  // and state count apart (num_ent_large_workspace_bytes)
+  double *means;
 };
 // LDS of num_entropy_kernel, laid out per sequence: (log alpha, Abar) or (log beta, Bbar) of two adjacent levels -- four
 // double vectors of ceil4(states) -- the frame's y per distinct pdf and, when they fit beside those, one float per arc.
@@ -899,6 +902,18 @@ inline int64_t num_ent_workspace_bytes(int64_t total_states, int64_t total_arcs,
   return num_ent_hist_bytes(total_states, T) + (terms_in_lds ? 0 : ((total_arcs * 4 + 255) & ~(int64_t)255));
 }
 int launch_num_entropy(const NumEntParams &p, hipStream_t stream);  // num_entropy_kernels.hip
+// num_entropy_large_kernels.hip: the same quantity for handles with a sequence beyond num_ent_fits.  Its LDS holds log alpha
+// (log beta) of two levels and the frame's y -- e2e_seq_lds_bytes, the any-size numerator's -- so its size rule is that
+// numerator's, e2e_large_fits per sequence: whatever tc_supervision_create_e2e_any builds.  Workspace: the history (with a
+// gradient), then two mean rows per sequence (always: the value alone keeps Abar there), then one float per arc (with a
+// gradient), each part rounded up to 256 bytes.
+inline bool num_ent_large_fits(int states, int pdfs) { return e2e_large_fits(states, pdfs); }
+inline int64_t num_ent_means_bytes(int64_t total_states) { return ((int64_t)16 * total_states + 255) & ~(int64_t)255; }
+inline int64_t num_ent_large_workspace_bytes(int64_t total_states, int64_t total_arcs, int T, bool grad) {
+  return num_ent_means_bytes(total_states) +
+         (grad ? num_ent_hist_bytes(total_states, T) + ((total_arcs * 4 + 255) & ~(int64_t)255) : 0);
+}
+int launch_num_entropy_large(const NumEntParams &p, hipStream_t stream);
 // The same quantity for a REGULAR supervision (tc_supervision_path_entropy_regular, num_entropy_regular_kernels.hip), which
 // takes NumEntParams too: `hist` is one pair (log alpha, Abar) per state of the handle, at seq_state_off[s] pairs, `terms` is
 // not read.  LDS, sized by the batch's widest level (L states, A arcs leaving it, U unique entries of a frame): two ping-pong
@@ -1049,7 +1064,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -1058,7 +1073,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

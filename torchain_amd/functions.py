@@ -1105,7 +1105,7 @@ class _NumPathEntropy(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, supervision):
-        entropy, logprob, _ = supervision._path_entropy("num_path_entropy", input)
+        entropy, logprob, _ = supervision._path_entropy("num_path_entropy", input, workspace=_workspace)  # (the large kernel's rows)
         ctx.input, ctx.supervision = input.detach(), supervision
         ctx.mark_non_differentiable(logprob)
         return entropy, logprob

@@ -1106,8 +1106,9 @@ class Supervision:
         through ``tc_supervision_path_entropy``, which walks the FST's whole state set every frame; regular, time-unfolded
         ones (``from_fst``, ``from_fsts``, ``from_sequences``, ``from_alignments``, the egs readers) through
         ``tc_supervision_path_entropy_regular``, which walks level by level and visits every state once per direction.
-        ``TorchainHipError`` (unsupported): an end-to-end sequence of more than about 5000 states; a regular handle whose
-        widest level breaks ``48 * max_level_states + 4 * max_frame_uniq + 4 * max_level_arcs + 2048 <= 163840`` (``stats()``).
+        An end-to-end handle with a sequence of more than about 5000 states takes the entry's large kernel, which keeps the
+        per-state means in a workspace (``path_entropy_kernel()``); every handle ``from_e2e_fsts`` builds is served.
+        ``TorchainHipError`` (unsupported): a regular handle whose widest level breaks ``48 * max_level_states + 4 * max_frame_uniq + 4 * max_level_arcs + 2048 <= 163840`` (``stats()``).
 
         The paths of sequence ``b`` are the arc sequences of exactly ``T_b`` arcs from its FST's start state to a final state,
         ``log W = sum_t (y_t(pdf_t) - cost_t) - final cost``, ``logprob[b] = log Z_b = log sum W`` (the numerator's, without the
@@ -1120,11 +1121,20 @@ class Supervision:
         affected."""
         return self._path_entropy("path_entropy", nnet_output)[:2]
 
+    def path_entropy_kernel(self):
+        """Which kernel ``path_entropy`` / ``functions.num_path_entropy`` run on this end-to-end handle
+        (``tc_supervision_path_entropy_kernel``, host arithmetic only): 0 the resident one, every sequence's four per-state
+        vectors in LDS; 1 the large one, for handles with a sequence beyond that.  ``TorchainHipError`` for a regular handle."""
+        kernel = int(lib.tc_supervision_path_entropy_kernel(self.ptr))
+        check(min(kernel, 0), "tc_supervision_path_entropy_kernel")
+        return kernel
+
     def _path_entropy(self, who, nnet_output, grad_output=None, workspace=None):
         """The checks and one launch of the handle's kind's entry (``tc_supervision_path_entropy`` for an end-to-end handle,
         ``tc_supervision_path_entropy_regular`` for a regular one): ``(entropy, logprob, grad)``.  With ``grad_output``
         (float64 ``(B,)``) the launch also writes ``grad_output[b] * d entropy[b] / d y`` in the prepared input's layout and
-        dtype, its history in ``workspace(device, stream, nbytes)``; without it ``grad`` is ``None`` and no workspace is needed."""
+        dtype, its history in ``workspace(device, stream, nbytes)``; without it ``grad`` is ``None``, and what the value
+        alone needs (the large end-to-end kernel's mean rows; 0 bytes otherwise) is allocated here."""
         x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise ValueError("%s: nnet_output must be a CUDA tensor (only the HIP implementation is available)" % who)
@@ -1154,10 +1164,12 @@ class Supervision:
                 if tuple(scale.shape) != (S,):
                     raise ValueError("%s: grad_output of shape %s is not (%d,)" % (who, tuple(scale.shape), S))
                 ws = workspace(device, cur, max(need, 256))
+            elif need > 0:
+                ws = workspace(device, cur, need) if workspace else torch.empty(need, dtype=torch.uint8, device=device)
             check(entry(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
                         x.stride(0) if x.dim() == 2 else 0, C.c_void_p(entropy.data_ptr()), C.c_void_p(logprob.data_ptr()),
                         C.c_void_p(grad.data_ptr()) if want_grad else None, P, C.c_void_p(scale.data_ptr()) if want_grad else None,
-                        C.c_void_p(ws.data_ptr()) if want_grad else None, ws.numel() if want_grad else 0, device.index,
+                        C.c_void_p(ws.data_ptr()) if ws is not None else None, ws.numel() if ws is not None else 0, device.index,
                         C.c_void_p(cur)), name)
         return entropy, logprob, grad
 
