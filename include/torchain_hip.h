@@ -1180,6 +1180,57 @@ int tc_supervision_path_entropy_regular(tc_supervision *supervision, const void 
                                         const double *grad_output_dev /* nullable, [S] */, void *workspace,
                                         int64_t workspace_bytes, int device, void *stream);
 
+/* ---- arc occupations of an end-to-end supervision (num_arc_post_kernels.hip) ---------------------------------------------------
+ * tc_supervision_arc_posteriors gives, per sequence s of an END-TO-END handle, the expected number of times each arc of the
+ * sequence's FST is taken under the numerator's posterior over the paths of exactly T_s arcs from the start state to a final
+ * state, and the probability that the path ends in each state.  With log W(path) = sum_t (y_t(pdf_t) - cost_t) - final cost (y
+ * unclamped, as in the numerator; the supervision's weight does not enter) and Z_s = sum W:
+ *     arcs[a]   = sum_t P(arc a at frame t | y_s) = sum_t exp(log alpha_t(src) + (y_t(pdf) - cost) + log beta_{t+1}(dst) - log Z_s)
+ *     finals[i] = P(the path ends in state i)     = exp(log alpha_T(i) - final(i) - log Z_s)
+ *     logprob[s] = log Z_s, the numerator's, bit for bit.
+ * So arcs = d log Z / d(-cost) and finals = d log Z / d(-final cost): the numerator's half of the LF-MMI gradient with
+ * respect to the graph's own weights (tc_den_arc_posteriors is the denominator's), and the E step of re-estimating
+ * transition, pronunciation and silence probabilities.  A sequence's arcs sum to T_s, its finals to 1, up to rounding.
+ *   arcs_dev    : device double[A], A = the handle's arcs: sequence after sequence, each in the CSR order of the FST handed to
+ *                 the create entry (tc_supervision_arc_posteriors_offsets gives the S + 1 offsets of the sequences).
+ *   finals_dev  : device double[N], N = the handle's states, laid out likewise.    logprob_dev : device double[S].
+ *   nnet_output, dtype, layout_bct, num_rows, num_cols, row_stride : as tc_supervision_best_path's.
+ *   workspace   : tc_supervision_arc_posteriors_workspace_bytes(supervision) bytes, 16-byte aligned: the history log alpha_t,
+ *                 8 bytes a (frame, state); the large form adds 12 bytes an arc.  The supervision's pool slot holds the
+ *                 tables only: its scratch is not touched, and a training step on the handle gives the same bits before
+ *                 and after this call.
+ * One launch, one workgroup of 256 threads a sequence.  The forward pass is the numerator's, operand for operand.  The
+ * backward pass is arc-stationary: out-arc k belongs to thread k % 256 for the whole sequence, which forms the arc's term
+ * (y_t(pdf) - cost) + log beta_{t+1}(dst) into an array by arc position and adds the float32 exp of
+ * (log alpha_t(src) - log Z) + term to the arc's double accumulator; a state's owner takes log beta_t as the log-sum over its
+ * contiguous slice of that array.  No atomics, every sum in a fixed order, accumulators are doubles stored as they are: a
+ * sequence's outputs do not depend on its batch.
+ * The RESIDENT form serves handles whose sequences are all within TC_E2E_MAX_STATES / _ARCS / _PDFS: arc records,
+ * accumulators, slice bounds and the next frame's log alpha and y in registers, log beta of two levels, log alpha_t, the
+ * terms and y in LDS -- 24 * ceil4(states) + 8 * ceil4(arcs) + 4 * ceil4(distinct pdfs) + 2048 bytes, 120832 at the limits.
+ * The LARGE form serves every other handle tc_supervision_create_e2e_any builds (16 * ceil4(states) + 4 * ceil4(distinct
+ * pdfs) + 2048 <= 163840 per sequence, any number of arcs): log beta and y alone in LDS, terms and sources in the workspace,
+ * accumulators in arcs_dev itself, log alpha_t(src) read from the history.  Same arithmetic in the same orders: on a handle
+ * that fits both, the resident form's bits ("force_num_arc_post_large").  tc_supervision_arc_posteriors_kernel says which one
+ * a handle takes: 0 resident, 1 large (as the switch stands at the call).
+ * A sequence with no path of T_s arcs gets logprob -inf, one with a NaN or +-inf at one of its own (frame, pdf) pairs -- its
+ * valid frames, the pdfs of its arcs: nothing else is read -- logprob NaN; both get +0 in all their arcs and finals, and the
+ * other sequences keep their bits.
+ * TC_ERR_UNSUPPORTED, before any launch (the three queries return it too): a regular (time-unfolded) supervision.
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null supervision, nnet_output or output; num_rows or num_cols that are
+ * not the handle's; an unknown dtype; a 2-D call with a 16-bit dtype or row_stride < num_cols; a misaligned pointer (the
+ * element's size; 8 for doubles).  TC_ERR_WORKSPACE: a short, misaligned or null workspace.  Asynchronous on `stream`, no
+ * allocation once the supervision is staged, no host synchronisation.  tc_debug_counter("num_arc_post_launches") counts the
+ * resident form's launches, "num_arc_post_large_launches" the large form's ("num_launches" does not move). */
+int64_t tc_supervision_arc_posteriors_workspace_bytes(const tc_supervision *supervision);
+int tc_supervision_arc_posteriors_kernel(const tc_supervision *supervision);
+int tc_supervision_arc_posteriors_offsets(const tc_supervision *supervision, int64_t *arc_offsets /* host, [S + 1] */,
+                                          int64_t *state_offsets /* host, [S + 1] */);
+int tc_supervision_arc_posteriors(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
+                                  int64_t num_rows, int32_t num_cols, int64_t row_stride, double *arcs_dev /* [A] */,
+                                  double *finals_dev /* [N] */, double *logprob_dev /* [S] */, void *workspace,
+                                  int64_t workspace_bytes, int device, void *stream);
+
 /* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
  * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token
  * sequences and scores each against its sequence's reference by the unit-cost Levenshtein distance: the risk of a
@@ -1433,6 +1484,9 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *   "force_num_entropy_large" (1: end-to-end supervisions that fit the resident entropy kernel take
  *                     num_entropy_large_kernels.hip, which otherwise serves those that do not fit; same bits.  Read at every
  *                     tc_supervision_path_entropy call and by its workspace and kernel queries)
+ *   "force_num_arc_post_large" (1: end-to-end supervisions within the resident limits take the large form of
+ *                     num_arc_post_kernels.hip, which otherwise serves those beyond them; same bits.  Read at every
+ *                     tc_supervision_arc_posteriors call and by its workspace and kernel queries)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -1479,7 +1533,9 @@ int tc_debug_set(const char *key, int value);
  * "den_entropy_streamed_launches" those of them that kept the per-frame vectors in the workspace;
  * "num_entropy_launches" = tc_supervision_path_entropy calls that launched the resident kernel (not counted in
  * "num_launches"), "num_entropy_large_launches" = those that launched num_entropy_large_kernels.hip (counted in neither), and
- * "num_entropy_regular_launches" = those of tc_supervision_path_entropy_regular.
+ * "num_entropy_regular_launches" = those of tc_supervision_path_entropy_regular;
+ * "num_arc_post_launches" = tc_supervision_arc_posteriors calls that launched the resident form of num_arc_post_kernels.hip,
+ * "num_arc_post_large_launches" = those that launched its large form (neither counted in "num_launches").
  * -1 for an unknown key. */
 int64_t tc_debug_counter(const char *key);
 

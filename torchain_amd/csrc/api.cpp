@@ -658,6 +658,83 @@ int tc_supervision_path_entropy_regular(tc_supervision *sup, const void *y, int 
   return supervision_mark_use(sup, device, stream);
 }
 
+// tc_supervision_arc_posteriors' size rule, per handle.  Every sequence within the resident numerator's limits: the resident
+// form of num_arc_post_kernels.hip, *large = false.  Otherwise, or with "force_num_arc_post_large", the large form for the
+// whole batch; every end-to-end handle that can be built meets its rule (e2e_large_fits: the create entries').
+static int num_arc_post_rule(const tc_supervision *sup, bool *large) {
+  if (!sup->e2e) return TC_ERR_UNSUPPORTED;
+  const E2eTables &e = sup->e2e_tab;
+  *large = e2e_beyond_resident(e.max_states, e.max_arcs, e.max_pdfs) || debug_flag(kDbgForceNumArcPostLarge);
+  for (int s = 0; *large && s < sup->S; ++s)
+    if (!e2e_large_fits(e.state_off[s + 1] - e.state_off[s], e.pdf_off[s + 1] - e.pdf_off[s])) return TC_ERR_UNSUPPORTED;
+  return TC_OK;
+}
+
+int64_t tc_supervision_arc_posteriors_workspace_bytes(const tc_supervision *sup) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  bool large = false;
+  const int rc = num_arc_post_rule(sup, &large);
+  if (rc != TC_OK) return rc;
+  return num_arc_workspace_bytes(sup->e2e_tab.total_states, sup->e2e_tab.arc_off[sup->S], sup->T, large);
+}
+
+int tc_supervision_arc_posteriors_kernel(const tc_supervision *sup) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  bool large = false;
+  const int rc = num_arc_post_rule(sup, &large);
+  return rc != TC_OK ? rc : large ? 1 : 0;
+}
+
+int tc_supervision_arc_posteriors_offsets(const tc_supervision *sup, int64_t *arc_offsets, int64_t *state_offsets) {
+  if (!sup || !arc_offsets || !state_offsets) return TC_ERR_INVALID_ARGUMENT;
+  if (!sup->e2e) return TC_ERR_UNSUPPORTED;
+  for (int s = 0; s <= sup->S; ++s) {
+    arc_offsets[s] = sup->e2e_tab.arc_off[s];
+    state_offsets[s] = sup->e2e_tab.state_off[s];
+  }
+  return TC_OK;
+}
+
+int tc_supervision_arc_posteriors(tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows, int32_t cols,
+                                  int64_t y_stride, double *arcs_dev, double *finals_dev, double *logprob_dev, void *workspace,
+                                  int64_t workspace_bytes, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!sup || !y || !arcs_dev || !finals_dev || !logprob_dev) return TC_ERR_INVALID_ARGUMENT;
+  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && dtype != TC_DTYPE_F32) return TC_ERR_INVALID_ARGUMENT;  // (2-D tensors are float32, as NumParams::y)
+  if ((int64_t)sup->S * sup->T != rows || sup->P != cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)y & (dtype == TC_DTYPE_F32 ? 3 : 1)) != 0 ||
+      (((uintptr_t)arcs_dev | (uintptr_t)finals_dev | (uintptr_t)logprob_dev) & 7) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  bool large = false;
+  int rc = num_arc_post_rule(sup, &large);
+  if (rc != TC_OK) return rc;
+  const E2eTables &e = sup->e2e_tab;
+  const int64_t need = num_arc_workspace_bytes(e.total_states, e.arc_off[sup->S], sup->T, large);
+  if (!workspace || need > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  hipStream_t stream = (hipStream_t)stream_v;
+  NumArcParams p;
+  // (a (B, C, T) tensor has no row stride: fill_num_params is given the dense one)
+  rc = fill_num_params(sup, device, stream, (const float *)y, rows, cols, layout_bct ? (int64_t)cols : y_stride, nullptr, 0,
+                       nullptr, 0, nullptr, &p.n);
+  if (rc != TC_OK) return rc;
+  p.n.y_bct = layout_bct ? 1 : 0;
+  p.n.elem = dtype;
+  p.arcs = arcs_dev;
+  p.finals = finals_dev;
+  p.logprob = logprob_dev;
+  p.hist = (double *)workspace;  // [history] [terms] [sources]
+  char *at = (char *)workspace + num_arc_hist_bytes(e.total_states, sup->T);
+  p.terms = large ? (double *)at : nullptr;
+  p.src = large ? (int32_t *)(at + num_arc_terms_bytes(e.arc_off[sup->S])) : nullptr;
+  rc = launch_num_arc_post(p, large, stream);
+  if (rc != TC_OK) return rc;
+  return supervision_mark_use(sup, device, stream);
+}
+
 int64_t tc_den_best_path_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {
   if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
   return den_best_workspace_bytes(g->H, S, T);

@@ -930,6 +930,37 @@ inline int64_t num_ent_regular_workspace_bytes(int64_t total_states, bool grad) 
   return grad ? ((int64_t)16 * total_states + 255) & ~(int64_t)255 : 0;
 }
 int launch_num_entropy_regular(const NumEntParams &p, hipStream_t stream);  // num_entropy_regular_kernels.hip
+// The arc occupations of an end-to-end supervision (tc_supervision_arc_posteriors, num_arc_post_kernels.hip).  `n` carries what
+// the numerator's launches carry; the pool slot's scratch is neither read nor written.  Workspace (num_arc_workspace_bytes): the
+// history log alpha_t, t = 0 .. T - 1, one double a (frame, state) at T * state_off[s] doubles; for the large form behind it
+// one double (the frame's term) and then one int32 (the source state) per arc, at arc_off[s]; each part rounded up to 256 bytes.
+struct NumArcParams {
+  NumParams n;
+  double *arcs;     // [arc_off[S]]: the handle's out-arc order
+  double *finals;   // [total_states]
+  double *logprob;  // [S]
+  double *hist;
+  double *terms;    // the large form alone (null for the resident one)
+  int32_t *src;
+};
+// LDS of the resident form, laid out per sequence: log beta of two levels and log alpha of one as doubles, a double per arc
+// and the frame's y per distinct pdf; kNumArcStaticLds covers the block reductions' slots.  118784 + 2048 bytes at
+// TC_E2E_MAX_STATES / _ARCS / _PDFS, which is the form's size rule (e2e_beyond_resident).  The large form's LDS is the
+// any-size numerator's, e2e_seq_lds_bytes, and its rule e2e_large_fits per sequence.
+constexpr int kNumArcStaticLds = 2048;
+inline size_t num_arc_lds_bytes(int states, int arcs, int pdfs) {
+  return (size_t)24 * ((states + 3) & ~3) + (size_t)8 * ((arcs + 3) & ~3) + (size_t)4 * ((pdfs + 3) & ~3);
+}
+static_assert((size_t)24 * TC_E2E_MAX_STATES + (size_t)8 * TC_E2E_MAX_ARCS + (size_t)4 * TC_E2E_MAX_PDFS + kNumArcStaticLds <=
+                  (size_t)kLdsLimitBytes,
+              "the resident arc-posterior kernel holds a sequence at the resident limits");
+inline int64_t num_arc_hist_bytes(int64_t total_states, int T) { return ((int64_t)8 * T * total_states + 255) & ~(int64_t)255; }
+inline int64_t num_arc_terms_bytes(int64_t total_arcs) { return (total_arcs * 8 + 255) & ~(int64_t)255; }
+inline int64_t num_arc_workspace_bytes(int64_t total_states, int64_t total_arcs, int T, bool large) {
+  return num_arc_hist_bytes(total_states, T) +
+         (large ? num_arc_terms_bytes(total_arcs) + ((total_arcs * 4 + 255) & ~(int64_t)255) : 0);
+}
+int launch_num_arc_post(const NumArcParams &p, bool large, hipStream_t stream);  // num_arc_post_kernels.hip
 
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
@@ -1064,7 +1095,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -1073,7 +1104,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -1138,6 +1138,35 @@ def num_path_entropy(input, supervision):
         return supervision.path_entropy(input)
 
 
+def num_arc_posteriors(input, supervision):
+    """The expected counts of an end-to-end ``supervision``'s own arcs under ``input``: ``post.arcs`` float64 ``(A_total,)`` in
+    the handle's arc order, ``post.finals`` float64 ``(N_total,)``, ``post.logprob`` float64 ``(B,)`` (the numerator's ``log Z``)
+    and the int64 ``(B + 1,)`` ``post.arc_offsets`` / ``post.state_offsets`` (``io.Supervision.arc_posteriors`` states the
+    quantity, the order and the arguments; ``tc_supervision_arc_posteriors``).  ``post.arcs`` is ``d log Z / d(-cost)``, so no
+    autograd is involved here; with ``den_arc_posteriors`` both halves of the LF-MMI gradient with respect to graph weights
+    exist.  Two uses:
+
+    Trainable arc costs -- HMM transition, pronunciation or silence probabilities -- ``cost(theta)`` a float64 ``(A_total,)``
+    tensor in the handle's arc order from which the FSTs were built; the numerator's share of the gradient of the loss
+    ``-weight * sum_b log Z_b``::
+
+        post = num_arc_posteriors(out, sup)
+        cost(theta).backward(gradient=weight * post.arcs)
+
+    Re-estimating them (EM; accumulate the counts of the arcs that share a parameter over an epoch first), e.g. the
+    probabilities of the arcs leaving each state of one sequence::
+
+        a0, a1 = post.arc_offsets[b], post.arc_offsets[b + 1]
+        src = torch.repeat_interleave(torch.arange(n_states), torch.as_tensor(arc_begin).diff())    # the FST's CSR rows
+        total = torch.zeros(n_states, dtype=torch.float64).index_add_(0, src, post.arcs[a0:a1].cpu())
+        new_cost = -torch.log(post.arcs[a0:a1].cpu() / total[src])
+    """
+    if not isinstance(supervision, io.Supervision):
+        raise TypeError("num_arc_posteriors takes an io.Supervision, got %s" % type(supervision).__name__)
+    with torch.no_grad():
+        return supervision.arc_posteriors(input, workspace=_workspace)
+
+
 def _int_vector(who, name, v, n, device, dtype=torch.int32):
     """``v`` as a contiguous ``(n,)`` tensor of ``dtype`` on ``device`` (a tensor already there is not brought to the host)."""
     t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import egs as _egs
-from ._lib import check, lib
+from ._lib import TorchainHipError, check, lib
 
 
 def _tuning_cache_path():
@@ -780,6 +780,7 @@ class DenominatorGraph:
 
 
 ArcPosteriors = collections.namedtuple("ArcPosteriors", "arcs entries leaks logprob per_seq_arcs per_seq_entries")
+NumArcPosteriors = collections.namedtuple("NumArcPosteriors", "arcs finals logprob arc_offsets state_offsets")
 
 
 def _group_rows(m, s0, n, B, T):
@@ -1172,6 +1173,68 @@ class Supervision:
                         C.c_void_p(ws.data_ptr()) if ws is not None else None, ws.numel() if ws is not None else 0, device.index,
                         C.c_void_p(cur)), name)
         return entropy, logprob, grad
+
+    def arc_posteriors(self, nnet_output, workspace=None):
+        """The expected counts of this end-to-end supervision's own arcs under ``nnet_output``
+        (``tc_supervision_arc_posteriors``): a ``NumArcPosteriors`` named tuple on the input's device with
+
+        ``arcs`` float64 ``(A_total,)``: per arc the expected number of times it is taken under its sequence's posterior over
+        the paths of exactly ``T_b`` arcs, ``sum_t P(arc at frame t | y_b)``.  The order is the handle's own: sequence after
+        sequence, each in the CSR order of the FST handed to ``from_e2e_fsts`` -- with ``den_graph=``, of the composed FSTs
+        that ``den_graph.normalize_fsts`` returns.  ``finals`` float64 ``(N_total,)``: the probability that the path ends in
+        each state.  ``logprob`` float64 ``(B,)``: the numerator's ``log Z``, bit for bit.  ``arc_offsets``,
+        ``state_offsets`` int64 ``(B + 1,)`` (host): where each sequence's arcs and states begin.
+
+        So ``arcs = d log Z / d(-cost)`` and ``finals = d log Z / d(-final cost)`` (the supervision's ``weight`` does not
+        enter); a sequence's arcs sum to ``T_b`` and its finals to 1.  A sequence without a path of its length gets ``logprob
+        -inf``, one with a NaN or an infinity among the outputs it reads ``NaN``; both get 0 in all their arcs and finals, and
+        the others keep their bits.  ``functions.num_arc_posteriors`` shows the two uses.
+
+        End-to-end handles only (``from_e2e_fsts``, the ``<End2End>`` egs; uniform and ragged, ``any_size`` or not);
+        ``TorchainHipError`` (unsupported) for a regular, time-unfolded handle.  Handles within 2048 states / 8192 arcs / 1024
+        distinct pdfs a sequence keep every arc in registers and the frame's terms in LDS; the others take the kernel's large
+        form (``arc_posteriors_kernel()``).  ``nnet_output`` is ``best_path``'s.  No autograd.  The handle's pool slot is not
+        written: a ``chain_loss`` on the handle is not affected."""
+        x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("arc_posteriors: nnet_output must be a CUDA tensor (only the HIP implementation is available)")
+        S, T, P = self.n_batch, self.n_frame, self.n_pdf
+        want = (S, P, T) if x.dim() == 3 else (S * T, P)
+        if x.dim() not in (2, 3) or tuple(x.shape) != want:
+            raise ValueError("arc_posteriors: nnet output of shape %s does not match the supervision (%s expected)"
+                             % (tuple(x.shape), want))
+        need = int(lib.tc_supervision_arc_posteriors_workspace_bytes(self.ptr))  # (host arithmetic only)
+        if need == -3:  # TC_ERR_UNSUPPORTED
+            raise TorchainHipError(need, "tc_supervision_arc_posteriors (end-to-end handles only; this one is regular, "
+                                         "time-unfolded)")
+        check(min(need, 0), "tc_supervision_arc_posteriors_workspace_bytes")
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dtype not in dtypes or (x.dim() == 2 and x.dtype != torch.float32):
+            x = x.float()
+        if (x.dim() == 3 and not x.is_contiguous()) or (x.dim() == 2 and (x.stride(1) != 1 or x.stride(0) < P)):
+            x = x.contiguous()
+        arc_off, state_off = np.zeros(S + 1, np.int64), np.zeros(S + 1, np.int64)
+        check(lib.tc_supervision_arc_posteriors_offsets(self.ptr, _p(arc_off), _p(state_off)), "tc_supervision_arc_posteriors_offsets")
+        device = x.device
+        arcs = torch.empty((int(arc_off[-1]),), dtype=torch.float64, device=device)
+        finals = torch.empty((int(state_off[-1]),), dtype=torch.float64, device=device)
+        logprob = torch.empty((S,), dtype=torch.float64, device=device)
+        with torch.cuda.device(device):
+            cur = torch.cuda.current_stream(device).cuda_stream
+            ws = workspace(device, cur, need) if workspace else torch.empty(need, dtype=torch.uint8, device=device)
+            check(lib.tc_supervision_arc_posteriors(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
+                                                    x.stride(0) if x.dim() == 2 else 0, C.c_void_p(arcs.data_ptr()),
+                                                    C.c_void_p(finals.data_ptr()), C.c_void_p(logprob.data_ptr()),
+                                                    C.c_void_p(ws.data_ptr()), ws.numel(), device.index, C.c_void_p(cur)),
+                  "tc_supervision_arc_posteriors")
+        return NumArcPosteriors(arcs, finals, logprob, torch.from_numpy(arc_off), torch.from_numpy(state_off))
+
+    def arc_posteriors_kernel(self):
+        """Which form of the kernel ``arc_posteriors`` runs on this end-to-end handle (``tc_supervision_arc_posteriors_kernel``,
+        host arithmetic only): 0 the resident one, 1 the large one.  ``TorchainHipError`` for a regular handle."""
+        kernel = int(lib.tc_supervision_arc_posteriors_kernel(self.ptr))
+        check(min(kernel, 0), "tc_supervision_arc_posteriors_kernel")
+        return kernel
 
     def posteriors(self, nnet_output, pdf_class=None):
         """The numerator's occupation posteriors ``gamma_num_t(j)`` under ``nnet_output``, dense float32 ``(T*B, C)`` (row
