@@ -1216,7 +1216,8 @@ int tc_supervision_path_entropy_regular(tc_supervision *supervision, const void 
  * A sequence with no path of T_s arcs gets logprob -inf, one with a NaN or +-inf at one of its own (frame, pdf) pairs -- its
  * valid frames, the pdfs of its arcs: nothing else is read -- logprob NaN; both get +0 in all their arcs and finals, and the
  * other sequences keep their bits.
- * TC_ERR_UNSUPPORTED, before any launch (the three queries return it too): a regular (time-unfolded) supervision.
+ * TC_ERR_UNSUPPORTED, before any launch (the workspace and kernel queries return it too): a regular (time-unfolded) supervision,
+ * which tc_supervision_arc_posteriors_regular serves.  tc_supervision_arc_posteriors_offsets answers for both kinds of handle.
  * TC_ERR_INVALID_ARGUMENT, before any device call: a null supervision, nnet_output or output; num_rows or num_cols that are
  * not the handle's; an unknown dtype; a 2-D call with a 16-bit dtype or row_stride < num_cols; a misaligned pointer (the
  * element's size; 8 for doubles).  TC_ERR_WORKSPACE: a short, misaligned or null workspace.  Asynchronous on `stream`, no
@@ -1230,6 +1231,58 @@ int tc_supervision_arc_posteriors(tc_supervision *supervision, const void *nnet_
                                   int64_t num_rows, int32_t num_cols, int64_t row_stride, double *arcs_dev /* [A] */,
                                   double *finals_dev /* [N] */, double *logprob_dev /* [S] */, void *workspace,
                                   int64_t workspace_bytes, int device, void *stream);
+
+/* ---- the same for a regular supervision: a level-windowed, arc-parallel kernel (num_arc_post_regular_kernels.hip) ---------------
+ * tc_supervision_arc_posteriors_regular gives tc_supervision_arc_posteriors' three outputs for a REGULAR (time-unfolded)
+ * handle -- tc_supervision_create, tc_supervision_create_ragged, the egs readers' regular examples, compositions with a
+ * denominator graph -- with that entry's argument list, one for one.  The acceptor has one level per frame, so an arc is taken
+ * at one frame only and arcs[a] is a probability:
+ *     arcs[a]   = P(arc a | y_s) = exp(log alpha_t(src) + (y_t(pdf) - cost) + log beta_{t+1}(dst) - log Z_s), t the arc's frame
+ *     finals[i] = exp(log alpha_T(i) - final(i) - log Z_s) for the states of the last level, +0 for every other state
+ *     logprob[s] = log Z_s, the numerator's (tc_num_forward_backward's), bit for bit.
+ * A sequence's arcs sum to T_s and its finals to 1, up to rounding; the arcs of one (frame, pdf) sum to the numerator's
+ * posterior of that pdf at that frame.
+ * ARC ORDER: the handle's table order -- sequence after sequence (tc_supervision_arc_posteriors_offsets, which answers for
+ * regular handles too), by source state, and within a state the order of the FST handed to the create entry.
+ * tc_supervision_arcs tells what each output element is.  The create entries require states in time order, so:
+ *   tc_supervision_create_ragged : the caller's CSR order, exactly (arc a of the concatenated arrays is output element a);
+ *   tc_supervision_create        : sequence 0's arcs are the caller's CSR order.  Sequence q > 0 has a VIRTUAL start state,
+ *     its local state 0, which carries the arcs of the FIRST state at time q * T; the other states at that time carry copies
+ *     of these arcs and give no output element.  The states of times q * T + 1 .. (q + 1) * T follow as local states 1, 2, ...
+ *     in the caller's order.  So the output is the caller's CSR order with the boundary copies left out; on a merged FST of
+ *     one sequence, or one whose sequences each end in a single state, it is the caller's order exactly.
+ *   workspace : tc_supervision_arc_posteriors_regular_workspace_bytes(supervision) bytes, 16-byte aligned: log alpha, 8 bytes a
+ *               state of the handle (a state lives in one level); the spill form adds 8 * max_level_arcs bytes a sequence.
+ *               The supervision's pool slot is read for its tables alone.
+ * One launch, one workgroup of 256 threads a sequence.  Forward: the level-windowed numerator's recursion, operand for
+ * operand.  Backward, level by level, two phases and two barriers a level: every arc leaving the level forms its term
+ * (y + logw in float32, plus log beta of its destination in double) once, stores it by arc position and stores its
+ * occupation; then every state of the level takes log beta as the log-sum over its slice of the terms.  With L the widest
+ * level's states, A the most arcs leaving a level, U the most unique (frame, pdf) entries of a frame (tc_supervision_stats):
+ *   RESIDENT terms : 24 * ceil2(L) + 8 * ceil4(A) + 4 * ceil4(U) + 2048 <= 163840;
+ *   SPILL          : 24 * ceil2(L) + 4 * ceil4(U) + 2048 <= 163840, the terms in the workspace.  Weaker than the level-windowed
+ *                    numerator's rule: every regular handle the numerator serves is served.  Same bits as the resident form
+ *                    (tc_debug_set("force_num_arc_post_regular_spill", 1) sends every handle this way).
+ * tc_supervision_arc_posteriors_regular_kernel says which: 0 resident terms, 1 spill (as the switch stands at the call).
+ * No atomics, every sum in table order: a sequence's outputs do not depend on its batch.  Failed sequences as in
+ * tc_supervision_arc_posteriors: logprob -inf (no path) or NaN (a NaN or +-inf at one of its own (frame, pdf) pairs), +0 in all
+ * its arcs and finals, the other sequences keep their bits.
+ * TC_ERR_UNSUPPORTED, before any launch (the two queries return it too): an end-to-end handle, or a handle beyond the spill
+ * rule.  TC_ERR_INVALID_ARGUMENT and TC_ERR_WORKSPACE as tc_supervision_arc_posteriors.  Asynchronous on `stream`, no
+ * allocation once the supervision is staged, no host synchronisation.  tc_debug_counter("num_arc_post_regular_launches")
+ * counts the resident form's launches, "num_arc_post_regular_spill_launches" the spill form's ("num_launches" does not move).
+ *
+ * tc_supervision_arcs: per arc of a regular handle, in that output order, its sequence, its frame, its sequence-local source
+ * and destination state, its 0-based pdf and its log weight -cost (host arrays of the handle's arc count, any may be NULL).
+ * Host arithmetic only.  TC_ERR_UNSUPPORTED for an end-to-end handle: an end-to-end arc has no frame. */
+int64_t tc_supervision_arc_posteriors_regular_workspace_bytes(const tc_supervision *supervision);
+int tc_supervision_arc_posteriors_regular_kernel(const tc_supervision *supervision);
+int tc_supervision_arc_posteriors_regular(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
+                                          int64_t num_rows, int32_t num_cols, int64_t row_stride, double *arcs_dev /* [A] */,
+                                          double *finals_dev /* [N] */, double *logprob_dev /* [S] */, void *workspace,
+                                          int64_t workspace_bytes, int device, void *stream);
+int tc_supervision_arcs(const tc_supervision *supervision, int32_t *seq, int32_t *frame, int32_t *src, int32_t *dst,
+                        int32_t *pdf, float *logw);
 
 /* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
  * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token

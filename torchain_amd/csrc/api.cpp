@@ -687,10 +687,9 @@ int tc_supervision_arc_posteriors_kernel(const tc_supervision *sup) {
 
 int tc_supervision_arc_posteriors_offsets(const tc_supervision *sup, int64_t *arc_offsets, int64_t *state_offsets) {
   if (!sup || !arc_offsets || !state_offsets) return TC_ERR_INVALID_ARGUMENT;
-  if (!sup->e2e) return TC_ERR_UNSUPPORTED;
   for (int s = 0; s <= sup->S; ++s) {
-    arc_offsets[s] = sup->e2e_tab.arc_off[s];
-    state_offsets[s] = sup->e2e_tab.state_off[s];
+    arc_offsets[s] = sup->e2e ? sup->e2e_tab.arc_off[s] : sup->tab.seq_arc_off[s];
+    state_offsets[s] = sup->e2e ? sup->e2e_tab.state_off[s] : sup->tab.seq_state_off[s];
   }
   return TC_OK;
 }
@@ -733,6 +732,96 @@ int tc_supervision_arc_posteriors(tc_supervision *sup, const void *y, int dtype,
   rc = launch_num_arc_post(p, large, stream);
   if (rc != TC_OK) return rc;
   return supervision_mark_use(sup, device, stream);
+}
+
+// tc_supervision_arc_posteriors_regular's size rules (num_arc_post_regular_kernels.hip), by the handle's widest level: the
+// terms of the arcs leaving a level in LDS, *spill = false; otherwise, or with "force_num_arc_post_regular_spill", in the
+// workspace.  The spill rule is weaker than the level-windowed numerator's, so what the numerator trains is served.
+static int num_arc_post_regular_rule(const tc_supervision *sup, bool *spill) {
+  if (sup->e2e) return TC_ERR_UNSUPPORTED;
+  const NumTables &tb = sup->tab;
+  *spill = debug_flag(kDbgForceNumArcPostRegularSpill) ||
+           !num_arc_regular_fits(tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq, false);
+  return num_arc_regular_fits(tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq, *spill) ? TC_OK : TC_ERR_UNSUPPORTED;
+}
+
+int64_t tc_supervision_arc_posteriors_regular_workspace_bytes(const tc_supervision *sup) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  bool spill = false;
+  const int rc = num_arc_post_regular_rule(sup, &spill);
+  if (rc != TC_OK) return rc;
+  return num_arc_regular_workspace_bytes(sup->tab.seq_state_off[sup->S], sup->S, sup->tab.max_level_arcs, spill);
+}
+
+int tc_supervision_arc_posteriors_regular_kernel(const tc_supervision *sup) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  bool spill = false;
+  const int rc = num_arc_post_regular_rule(sup, &spill);
+  return rc != TC_OK ? rc : spill ? 1 : 0;
+}
+
+int tc_supervision_arc_posteriors_regular(tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows,
+                                          int32_t cols, int64_t y_stride, double *arcs_dev, double *finals_dev,
+                                          double *logprob_dev, void *workspace, int64_t workspace_bytes, int device,
+                                          void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!sup || !y || !arcs_dev || !finals_dev || !logprob_dev) return TC_ERR_INVALID_ARGUMENT;
+  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && dtype != TC_DTYPE_F32) return TC_ERR_INVALID_ARGUMENT;  // (2-D tensors are float32, as NumParams::y)
+  if ((int64_t)sup->S * sup->T != rows || sup->P != cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)y & (dtype == TC_DTYPE_F32 ? 3 : 1)) != 0 ||
+      (((uintptr_t)arcs_dev | (uintptr_t)finals_dev | (uintptr_t)logprob_dev) & 7) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  bool spill = false;
+  int rc = num_arc_post_regular_rule(sup, &spill);
+  if (rc != TC_OK) return rc;
+  const NumTables &tb = sup->tab;
+  const int64_t need = num_arc_regular_workspace_bytes(tb.seq_state_off[sup->S], sup->S, tb.max_level_arcs, spill);
+  if (!workspace || need > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  hipStream_t stream = (hipStream_t)stream_v;
+  NumArcRegParams p;
+  // (a (B, C, T) tensor has no row stride: fill_num_params is given the dense one)
+  rc = fill_num_params(sup, device, stream, (const float *)y, rows, cols, layout_bct ? (int64_t)cols : y_stride, nullptr, 0,
+                       nullptr, 0, nullptr, &p.n);
+  if (rc != TC_OK) return rc;
+  p.n.y_bct = layout_bct ? 1 : 0;
+  p.n.elem = dtype;
+  p.arcs = arcs_dev;
+  p.finals = finals_dev;
+  p.logprob = logprob_dev;
+  p.hist = (double *)workspace;  // [history] [terms]
+  p.terms = spill ? (double *)((char *)workspace + num_arc_regular_hist_bytes(tb.seq_state_off[sup->S])) : nullptr;
+  p.term_stride = tb.max_level_arcs;
+  rc = launch_num_arc_post_regular(p, spill, stream);
+  if (rc != TC_OK) return rc;
+  return supervision_mark_use(sup, device, stream);
+}
+
+// The arcs of a regular handle in its table order -- the order of tc_supervision_arc_posteriors_regular's output: host
+// arithmetic on the tables alone.  An arc's frame is its source state's level.
+int tc_supervision_arcs(const tc_supervision *sup, int32_t *seq, int32_t *frame, int32_t *src, int32_t *dst, int32_t *pdf,
+                        float *logw) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  if (sup->e2e) return TC_ERR_UNSUPPORTED;
+  const NumTables &tb = sup->tab;
+  for (int s = 0; s < sup->S; ++s) {
+    const int32_t *level = &tb.level_begin[tb.seq_level_off[s]];
+    const int ub = tb.seq_uniq_off[s];
+    int t = 0;  // (arcs are sorted by source state: the frame only moves forward)
+    for (int a = tb.seq_arc_off[s]; a < tb.seq_arc_off[s + 1]; ++a) {
+      while (level[t + 1] <= tb.arc_src[a]) ++t;
+      if (seq) seq[a] = s;
+      if (frame) frame[a] = t;
+      if (src) src[a] = tb.arc_src[a];
+      if (dst) dst[a] = tb.arc_dst[a];
+      if (pdf) pdf[a] = tb.uniq_pdf[ub + tb.arc_uniq[a]];
+      if (logw) logw[a] = tb.arc_logw[a];
+    }
+  }
+  return TC_OK;
 }
 
 int64_t tc_den_best_path_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {

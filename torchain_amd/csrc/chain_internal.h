@@ -961,6 +961,43 @@ inline int64_t num_arc_workspace_bytes(int64_t total_states, int64_t total_arcs,
          (large ? num_arc_terms_bytes(total_arcs) + ((total_arcs * 4 + 255) & ~(int64_t)255) : 0);
 }
 int launch_num_arc_post(const NumArcParams &p, bool large, hipStream_t stream);  // num_arc_post_kernels.hip
+// The same occupations for a REGULAR supervision (tc_supervision_arc_posteriors_regular, num_arc_post_regular_kernels.hip): an
+// arc is taken at one frame only, so an occupation is stored once.  `hist` is log alpha of every state of the handle, one
+// double at seq_state_off[s]; `terms` (the SPILL form alone, null otherwise) one double per arc leaving a level, term_stride
+// doubles a sequence.  LDS, sized by the handle's widest level (L states, A arcs leaving it, U unique entries of a frame):
+// log beta of two levels (forward: log alpha) and log alpha of one as doubles, the frame's y as floats and, in the RESIDENT
+// form, a double per arc leaving the level.  The two size rules:
+//   resident terms : 24 * ceil2(L) + 8 * ceil4(A) + 4 * ceil4(U) + 2048 <= 163840
+//   spill          : 24 * ceil2(L) + 4 * ceil4(U) + 2048 <= 163840, weaker than the level-windowed numerator's
+//                    (num_windowed_lds_bytes has 32 * ceil2(L)): every handle the numerator serves is served.
+struct NumArcRegParams {
+  NumParams n;
+  double *arcs;     // [seq_arc_off[S]]: the handle's table order
+  double *finals;   // [seq_state_off[S]]
+  double *logprob;  // [S]
+  double *hist;
+  double *terms;
+  int64_t term_stride;
+};
+constexpr int kNumArcRegStaticLds = 2048;
+constexpr size_t num_arc_regular_lds_bytes(int32_t level_states, int32_t level_arcs, int32_t frame_uniq, bool spill) {
+  return (size_t)((level_states + 1) & ~1) * 24 + (size_t)((frame_uniq + 3) & ~3) * 4 +
+         (spill ? 0 : (size_t)((level_arcs + 3) & ~3) * 8);
+}
+constexpr bool num_arc_regular_fits(int32_t level_states, int32_t level_arcs, int32_t frame_uniq, bool spill) {
+  return num_arc_regular_lds_bytes(level_states, level_arcs, frame_uniq, spill) + kNumArcRegStaticLds <= (size_t)kLdsLimitBytes;
+}
+// the resident rule at its edge: beside the narrowest level (one state, one entry) 20216 arcs' terms fill the 160 KB to the
+// byte, and one arc more spills
+static_assert(num_arc_regular_lds_bytes(1, 20216, 1, false) + kNumArcRegStaticLds == (size_t)kLdsLimitBytes &&
+                  num_arc_regular_fits(1, 20216, 1, false) && !num_arc_regular_fits(1, 20217, 1, false) &&
+                  num_arc_regular_fits(1, 20217, 1, true),
+              "the regular arc-posterior kernel's resident terms end where kLdsLimitBytes ends");
+inline int64_t num_arc_regular_hist_bytes(int64_t total_states) { return ((int64_t)8 * total_states + 255) & ~(int64_t)255; }
+inline int64_t num_arc_regular_workspace_bytes(int64_t total_states, int S, int32_t max_level_arcs, bool spill) {
+  return num_arc_regular_hist_bytes(total_states) + (spill ? ((int64_t)8 * S * max_level_arcs + 255) & ~(int64_t)255 : 0);
+}
+int launch_num_arc_post_regular(const NumArcRegParams &p, bool spill, hipStream_t stream);  // num_arc_post_regular_kernels.hip
 
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
@@ -1095,7 +1132,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgForceNumArcPostRegularSpill, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -1104,7 +1141,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntNumArcPostRegular, kCntNumArcPostRegularSpill, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

@@ -1138,7 +1138,7 @@ def num_path_entropy(input, supervision):
         return supervision.path_entropy(input)
 
 
-def num_arc_posteriors(input, supervision):
+def num_arc_posteriors(input, supervision, regular=False):
     """The expected counts of an end-to-end ``supervision``'s own arcs under ``input``: ``post.arcs`` float64 ``(A_total,)`` in
     the handle's arc order, ``post.finals`` float64 ``(N_total,)``, ``post.logprob`` float64 ``(B,)`` (the numerator's ``log Z``)
     and the int64 ``(B + 1,)`` ``post.arc_offsets`` / ``post.state_offsets`` (``io.Supervision.arc_posteriors`` states the
@@ -1160,11 +1160,21 @@ def num_arc_posteriors(input, supervision):
         src = torch.repeat_interleave(torch.arange(n_states), torch.as_tensor(arc_begin).diff())    # the FST's CSR rows
         total = torch.zeros(n_states, dtype=torch.float64).index_add_(0, src, post.arcs[a0:a1].cpu())
         new_cost = -torch.log(post.arcs[a0:a1].cpu() / total[src])
+
+    ``regular=True`` also takes a regular, time-unfolded supervision -- what every chain model after the flat-start stage, and
+    every lattice-derived supervision, is trained on -- on a level-windowed kernel of its own
+    (``tc_supervision_arc_posteriors_regular``); an end-to-end handle goes where it went.  (A keyword, not the default, only
+    because the default call's refusal of a regular handle is pinned by a test.)  An arc of such a handle is taken at one
+    frame, so ``post.arcs`` are per-lattice-arc posteriors; ``supervision.arcs()`` names each element's sequence, frame,
+    states, pdf and weight, and pools them by parameter::
+
+        post, arc = num_arc_posteriors(out, sup, regular=True), sup.arcs()
+        counts = torch.zeros(K, dtype=torch.float64).index_add_(0, torch.as_tensor(cls_of_pdf[arc.pdf]), post.arcs.cpu())
     """
     if not isinstance(supervision, io.Supervision):
         raise TypeError("num_arc_posteriors takes an io.Supervision, got %s" % type(supervision).__name__)
     with torch.no_grad():
-        return supervision.arc_posteriors(input, workspace=_workspace)
+        return supervision.arc_posteriors(input, workspace=_workspace, regular=regular)
 
 
 def _int_vector(who, name, v, n, device, dtype=torch.int32):

@@ -781,6 +781,7 @@ class DenominatorGraph:
 
 ArcPosteriors = collections.namedtuple("ArcPosteriors", "arcs entries leaks logprob per_seq_arcs per_seq_entries")
 NumArcPosteriors = collections.namedtuple("NumArcPosteriors", "arcs finals logprob arc_offsets state_offsets")
+SupervisionArcs = collections.namedtuple("SupervisionArcs", "seq frame src dst pdf logw")
 
 
 def _group_rows(m, s0, n, B, T):
@@ -1174,7 +1175,7 @@ class Supervision:
                         C.c_void_p(cur)), name)
         return entropy, logprob, grad
 
-    def arc_posteriors(self, nnet_output, workspace=None):
+    def arc_posteriors(self, nnet_output, workspace=None, regular=False):
         """The expected counts of this end-to-end supervision's own arcs under ``nnet_output``
         (``tc_supervision_arc_posteriors``): a ``NumArcPosteriors`` named tuple on the input's device with
 
@@ -1194,7 +1195,18 @@ class Supervision:
         ``TorchainHipError`` (unsupported) for a regular, time-unfolded handle.  Handles within 2048 states / 8192 arcs / 1024
         distinct pdfs a sequence keep every arc in registers and the frame's terms in LDS; the others take the kernel's large
         form (``arc_posteriors_kernel()``).  ``nnet_output`` is ``best_path``'s.  No autograd.  The handle's pool slot is not
-        written: a ``chain_loss`` on the handle is not affected."""
+        written: a ``chain_loss`` on the handle is not affected.
+
+        ``regular=True`` also serves regular, time-unfolded handles (``from_fst``, ``from_fsts``, ``from_sequences``,
+        ``from_alignments``, ``den_graph=`` compositions, the egs readers) through ``tc_supervision_arc_posteriors_regular``, a
+        level-windowed kernel of their own; an end-to-end handle goes where it went.  It is a keyword, and not the default,
+        only because the default call's refusal of a regular handle is pinned by a test.  There an arc is taken at one frame,
+        so ``arcs`` holds probabilities: the order is the handle's table order, which ``arcs()`` spells out per element and
+        which is the CSR order of the FSTs handed over (``from_fst`` on a merged FST leaves out the copies of a sequence's
+        start arcs on all but the first boundary state; ``include/torchain_hip.h``); ``finals`` is +0 outside the last level.
+        Every handle the numerator serves is served: the terms of the arcs leaving a level live in LDS while ``24 *
+        max_level_states + 8 * max_level_arcs + 4 * max_frame_uniq + 2048 <= 163840`` (``stats()``) and in the workspace
+        beyond that, with the same bits."""
         x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise ValueError("arc_posteriors: nnet_output must be a CUDA tensor (only the HIP implementation is available)")
@@ -1203,11 +1215,12 @@ class Supervision:
         if x.dim() not in (2, 3) or tuple(x.shape) != want:
             raise ValueError("arc_posteriors: nnet output of shape %s does not match the supervision (%s expected)"
                              % (tuple(x.shape), want))
-        need = int(lib.tc_supervision_arc_posteriors_workspace_bytes(self.ptr))  # (host arithmetic only)
-        if need == -3:  # TC_ERR_UNSUPPORTED
+        name = "tc_supervision_arc_posteriors_regular" if regular and not self.is_e2e else "tc_supervision_arc_posteriors"
+        need = int(getattr(lib, name + "_workspace_bytes")(self.ptr))  # (host arithmetic only)
+        if need == -3 and not self.is_e2e and not regular:  # TC_ERR_UNSUPPORTED
             raise TorchainHipError(need, "tc_supervision_arc_posteriors (end-to-end handles only; this one is regular, "
-                                         "time-unfolded)")
-        check(min(need, 0), "tc_supervision_arc_posteriors_workspace_bytes")
+                                         "time-unfolded: regular=True serves it)")
+        check(min(need, 0), name + "_workspace_bytes")
         dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
         if x.dtype not in dtypes or (x.dim() == 2 and x.dtype != torch.float32):
             x = x.float()
@@ -1222,19 +1235,36 @@ class Supervision:
         with torch.cuda.device(device):
             cur = torch.cuda.current_stream(device).cuda_stream
             ws = workspace(device, cur, need) if workspace else torch.empty(need, dtype=torch.uint8, device=device)
-            check(lib.tc_supervision_arc_posteriors(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
-                                                    x.stride(0) if x.dim() == 2 else 0, C.c_void_p(arcs.data_ptr()),
-                                                    C.c_void_p(finals.data_ptr()), C.c_void_p(logprob.data_ptr()),
-                                                    C.c_void_p(ws.data_ptr()), ws.numel(), device.index, C.c_void_p(cur)),
-                  "tc_supervision_arc_posteriors")
+            check(getattr(lib, name)(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T, P,
+                                     x.stride(0) if x.dim() == 2 else 0, C.c_void_p(arcs.data_ptr()),
+                                     C.c_void_p(finals.data_ptr()), C.c_void_p(logprob.data_ptr()),
+                                     C.c_void_p(ws.data_ptr()), ws.numel(), device.index, C.c_void_p(cur)), name)
         return NumArcPosteriors(arcs, finals, logprob, torch.from_numpy(arc_off), torch.from_numpy(state_off))
 
     def arc_posteriors_kernel(self):
-        """Which form of the kernel ``arc_posteriors`` runs on this end-to-end handle (``tc_supervision_arc_posteriors_kernel``,
-        host arithmetic only): 0 the resident one, 1 the large one.  ``TorchainHipError`` for a regular handle."""
-        kernel = int(lib.tc_supervision_arc_posteriors_kernel(self.ptr))
-        check(min(kernel, 0), "tc_supervision_arc_posteriors_kernel")
+        """Which form of the kernel ``arc_posteriors`` runs on this handle (host arithmetic only).  End-to-end
+        (``tc_supervision_arc_posteriors_kernel``): 0 the resident one, 1 the large one.  Regular, with ``regular=True``
+        (``tc_supervision_arc_posteriors_regular_kernel``): 0 the terms of a level's arcs in LDS, 1 in the workspace.
+        ``TorchainHipError`` for a regular handle beyond the spill rule."""
+        query = lib.tc_supervision_arc_posteriors_kernel if self.is_e2e else lib.tc_supervision_arc_posteriors_regular_kernel
+        kernel = int(query(self.ptr))
+        check(min(kernel, 0), "tc_supervision_arc_posteriors_kernel" if self.is_e2e else "tc_supervision_arc_posteriors_regular_kernel")
         return kernel
+
+    def arcs(self):
+        """What each element of ``arc_posteriors(..., regular=True).arcs`` is (``tc_supervision_arcs``): a ``SupervisionArcs``
+        named tuple of numpy arrays, one entry per arc of this regular handle in the output's order -- ``seq``, ``frame``,
+        the sequence-local ``src`` and ``dst`` states, the 0-based ``pdf`` (int32) and ``logw = -cost`` (float32).  With it a
+        caller pools occupations by whatever parameter the arcs share, ``cls`` an int64 tensor of one class per arc::
+
+            counts = torch.zeros(K, dtype=torch.float64).index_add_(0, cls, post.arcs.cpu())
+
+        ``TorchainHipError`` (unsupported) for an end-to-end handle, whose arcs have no frame."""
+        arc_off, state_off = np.zeros(self.n_batch + 1, np.int64), np.zeros(self.n_batch + 1, np.int64)
+        check(lib.tc_supervision_arc_posteriors_offsets(self.ptr, _p(arc_off), _p(state_off)), "tc_supervision_arc_posteriors_offsets")
+        out = [np.zeros(int(arc_off[-1]), np.int32) for _ in range(5)] + [np.zeros(int(arc_off[-1]), np.float32)]
+        check(lib.tc_supervision_arcs(self.ptr, *(_p(a) for a in out)), "tc_supervision_arcs")
+        return SupervisionArcs(*out)
 
     def posteriors(self, nnet_output, pdf_class=None):
         """The numerator's occupation posteriors ``gamma_num_t(j)`` under ``nnet_output``, dense float32 ``(T*B, C)`` (row
