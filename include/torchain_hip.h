@@ -1284,6 +1284,65 @@ int tc_supervision_arc_posteriors_regular(tc_supervision *supervision, const voi
 int tc_supervision_arcs(const tc_supervision *supervision, int32_t *seq, int32_t *frame, int32_t *src, int32_t *dst,
                         int32_t *pdf, float *logw);
 
+/* ---- alignments drawn from a supervision's path posterior (num_sample_kernels.hip) --------------------------------------------
+ * tc_supervision_sample_paths draws K whole alignments per sequence from P(path | y, supervision), for REGULAR and
+ * END-TO-END handles alike: what tc_den_sample_paths is to the denominator graph.  The paths are those of exactly T_s arcs
+ * from the start state to a final state of sequence s's FST -- the numerator's model: no clamp on y, no leaky term, and the
+ * supervision's weight does not enter.  This text is the rule; a float64 reference that follows it reproduces every output
+ * except where a uniform falls within rounding of an interval's end.
+ *   la_t(j)   : the numerator's log alpha in float64, formed by the numerator's own device functions (num_device.h for regular
+ *               handles, the forward half of num_e2e_kernel for end-to-end ones): logprob[s] = log Z_s is the numerator's
+ *               (tc_num_forward_backward's, tc_supervision_path_entropy's), bit for bit.
+ *   pick(weights, u) : tc_den_sample_paths' rule -- the first index, in list order, whose inclusive cumulative sum exceeds
+ *               u * total, in doubles; the last index of positive weight when rounding leaves none; a zero weight is never picked.
+ *   per sample, with its uniforms u[0 .. T]:
+ *     j_T = pick(exp(la_T(i) + (double)final_lw(i) - log Z) over i, u[T]); i runs over the sequence's states in state order
+ *           (end-to-end) or over the last level's states in state order (regular); final_lw = -final cost, -inf: not final.
+ *     for t = T - 1 .. 0: the in-arcs of j_{t+1} in the handle's in-list order (the lists the forward pass and
+ *           tc_supervision_best_path walk); arc a weighs exp(((double)(lw_a + y_t(pdf_a)) + la_t(src_a)) - la_{t+1}(j_{t+1})),
+ *           the float32 sum rounded once -- the operand the forward pass log-adds; pick with u[t] gives pdf_t and j_t = src_a.
+ *     score = (double)final_lw(j_T) + the terms (double)(lw_a + y_t(pdf_a)) added in the order t = T - 1 .. 0: the path's log
+ *           weight, exactly reproducible; score - logprob = log P(path | y).
+ *   uniforms  : float32 (S, K, T_max + 1) in [0, 1), the caller's: there is no generator in the kernel.  A sample is a function
+ *               of its own uniforms: sample k of a K-sample call is sample k of any other, and a sequence's samples do not
+ *               depend on its batch.
+ *   pdf_dev   : int32 (S, K, T_max), 0-based pdfs; score_dev: double (S, K); logprob_dev: double (S);
+ *   state_dev : nullable, int32 (S, K, T_max + 1): j_0 .. j_T, sequence-local states (regular: the handle's time-ordered local
+ *               states; slot 0 is the start state).
+ *   nnet_output, dtype, layout_bct, num_rows, num_cols, row_stride: as tc_supervision_arc_posteriors takes them.
+ *   workspace : tc_supervision_sample_paths_workspace_bytes(supervision) bytes, 16-byte aligned.  The forward pass writes its
+ *               history THERE -- end-to-end: the rows la_t, t = 0 .. T, 8 bytes a (frame, state); regular: 8 bytes a state.
+ *               The supervision's pool slot is read for its tables alone.
+ * Failures: a sequence without a path of its length gets logprob -inf; one with a NaN or an infinity among the outputs it reads
+ * gets logprob NaN.  Both get -1 in every pdf and state slot and NaN in their scores; the other sequences keep their bits.
+ * The padding frames of a ragged handle get -1 (pdf slots t >= T_s, state slots t > T_s), and nothing at t >= T_s is read.
+ * One launch, one workgroup of 256 threads a sequence.  The traceback is LEVEL-SYNCHRONOUS: all K samples of a sequence step
+ * back one frame together; wave w owns the samples w, w + 4, ..., whose current state, la_{t+1}(j_{t+1}) and running score
+ * stay in its registers; a pick is wave-wide (chunks of 64, an inclusive double prefix, the crossing lane by ballot; lists
+ * longer than 64 in two passes).  Two forms, the same bits:
+ *   STAGED   : per level the workgroup stages la_t (end-to-end: the row; regular: the level's window) and the frame's y (per
+ *              distinct pdf; per unique entry) in LDS once, the next level's a level ahead into a second buffer; the picks
+ *              gather from LDS and only the in-arc records and list bounds come from L2.
+ *              16 * ceil4(states) + 8 * ceil4(distinct pdfs) + 2048 <= 163840 for every sequence (end-to-end);
+ *              16 * ceil2(L) + 8 * ceil4(U) + 2048 <= 163840 (regular: L the widest level, U the most unique entries of a frame).
+ *   STREAMED : the picks read la_t from the workspace and y from the caller's tensor.  Every handle beyond the staged rule, and
+ *              every handle with tc_debug_set("force_num_sample_streamed", 1).  Its LDS is the forward pass's, so its rule is
+ *              the numerator's own, as tc_supervision_best_path's: every handle the numerator serves is served.
+ * tc_supervision_sample_paths_kernel says which: 0 staged, 1 streamed (as the switch stands at the call).
+ * TC_ERR_INVALID_ARGUMENT, before any device call: a null handle or pointer (state_dev excepted), num_samples <= 0, a dtype or
+ * shape the handle does not take, misaligned pointers.  TC_ERR_WORKSPACE: a null, short or misaligned workspace.
+ * Asynchronous on `stream`, no allocation once the supervision is staged, no host synchronisation.
+ * tc_debug_counter("num_sample_launches") counts the launches, "num_sample_streamed_launches" those of them in the streamed
+ * form ("num_launches" and "best_path_launches" do not move). */
+int64_t tc_supervision_sample_paths_workspace_bytes(const tc_supervision *supervision);
+int tc_supervision_sample_paths_kernel(const tc_supervision *supervision);
+int tc_supervision_sample_paths(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
+                                int64_t num_rows, int32_t num_cols, int64_t row_stride, int32_t num_samples,
+                                const float *uniforms_dev /* [S][K][T + 1] */, int32_t *pdf_dev /* [S][K][T] */,
+                                double *score_dev /* [S][K] */, double *logprob_dev /* [S] */,
+                                int32_t *state_dev /* nullable, [S][K][T + 1] */, void *workspace, int64_t workspace_bytes,
+                                int device, void *stream);
+
 /* ---- sampled paths scored on the device (path_edit_kernels.hip) ------------------------------------------------------------
  * tc_paths_edit_distance turns frame-level pdf paths -- what tc_den_sample_paths and tc_den_best_path write -- into token
  * sequences and scores each against its sequence's reference by the unit-cost Levenshtein distance: the risk of a

@@ -257,6 +257,12 @@ def _load():
     L.tc_supervision_arc_posteriors_regular_kernel.argtypes = [vp]
     L.tc_supervision_arc_posteriors_regular.restype = C.c_int
     L.tc_supervision_arc_posteriors_regular.argtypes = L.tc_supervision_arc_posteriors.argtypes
+    L.tc_supervision_sample_paths_workspace_bytes.restype = i64
+    L.tc_supervision_sample_paths_workspace_bytes.argtypes = [vp]
+    L.tc_supervision_sample_paths_kernel.restype = C.c_int
+    L.tc_supervision_sample_paths_kernel.argtypes = [vp]
+    L.tc_supervision_sample_paths.restype = C.c_int
+    L.tc_supervision_sample_paths.argtypes = [vp, vp, C.c_int, C.c_int, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, i64, C.c_int, vp]
     L.tc_supervision_arcs.restype = C.c_int
     L.tc_supervision_arcs.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.tc_den_arc_posteriors_workspace_bytes.restype = i64

@@ -824,6 +824,85 @@ int tc_supervision_arcs(const tc_supervision *sup, int32_t *seq, int32_t *frame,
   return TC_OK;
 }
 
+// tc_supervision_sample_paths' size rules (num_sample_kernels.hip).  The streamed form's LDS is the forward pass's, so its
+// rule is the numerator's own, as tc_supervision_best_path's; the staged form needs a second y buffer beside it.  *streamed:
+// the handle is beyond the staged rule, or "force_num_sample_streamed" is set.
+static int num_sample_rule(const tc_supervision *sup, bool *streamed) {
+  bool staged = !debug_flag(kDbgForceNumSampleStreamed);
+  if (sup->e2e) {
+    const E2eTables &e = sup->e2e_tab;
+    for (int s = 0; s < sup->S; ++s) {
+      const int ns = (e.state_off[s + 1] - e.state_off[s] + 3) & ~3, np = (e.pdf_off[s + 1] - e.pdf_off[s] + 3) & ~3;
+      if (!num_sample_fits(ns, np, true)) return TC_ERR_UNSUPPORTED;  // (not reached: e2e_large_fits, the create entries')
+      staged = staged && num_sample_fits(ns, np, false);
+    }
+  } else {
+    const NumTables &tb = sup->tab;
+    const int L = (tb.max_level_states + 1) & ~1, U = (tb.max_frame_uniq + 3) & ~3;
+    if (!num_sample_fits(L, U, true)) return TC_ERR_UNSUPPORTED;
+    staged = staged && num_sample_fits(L, U, false);
+  }
+  *streamed = !staged;
+  return TC_OK;
+}
+
+int64_t tc_supervision_sample_paths_workspace_bytes(const tc_supervision *sup) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  bool streamed = false;
+  const int rc = num_sample_rule(sup, &streamed);
+  if (rc != TC_OK) return rc;
+  return num_sample_workspace_bytes(sup->e2e, sup->e2e ? sup->e2e_tab.total_states : sup->tab.seq_state_off[sup->S], sup->T);
+}
+
+int tc_supervision_sample_paths_kernel(const tc_supervision *sup) {
+  if (!sup) return TC_ERR_INVALID_ARGUMENT;
+  bool streamed = false;
+  const int rc = num_sample_rule(sup, &streamed);
+  return rc != TC_OK ? rc : streamed ? 1 : 0;
+}
+
+int tc_supervision_sample_paths(tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows, int32_t cols,
+                                int64_t y_stride, int32_t num_samples, const float *uniforms_dev, int32_t *pdf_dev,
+                                double *score_dev, double *logprob_dev, int32_t *state_dev, void *workspace,
+                                int64_t workspace_bytes, int device, void *stream_v) {
+  // (every argument check in front of the first device call)
+  if (!sup || !y || !uniforms_dev || !pdf_dev || !score_dev || !logprob_dev || num_samples <= 0) return TC_ERR_INVALID_ARGUMENT;
+  if (dtype != TC_DTYPE_F32 && dtype != TC_DTYPE_BF16 && dtype != TC_DTYPE_F16) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && dtype != TC_DTYPE_F32) return TC_ERR_INVALID_ARGUMENT;  // (2-D tensors are float32, as NumParams::y)
+  if ((int64_t)sup->S * sup->T != rows || sup->P != cols) return TC_ERR_INVALID_ARGUMENT;
+  if (!layout_bct && y_stride < cols) return TC_ERR_INVALID_ARGUMENT;
+  if (((uintptr_t)y & (dtype == TC_DTYPE_F32 ? 3 : 1)) != 0 ||
+      (((uintptr_t)uniforms_dev | (uintptr_t)pdf_dev | (uintptr_t)state_dev) & 3) != 0 ||
+      (((uintptr_t)score_dev | (uintptr_t)logprob_dev) & 7) != 0)
+    return TC_ERR_INVALID_ARGUMENT;
+  bool streamed = false;
+  int rc = num_sample_rule(sup, &streamed);
+  if (rc != TC_OK) return rc;
+  const int64_t need =
+      num_sample_workspace_bytes(sup->e2e, sup->e2e ? sup->e2e_tab.total_states : sup->tab.seq_state_off[sup->S], sup->T);
+  if (!workspace || need > workspace_bytes || !aligned16(workspace)) return TC_ERR_WORKSPACE;
+  DeviceGuard guard(device);
+  if (!guard.ok) return TC_ERR_HIP;
+  hipStream_t stream = (hipStream_t)stream_v;
+  NumSampleParams p;
+  // (a (B, C, T) tensor has no row stride: fill_num_params is given the dense one)
+  rc = fill_num_params(sup, device, stream, (const float *)y, rows, cols, layout_bct ? (int64_t)cols : y_stride, nullptr, 0,
+                       nullptr, 0, nullptr, &p.n);
+  if (rc != TC_OK) return rc;
+  p.n.y_bct = layout_bct ? 1 : 0;
+  p.n.elem = dtype;
+  p.uniforms = uniforms_dev;
+  p.pdf_out = pdf_dev;
+  p.score_out = score_dev;
+  p.logprob = logprob_dev;
+  p.state_out = state_dev;
+  p.hist = (double *)workspace;
+  p.K = num_samples;
+  rc = launch_num_sample_paths(p, streamed, stream);
+  if (rc != TC_OK) return rc;
+  return supervision_mark_use(sup, device, stream);
+}
+
 int64_t tc_den_best_path_workspace_bytes(const tc_den_graph *g, int32_t S, int32_t T) {
   if (!g || S <= 0 || T <= 0) return TC_ERR_INVALID_ARGUMENT;
   return den_best_workspace_bytes(g->H, S, T);

@@ -998,6 +998,36 @@ inline int64_t num_arc_regular_workspace_bytes(int64_t total_states, int S, int3
   return num_arc_regular_hist_bytes(total_states) + (spill ? ((int64_t)8 * S * max_level_arcs + 255) & ~(int64_t)255 : 0);
 }
 int launch_num_arc_post_regular(const NumArcRegParams &p, bool spill, hipStream_t stream);  // num_arc_post_regular_kernels.hip
+// Alignments drawn from a supervision's path posterior (tc_supervision_sample_paths, num_sample_kernels.hip), regular and
+// end-to-end handles alike.  `n` carries what the numerator's launches carry; the pool slot's scratch is neither read nor
+// written.  `hist` is the caller's workspace: end-to-end, the rows log alpha_t, t = 0 .. T, one double a (frame, state) at
+// (T + 1) * state_off[s] doubles; regular, one double per state of the handle at seq_state_off[s].
+struct NumSampleParams {
+  NumParams n;
+  const float *uniforms;  // [S][K][T + 1]
+  int32_t *pdf_out;       // [S][K][T]
+  double *score_out;      // [S][K]
+  double *logprob;        // [S]
+  int32_t *state_out;     // nullable: [S][K][T + 1], sequence-local states
+  double *hist;
+  int K;
+};
+// LDS of the kernel: the forward pass's two double vectors (end-to-end: ceil4(states) of the sequence; regular: the widest
+// level) and the frame's y (per distinct pdf; per unique entry of the widest frame).  The STAGED traceback reuses the two
+// vectors for log alpha of two adjacent levels and needs a second y buffer beside the first; the STREAMED one needs nothing
+// more than the forward pass, whose rule is the numerator's own (e2e_large_fits / num_windowed_fits, as best_path's).
+// (states, ys: rounded as the numerator rounds them -- ceil4 of a sequence's states and distinct pdfs; NumParams::win_states
+// and win_uniq)
+constexpr size_t num_sample_lds_bytes(int32_t states, int32_t ys, bool streamed) {
+  return (size_t)16 * states + (size_t)(streamed ? 4 : 8) * ys;
+}
+constexpr bool num_sample_fits(int32_t states, int32_t ys, bool streamed) {
+  return num_sample_lds_bytes(states, ys, streamed) + 2048 <= (size_t)kLdsLimitBytes;
+}
+inline int64_t num_sample_workspace_bytes(bool e2e, int64_t total_states, int T) {
+  return ((int64_t)8 * (e2e ? T + 1 : 1) * total_states + 255) & ~(int64_t)255;
+}
+int launch_num_sample_paths(const NumSampleParams &p, bool streamed, hipStream_t stream);  // num_sample_kernels.hip
 
 // Side streams and fork / join events per (device, caller stream) (made on first use; the hot path only records and waits):
 // `den_side` carries the backward recursion of the two-CU form (den_tied_split.hip), `num_side` the numerator when
@@ -1132,7 +1162,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgForceNumArcPostRegularSpill, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgForceNumArcPostRegularSpill, kDbgForceNumSampleStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -1141,7 +1171,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntNumArcPostRegular, kCntNumArcPostRegularSpill, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntNumArcPostRegular, kCntNumArcPostRegularSpill, kCntNumSample, kCntNumSampleStreamed, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

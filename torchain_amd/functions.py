@@ -1177,6 +1177,31 @@ def num_arc_posteriors(input, supervision, regular=False):
         return supervision.arc_posteriors(input, workspace=_workspace, regular=regular)
 
 
+def num_sample_paths(input, supervision, num_samples, generator=None, uniforms=None, return_states=False):
+    """``num_samples`` whole alignments a sequence drawn from a ``supervision``'s own path posterior under ``input``,
+    ``P(path | y, supervision)``: an ``io.NumSampledPaths`` named tuple ``(pdfs int32 (B, K, Tmax), scores float64 (B, K),
+    logprob float64 (B,), states int32 (B, K, Tmax + 1) or None)`` (``io.Supervision.sample_paths`` states the quantity and
+    the arguments; ``tc_supervision_sample_paths``).  Regular and end-to-end supervisions, uniform and ragged.  The random
+    numbers come from ``generator`` or are given as ``uniforms``.  Autograd is not involved; two uses:
+
+    The gradient of an alignment-level risk under the numerator -- emission delay, the number of silence frames, a duration
+    penalty: anything that is a number per alignment of the transcript -- by the fused surrogate::
+
+        paths = num_sample_paths(out, sup, 16)
+        risks = delay_of(paths.pdfs)                          # (B, K), the caller's
+        sampled_risk_surrogate(out, paths.pdfs, risks, fused=True).backward()    # grad E_num[risk]
+
+    The flat-start hand-over with the ambiguity kept: several alignments per utterance instead of ``best_path``'s one::
+
+        sups = [io.Supervision.from_alignments(w, paths.pdfs[:, k].cpu(), label_dim, den_graph=g) for k in range(K)]
+    """
+    if not isinstance(supervision, io.Supervision):
+        raise TypeError("num_sample_paths takes an io.Supervision, got %s" % type(supervision).__name__)
+    with torch.no_grad():
+        return supervision.sample_paths(input, num_samples, generator=generator, uniforms=uniforms,
+                                        return_states=return_states, workspace=_workspace)
+
+
 def _int_vector(who, name, v, n, device, dtype=torch.int32):
     """``v`` as a contiguous ``(n,)`` tensor of ``dtype`` on ``device`` (a tensor already there is not brought to the host)."""
     t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)

@@ -782,6 +782,7 @@ class DenominatorGraph:
 ArcPosteriors = collections.namedtuple("ArcPosteriors", "arcs entries leaks logprob per_seq_arcs per_seq_entries")
 NumArcPosteriors = collections.namedtuple("NumArcPosteriors", "arcs finals logprob arc_offsets state_offsets")
 SupervisionArcs = collections.namedtuple("SupervisionArcs", "seq frame src dst pdf logw")
+NumSampledPaths = collections.namedtuple("NumSampledPaths", "pdfs scores logprob states")
 
 
 def _group_rows(m, s0, n, B, T):
@@ -1249,6 +1250,84 @@ class Supervision:
         query = lib.tc_supervision_arc_posteriors_kernel if self.is_e2e else lib.tc_supervision_arc_posteriors_regular_kernel
         kernel = int(query(self.ptr))
         check(min(kernel, 0), "tc_supervision_arc_posteriors_kernel" if self.is_e2e else "tc_supervision_arc_posteriors_regular_kernel")
+        return kernel
+
+    def sample_paths(self, nnet_output, num_samples, generator=None, uniforms=None, return_states=False, workspace=None):
+        """``num_samples`` whole alignments a sequence drawn from this supervision's own path posterior under
+        ``nnet_output`` (``tc_supervision_sample_paths``): exact samples of ``P(path | y_b, supervision)`` over the paths of
+        exactly ``T_b`` arcs from the start state to a final state -- the numerator's model: no clamp, no leaky term, and
+        ``weight`` does not enter.  It is ``best_path`` with draws where that one maximises, and what
+        ``DenominatorGraph.sample_paths`` is to the denominator.  Regular and end-to-end handles, uniform and ragged, are
+        served alike.  Returns a ``NumSampledPaths`` named tuple on the input's device:
+
+        ``pdfs`` int32 ``(B, K, Tmax)``, 0-based; ``scores`` float64 ``(B, K)``, each path's log weight (``scores -
+        logprob[:, None]`` is ``log P(path | y)``); ``logprob`` float64 ``(B,)``, the numerator's ``log Z`` bit for bit;
+        ``states`` int32 ``(B, K, Tmax + 1)`` with ``return_states`` (sequence-local states ``j_0 .. j_T``), else ``None``.
+        A sequence without a path of its length gets ``logprob -inf``, one with a NaN or an infinity among the outputs it
+        reads ``NaN``; both get ``-1`` in every pdf and state slot and NaN scores, and the others keep their bits.  Padding
+        frames of a ragged handle hold ``-1``.
+
+        The random numbers are an input: ``uniforms``, float32 ``(B, K, Tmax + 1)`` in ``[0, 1)`` on the output's device
+        (``u[..., Tb]`` picks the final state, ``u[..., t]`` the arc of frame ``t``; ``include/torchain_hip.h`` states the
+        rule), or ``None`` for ``torch.rand((B, K, Tmax + 1), generator=generator, device=...)``.  A sample is a function of
+        its own uniforms: sample ``k`` does not depend on ``K`` or on the batch.  ``nnet_output`` is ``arc_posteriors``'s:
+        2-D float32 ``(T*B, C)`` and contiguous ``(B, C, T)`` float32 / bfloat16 / float16 are read where they lie.  No
+        autograd: ``functions.sampled_risk_surrogate`` turns the samples and their risks into a gradient.  The handle's
+        pool slot is not written: a ``chain_loss`` on the handle is not affected.  ``sample_paths_kernel()`` says which
+        form of the traceback runs."""
+        who = "sample_paths"
+        x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError("%s: nnet_output must be a CUDA tensor (only the HIP implementation is available)" % who)
+        S, T, P = self.n_batch, self.n_frame, self.n_pdf
+        want = (S, P, T) if x.dim() == 3 else (S * T, P)
+        if x.dim() not in (2, 3) or tuple(x.shape) != want:
+            raise ValueError("%s: nnet output of shape %s does not match the supervision (%s expected)"
+                             % (who, tuple(x.shape), want))
+        if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or int(num_samples) < 1:
+            raise ValueError("%s: num_samples must be an int >= 1, got %r" % (who, num_samples))
+        K, device = int(num_samples), x.device
+        if uniforms is not None:
+            if generator is not None:
+                raise ValueError("%s: give `uniforms` or `generator`, not both" % who)
+            if not isinstance(uniforms, torch.Tensor) or uniforms.device != device or uniforms.dtype != torch.float32:
+                raise ValueError("%s: uniforms must be a float32 tensor on the output's device (%s)" % (who, device))
+            if tuple(uniforms.shape) != (S, K, T + 1):
+                raise ValueError("%s: uniforms of shape %s are not (%d, %d, %d)" % (who, tuple(uniforms.shape), S, K, T + 1))
+        elif generator is not None and not isinstance(generator, torch.Generator):
+            raise TypeError("%s: generator must be a torch.Generator, got %s" % (who, type(generator).__name__))
+        need = int(lib.tc_supervision_sample_paths_workspace_bytes(self.ptr))  # (host arithmetic only)
+        check(min(need, 0), "tc_supervision_sample_paths_workspace_bytes")
+        dtypes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # TC_DTYPE_*
+        if x.dtype not in dtypes or (x.dim() == 2 and x.dtype != torch.float32):
+            x = x.float()
+        if (x.dim() == 3 and not x.is_contiguous()) or (x.dim() == 2 and (x.stride(1) != 1 or x.stride(0) < P)):
+            x = x.contiguous()
+        with torch.cuda.device(device):
+            cur = torch.cuda.current_stream(device).cuda_stream
+            u = uniforms.detach().contiguous() if uniforms is not None else torch.rand((S, K, T + 1), generator=generator,
+                                                                                       device=device)
+            pdfs = torch.empty((S, K, T), dtype=torch.int32, device=device)
+            scores = torch.empty((S, K), dtype=torch.float64, device=device)
+            logprob = torch.empty((S,), dtype=torch.float64, device=device)
+            states = torch.empty((S, K, T + 1), dtype=torch.int32, device=device) if return_states else None
+            ws = workspace(device, cur, need) if workspace else torch.empty(need, dtype=torch.uint8, device=device)
+            check(lib.tc_supervision_sample_paths(self.ptr, C.c_void_p(x.data_ptr()), dtypes[x.dtype], int(x.dim() == 3), S * T,
+                                                  P, x.stride(0) if x.dim() == 2 else 0, K, C.c_void_p(u.data_ptr()),
+                                                  C.c_void_p(pdfs.data_ptr()), C.c_void_p(scores.data_ptr()),
+                                                  C.c_void_p(logprob.data_ptr()),
+                                                  None if states is None else C.c_void_p(states.data_ptr()),
+                                                  C.c_void_p(ws.data_ptr()), ws.numel(), device.index, C.c_void_p(cur)),
+                  "tc_supervision_sample_paths")
+        return NumSampledPaths(pdfs, scores, logprob, states)
+
+    def sample_paths_kernel(self):
+        """Which form of the traceback ``sample_paths`` runs on this handle (``tc_supervision_sample_paths_kernel``; host
+        arithmetic only): 0 staged -- each level's log alpha and y in LDS once for all samples -- 1 streamed, from the
+        workspace and the tensor: handles whose second y buffer does not fit LDS, and every handle with
+        ``set_debug("force_num_sample_streamed", 1)``.  The two give the same bits."""
+        kernel = int(lib.tc_supervision_sample_paths_kernel(self.ptr))
+        check(min(kernel, 0), "tc_supervision_sample_paths_kernel")
         return kernel
 
     def arcs(self):
