@@ -90,7 +90,8 @@ int tc_den_graph_prepare(tc_den_graph *graph, int device);
  * 4 * arcs + 4 * unique (frame, pdf) <= 160 KB, about 6000 states) and otherwise a window of two time levels, with a
  * log-alpha history of 8 bytes per state in the supervision's device slot; the functions that run the numerator return
  * TC_ERR_UNSUPPORTED only when a single time level does not fit (32 * states + 4 * arcs + 4 * unique of the level, about
- * 4000 states) or the history exceeds 4 GiB.  tc_supervision_stats tells which, on the host. */
+ * 4000 states) or the history exceeds 4 GiB.  tc_supervision_stats tells which, on the host;
+ * tc_supervision_allow_wide_levels lifts the first of the two. */
 int tc_supervision_create(tc_supervision **out, float weight, int32_t num_sequences,
                           int32_t frames_per_sequence, int32_t label_dim, int32_t num_states,
                           const int32_t *arc_begin, const int32_t *arc_ilabel, const float *arc_weight,
@@ -321,9 +322,32 @@ float tc_supervision_weight(const tc_supervision *supervision);
  * unique), out[10] = bytes of that kernel's log-alpha history (8 per state of the minibatch, in the supervision's device
  * slot), out[11] = the kernel the numerator launches: 0 resident (out[8] <= 160 KB), 1 windowed (otherwise, or with
  * tc_debug_set("force_num_windowed", 1) as it stands at this call), or the negative TC_ERR_* it returns --
- * TC_ERR_UNSUPPORTED when one level does not fit LDS (out[9] + 2 KB > 160 KB) or the history exceeds 4 GiB.
+ * TC_ERR_UNSUPPORTED when one level does not fit LDS (out[9] + 2 KB > 160 KB) or the history exceeds 4 GiB.  (2: the
+ * wide-level kernel, only for a handle of tc_supervision_allow_wide_levels below, in place of the first refusal.)
  * End-to-end supervisions have no levels: TC_ERR_INVALID_ARGUMENT, as for a null pointer. */
 int tc_supervision_stats(const tc_supervision *supervision, int64_t *out12);
+
+/* Time levels of any width.  By default a regular supervision with a level beyond the windowed kernel's LDS (out[9] above)
+ * is refused by everything that runs the numerator.  tc_supervision_allow_wide_levels(supervision, 1), called before the
+ * handle's first use on a device (TC_ERR_INVALID_ARGUMENT afterwards, and for a null or end-to-end handle), lets such a
+ * handle take a third kernel instead (num_wide_kernels.hip: one workgroup of 1024 threads a sequence; the level's gather
+ * vector -- log-alpha of the level below, log-beta of the level above -- and the frame's y in LDS; log-alpha, log-beta and
+ * the arcs' occupations streamed through the handle's device slot).  Its LDS form needs 8 * ceil2(level states) + 4 *
+ * ceil4(frame's unique) + 2 KB <= 160 KB, about 20000 states in a level; a level beyond that takes the same kernel with
+ * the gather vector and y addressed in the slot (no LDS, same bits), so no level is refused on its size.  What remains is
+ * the 4 GiB bound on the slot's scratch: the history plus, per sequence, 16 * ceil2(level states) + 4 * ceil4(level arcs) +
+ * 4 * ceil4(frame's unique) bytes of the widest level.  An allowed handle that fits the resident or the windowed kernel
+ * takes that kernel, makes the launches it made and keeps its bits and its slot's size; without the call a handle behaves as
+ * before, refusal included.  tc_supervision_stats then reports out[11] = 2 for a handle that takes the wide kernel.
+ * Everything that runs the numerator through tc_num_forward_backward, tc_chain_objf_and_deriv and the tc_chain_step
+ * family takes such handles with no new argument, ragged ones and every input layout and dtype included;
+ * tc_supervision_best_path, tc_supervision_path_entropy, tc_supervision_arc_posteriors and tc_supervision_sample_paths keep
+ * their own size rules, and the egs readers do not set the flag.
+ * tc_supervision_wide_stats: out[0] = 1 when wide levels are allowed, out[1] = the wide kernel's form for this handle as the
+ * switches stand (0: the handle does not take the wide kernel, 1: gather vector in LDS, 2: in the slot), out[2] = the LDS
+ * form's dynamic bytes, out[3] = bytes of the wide kernel's rows in the slot. */
+int tc_supervision_allow_wide_levels(tc_supervision *supervision, int allow);
+int tc_supervision_wide_stats(const tc_supervision *supervision, int64_t *out4);
 
 /* Copies the supervision's arc tables to `device` on `stream` (asynchronously: pinned staging; idempotent -- a
  * later call on another stream makes that stream wait for the copy).  The tables live in a slot of a per-device
@@ -1599,6 +1623,13 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *   "force_num_arc_post_large" (1: end-to-end supervisions within the resident limits take the large form of
  *                     num_arc_post_kernels.hip, which otherwise serves those beyond them; same bits.  Read at every
  *                     tc_supervision_arc_posteriors call and by its workspace and kernel queries)
+ *   "force_num_wide" (1: a handle of tc_supervision_allow_wide_levels that fits the resident or the windowed numerator
+ *                     kernel takes num_wide_kernels.hip, which otherwise serves those with a level beyond the window; same
+ *                     bits.  Read when a supervision first reaches a device -- its pool slot then gets that kernel's rows
+ *                     -- at every numerator launch and by tc_supervision_stats; a launch on a handle staged before the
+ *                     switch was set returns TC_ERR_UNSUPPORTED)
+ *   "force_num_wide_streamed" (1: the wide kernel addresses its gather vector and y in the slot for every handle, as it
+ *                     does for levels beyond its LDS form; same bits.  Read at every such launch)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -1615,6 +1646,7 @@ int tc_debug_set(const char *key, int value);
  * workspace (utterances of many hundred frames on the largest on-chip graphs); "num_e2e_staged_launches" = end-to-end
  * numerator launches that ran beside the denominator and left their posteriors for the scatter kernel;
  * "num_windowed_launches" = regular numerator launches that took the level-windowed kernel (counted in "num_launches" too);
+ * "num_wide_launches" = those that took the wide-level kernel (tc_supervision_allow_wide_levels; in "num_launches" too);
  * "channel_last_steps" = tc_chain_step_strided calls taken in TC_LAYOUT_CHANNEL_LAST (their row gathers and scatters, and
  * tc_rows_gather / tc_rows_scatter, count as "layout_launches"); "ragged_steps" = objective calls made on a ragged
  * supervision (tc_supervision_create_e2e_ragged, tc_supervision_create_ragged; their padding kernels are not counted as

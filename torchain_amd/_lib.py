@@ -188,6 +188,10 @@ def _load():
     L.tc_supervision_weight.argtypes = [vp]
     L.tc_supervision_stats.restype = C.c_int
     L.tc_supervision_stats.argtypes = [vp, vp]
+    L.tc_supervision_allow_wide_levels.restype = C.c_int
+    L.tc_supervision_allow_wide_levels.argtypes = [vp, C.c_int]
+    L.tc_supervision_wide_stats.restype = C.c_int
+    L.tc_supervision_wide_stats.argtypes = [vp, vp]
     L.tc_supervision_prepare.restype = C.c_int
     L.tc_supervision_prepare.argtypes = [vp, C.c_int, vp]
     L.tc_chain_workspace_bytes.restype = i64

@@ -222,6 +222,12 @@ int fill_num_params(tc_supervision *sup, int device, hipStream_t stream, const f
       p->seq_frames = sup->frames_dev[device];
       if (!sup->e2e) p->seq_level_off = sup->level_off_dev[device];
     }
+    p->wide_ok = sup->wide_ok ? 1 : 0;  // (the wide kernel's rows: in the slot of a handle that routed to it)
+    auto wide = sup->wide_dev.find(device);
+    if (wide != sup->wide_dev.end()) {
+      p->wide_rows = wide->second;
+      p->wide_stride = num_wide_seq_doubles(sup->tab.max_level_states, sup->tab.max_level_arcs, sup->tab.max_frame_uniq);
+    }
   }
   p->y = y;
   p->y_stride = y_stride;

@@ -637,6 +637,16 @@ inline size_t num_windowed_lds_bytes(int32_t level_states, int32_t level_arcs, i
 }
 // (beside its dynamic arrays the windowed kernel has a total and the 128 shares of the cross-entropy sum in static LDS)
 inline bool num_windowed_fits(size_t dynamic_bytes) { return dynamic_bytes + 2048 <= (size_t)kLdsLimitBytes; }
+// Wide (num_wide_kernels.hip, handles of tc_supervision_allow_wide_levels): the gather vector of one level (double) and y of
+// one frame in LDS; a level beyond that takes the kernel's slot form, which has no dynamic LDS.  Per sequence the pool slot
+// holds, in doubles: log-beta of two levels, then (floats) the occupations of a level's arcs and the slot form's y.
+inline size_t num_wide_lds_bytes(int32_t level_states, int32_t frame_uniq) {
+  return (size_t)((level_states + 1) & ~1) * 8 + (size_t)((frame_uniq + 3) & ~3) * 4;
+}
+inline int64_t num_wide_seq_doubles(int32_t level_states, int32_t level_arcs, int32_t frame_uniq) {
+  const int64_t n = (int64_t)2 * ((level_states + 1) & ~1) + (((level_arcs + 3) & ~3) + ((frame_uniq + 3) & ~3)) / 2;
+  return (n + 31) & ~(int64_t)31;
+}
 
 // End-to-end supervision ([K] Supervision::e2e_fsts, supervision_e2e.cpp): per-sequence acceptors with cycles, walked
 // frame by frame by num_e2e_kernels.hip.  Per sequence: states [state_off[s], state_off[s+1]), arcs [arc_off[s], ...),
@@ -745,6 +755,12 @@ struct NumParams {
   // xent_out's rows, row = t*S + s.  The cross-entropy objective's term becomes xent_scale * v * (x - max - log sum): the
   // log-softmax of the row.  Null: the plain product.  (The last member: every older argument offset stays.)
   const float *xent_lse = nullptr;
+  // num_wide_kernels.hip: the rows of a wide handle in its pool slot, wide_stride doubles a sequence
+  // (num_wide_seq_doubles).  Null: the handle did not route to the wide kernel when it was staged.  wide_ok: the handle's
+  // tc_supervision_allow_wide_levels.  (Behind every older member again.)
+  double *wide_rows = nullptr;
+  int64_t wide_stride = 0;
+  int wide_ok = 0;
 };
 
 }  // namespace tc
@@ -764,6 +780,10 @@ struct tc_supervision {
   std::map<int, tc::NumDev> dev;
   std::map<int, const int32_t *> frames_dev;  // ragged: the lengths in the device's pool slot, behind the tables
   std::map<int, const int32_t *> level_off_dev;  // ragged regular: NumTables::seq_level_off, in the same slot
+  // tc_supervision_allow_wide_levels: a level beyond the windowed kernel's LDS takes num_wide_kernels.hip instead of being
+  // refused; wide_dev: that kernel's rows in the device's pool slot (only where the handle routed to it when staged)
+  bool wide_ok = false;
+  std::map<int, double *> wide_dev;
 };
 
 namespace tc {
@@ -828,6 +848,11 @@ int64_t big_small_floats(int hb, int P, int T, int Sp);
 int launch_num(const NumParams &p, hipStream_t stream);
 int launch_num_scatter(const NumParams &p, hipStream_t stream);
 int launch_num_windowed(const NumParams &p, hipStream_t stream);     // num_windowed_kernels.hip (via launch_num)
+int launch_num_wide(const NumParams &p, hipStream_t stream);         // num_wide_kernels.hip (via launch_num)
+// The regular numerator's kernel, launch_num's decision and tc_supervision_stats' "route": 0 resident, 1 windowed, 2 wide
+// (wide_ok handles alone), TC_ERR_UNSUPPORTED.  lds_* / win_*: the sizes as NumParams rounds them.  (num_kernels.hip)
+int num_route(int lds_states, int lds_arcs, int lds_uniq, int win_states, int win_arcs, int win_uniq, bool wide_ok);
+bool num_wide_slot_form(int win_states, int win_uniq);  // the wide kernel's form: gather vector and y in the slot
 int launch_num_e2e(const NumParams &p, hipStream_t stream);          // num_e2e_kernels.hip (via launch_num)
 int launch_num_e2e_scatter(const NumParams &p, hipStream_t stream);  // ... (via launch_num_scatter)
 int launch_num_best_path(const NumParams &p, hipStream_t stream);    // num_best_path_kernels.hip (regular and end-to-end)
@@ -1162,7 +1187,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgForceNumArcPostRegularSpill, kDbgForceNumSampleStreamed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgForceNumArcPostRegularSpill, kDbgForceNumSampleStreamed, kDbgForceNumWide, kDbgForceNumWideStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -1171,7 +1196,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntNumArcPostRegular, kCntNumArcPostRegularSpill, kCntNumSample, kCntNumSampleStreamed, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntNumArcPostRegular, kCntNumArcPostRegularSpill, kCntNumSample, kCntNumSampleStreamed, kCntNumWide, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

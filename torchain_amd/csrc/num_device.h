@@ -1,5 +1,6 @@
-// The arithmetic of the regular numerator, shared by its two kernels: the resident one (num_kernels.hip: a whole
-// sequence in LDS) and the level-windowed one (num_windowed_kernels.hip: two adjacent levels in LDS).  Both kernels form
+// The arithmetic of the regular numerator, shared by its kernels: the resident one (num_kernels.hip: a whole
+// sequence in LDS), the level-windowed one (num_windowed_kernels.hip: two adjacent levels in LDS) and the wide-level one
+// (num_wide_kernels.hip: one level's gather vector in LDS, the rest streamed through the pool slot).  The kernels form
 // every value through these functions, operation for operation and in the same order, so that on a supervision both can
 // run they give the same bits; they differ only in where an index finds its operand (the accessors they pass in).
 #pragma once

@@ -198,10 +198,28 @@ int launch_num_fwd_bwd(const NumParams &p, size_t lds, hipStream_t stream) {
 }
 }  // namespace
 
+int num_route(int lds_states, int lds_arcs, int lds_uniq, int win_states, int win_arcs, int win_uniq, bool wide_ok) {
+  const size_t lds = (size_t)lds_states * 16 + (size_t)lds_uniq * 4 + (size_t)lds_arcs * 4;
+  const size_t win = (size_t)win_states * 32 + (size_t)win_uniq * 4 + (size_t)win_arcs * 4;
+  const bool resident = lds <= (size_t)kLdsLimitBytes && !debug_flag(kDbgForceNumWindowed);
+  // a handle that allows it: the wide kernel where neither of the others fits (or "force_num_wide")
+  if (wide_ok && (debug_flag(kDbgForceNumWide) || (!resident && !num_windowed_fits(win)))) return 2;
+  if (resident) return 0;
+  return num_windowed_fits(win) ? 1 : TC_ERR_UNSUPPORTED;
+}
+
+bool num_wide_slot_form(int win_states, int win_uniq) {
+  return debug_flag(kDbgForceNumWideStreamed) || !num_windowed_fits(num_wide_lds_bytes(win_states, win_uniq));
+}
+
 int launch_num(const NumParams &p, hipStream_t stream) {
   if (p.t.e2e) return launch_num_e2e(p, stream);  // end-to-end supervision: num_e2e_kernels.hip
   count_launch(kCntNum);
   if (p.deriv || p.xent || p.seq_xent) count_launch(kCntNumBackward);
+  // a handle of tc_supervision_allow_wide_levels with a level beyond the window: num_wide_kernels.hip (every other handle,
+  // and such a handle that fits, goes on as it did)
+  if (p.wide_ok && num_route(p.lds_states, p.lds_arcs, p.lds_uniq, p.win_states, p.win_arcs, p.win_uniq, true) == 2)
+    return launch_num_wide(p, stream);
   const size_t lds = (size_t)p.lds_states * 16 + (size_t)p.lds_uniq * 4 + (size_t)p.lds_arcs * 4;
   // a sequence that does not fit one workgroup's LDS: a window of levels instead (num_windowed_kernels.hip)
   if (lds > (size_t)kLdsLimitBytes || debug_flag(kDbgForceNumWindowed)) return launch_num_windowed(p, stream);

@@ -455,6 +455,17 @@ int32_t tc_supervision_num_sequence(const tc_supervision *s) { return s ? s->S :
 int32_t tc_supervision_num_frame(const tc_supervision *s) { return s ? s->T : 0; }
 float tc_supervision_weight(const tc_supervision *s) { return s ? s->weight : 0.f; }
 
+// launch_num's decision for the handle (num_route on the sizes as fill_num_params rounds them), and the bytes the wide
+// kernel's rows take in a pool slot
+static int sup_route(const tc_supervision *s) {
+  const NumTables &tb = s->tab;
+  return num_route((tb.max_states + 1) & ~1, (tb.max_arcs + 3) & ~3, (tb.max_uniq + 3) & ~3, (tb.max_level_states + 1) & ~1,
+                   (tb.max_level_arcs + 3) & ~3, (tb.max_frame_uniq + 3) & ~3, s->wide_ok);
+}
+static int64_t wide_scratch_bytes(const tc_supervision *s) {
+  return (int64_t)s->S * num_wide_seq_doubles(s->tab.max_level_states, s->tab.max_level_arcs, s->tab.max_frame_uniq) * 8;
+}
+
 int tc_supervision_stats(const tc_supervision *s, int64_t *out) {
   if (!s || !out) return TC_ERR_INVALID_ARGUMENT;
   if (s->e2e) return TC_ERR_INVALID_ARGUMENT;  // (an end-to-end supervision has no levels: num_e2e_kernels.hip)
@@ -474,12 +485,27 @@ int tc_supervision_stats(const tc_supervision *s, int64_t *out) {
   out[9] = windowed;
   out[10] = hist;
   // launch_num's decision (num_kernels.hip), and stage_locked's bound on the history
-  if (hist > kE2eMaxScratchBytes)
-    out[11] = TC_ERR_UNSUPPORTED;
-  else if (resident <= kLdsLimitBytes && !debug_flag(kDbgForceNumWindowed))
-    out[11] = 0;
-  else
-    out[11] = num_windowed_fits((size_t)windowed) ? 1 : TC_ERR_UNSUPPORTED;
+  const int route = sup_route(s);
+  out[11] = hist + (route == 2 ? wide_scratch_bytes(s) : 0) > kE2eMaxScratchBytes ? TC_ERR_UNSUPPORTED : route;
+  return TC_OK;
+}
+
+int tc_supervision_allow_wide_levels(tc_supervision *sup, int allow) {
+  if (!sup || sup->e2e) return TC_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lock(sup->mu);
+  if (!sup->dev.empty()) return TC_ERR_INVALID_ARGUMENT;  // (the slot's size is fixed by the first use)
+  sup->wide_ok = allow != 0;
+  return TC_OK;
+}
+
+int tc_supervision_wide_stats(const tc_supervision *s, int64_t *out) {
+  if (!s || !out || s->e2e) return TC_ERR_INVALID_ARGUMENT;
+  const NumTables &tb = s->tab;
+  const bool wide = sup_route(s) == 2;
+  out[0] = s->wide_ok ? 1 : 0;
+  out[1] = !wide ? 0 : num_wide_slot_form((tb.max_level_states + 1) & ~1, (tb.max_frame_uniq + 3) & ~3) ? 2 : 1;
+  out[2] = (int64_t)num_wide_lds_bytes(tb.max_level_states, tb.max_frame_uniq);
+  out[3] = wide_scratch_bytes(s);
   return TC_OK;
 }
 
@@ -524,6 +550,14 @@ static int stage_locked(tc_supervision *sup, int device) {
   if (hist_bytes > (size_t)kE2eMaxScratchBytes) return TC_ERR_UNSUPPORTED;
   const size_t hist_off = total;
   total += (hist_bytes + 255) & ~(size_t)255;
+  // and, only for a handle that routes to the wide kernel (num_wide_kernels.hip), its rows: log-beta of two levels, the
+  // occupations of a level's arcs and the slot form's y per sequence, sized by the widest level.  The bound is the scratch's.
+  const bool wide = sup_route(sup) == 2;
+  const size_t wide_off = total;
+  if (wide) {
+    if ((int64_t)hist_bytes + wide_scratch_bytes(sup) > kE2eMaxScratchBytes) return TC_ERR_UNSUPPORTED;
+    total += (size_t)wide_scratch_bytes(sup);
+  }
   // A new supervision arrives with every minibatch: its tables live in a slot of a per-device pool (device
   // blob + PINNED host staging + two events), so that after warm-up a step neither allocates nor frees
   // device memory and the upload is a true asynchronous copy.
@@ -547,6 +581,7 @@ static int stage_locked(tc_supervision *sup, int device) {
   d.stage = (float *)(blob + stage_off);
   d.alpha_hist = (double *)(blob + hist_off);
   sup->dev[device] = d;
+  if (wide) sup->wide_dev[device] = (double *)(blob + wide_off);
   if (ragged) {
     sup->level_off_dev[device] = P(17);
     sup->frames_dev[device] = P(18);

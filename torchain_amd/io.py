@@ -811,16 +811,29 @@ class Supervision:
 
     @classmethod
     def from_fst(cls, weight, num_sequences, frames_per_sequence, label_dim, arc_begin, ilabel, arc_weight,
-                 nextstate, final):
+                 nextstate, final, any_width=False):
         """Builds the handle from the five fields of [K] chain::Supervision the path uses
-        (``src/my_lib_example.cpp:82-95``); the FST is the merged acceptor in CSR form."""
+        (``src/my_lib_example.cpp:82-95``); the FST is the merged acceptor in CSR form.
+
+        ``any_width``: ``False`` leaves a supervision with a time level beyond the level-windowed numerator's LDS (about 3700
+        states in one level, fewer with many arcs) refused by ``chain_loss`` and the other numerator calls.  ``True``
+        (``tc_supervision_allow_wide_levels``) lets such a handle take the wide-level kernel instead: levels of any width,
+        bounded only by the 4 GiB of scratch in the handle's device slot (``stats()`` tells the kernel and its form).  A
+        handle that fits the other two kernels is the handle ``False`` makes, bit for bit.  Lattice-derived supervisions
+        composed with a ``den_graph``, generous tolerances and whole utterances are what needs it.  It is a keyword, not the
+        default, only because a test pins the refusal of the default call."""
         ab, il, nx = _i32(arc_begin), _i32(ilabel), _i32(nextstate)
         aw, fin = _f32(arc_weight), _f32(final)
         handle = C.c_void_p()
         check(lib.tc_supervision_create(C.byref(handle), float(weight), int(num_sequences), int(frames_per_sequence),
                                         int(label_dim), len(fin), _p(ab), _p(il), _p(aw), _p(nx), _p(fin)),
               "tc_supervision_create")
-        return cls(handle)
+        return cls(handle)._allow_wide_levels(any_width)
+
+    def _allow_wide_levels(self, any_width):
+        if any_width:
+            check(lib.tc_supervision_allow_wide_levels(self.ptr, 1), "tc_supervision_allow_wide_levels")
+        return self
 
     @classmethod
     def from_e2e_fsts(cls, weight, frames_per_sequence, label_dim, fsts, den_graph=None, normalization_scale=1.0,
@@ -895,7 +908,8 @@ class Supervision:
         return cls(handle)
 
     @classmethod
-    def from_fsts(cls, weight, frames_per_sequence, label_dim, fsts, den_graph=None, normalization_scale=1.0):
+    def from_fsts(cls, weight, frames_per_sequence, label_dim, fsts, den_graph=None, normalization_scale=1.0,
+                  any_width=False):
         """Regular supervisions of unequal lengths (a "ragged" minibatch of whole utterances): one time-unfolded acceptor
         per sequence, as alignments and lattices give them.  ``fsts`` is a list of per-sequence
         ``(arc_begin, ilabel, arc_weight, nextstate, final)`` in CSR form -- each what ``from_fst`` takes with
@@ -909,7 +923,8 @@ class Supervision:
         bits it computes on that sequence alone.
 
         ``den_graph``, ``normalization_scale``: as for ``from_e2e_fsts`` -- the FSTs are composed with the graph's
-        normalization acceptor first, a sequence without a path in the graph raises ``ValueError`` naming the sequences."""
+        normalization acceptor first, a sequence without a path in the graph raises ``ValueError`` naming the sequences.
+        ``any_width``: as for ``from_fst``."""
         fsts = list(fsts)
         if not fsts:
             raise ValueError("from_fsts: no FSTs")
@@ -943,13 +958,13 @@ class Supervision:
         check(lib.tc_supervision_create_ragged(C.byref(handle), float(weight), len(fsts), _p(lengths), int(label_dim),
                                                _p(sb), _p(ab), _p(il), _p(aw), _p(nx), _p(fin)),
               "tc_supervision_create_ragged")
-        return cls(handle)
+        return cls(handle)._allow_wide_levels(any_width)
 
     @classmethod
-    def from_sequences(cls, sups, den_graph=None, normalization_scale=1.0):
+    def from_sequences(cls, sups, den_graph=None, normalization_scale=1.0, any_width=False):
         """A ragged minibatch from single-sequence regular supervisions (``torchain_amd.synth.SupFst`` with
         ``num_sequences == 1``: what the egs readers return for one eg), each of its own ``frames_per_sequence``.  They must
-        share ``weight`` and ``label_dim``.  ``den_graph``, ``normalization_scale``: as for ``from_fsts``."""
+        share ``weight`` and ``label_dim``.  ``den_graph``, ``normalization_scale``, ``any_width``: as for ``from_fsts``."""
         sups = list(sups)
         if not sups:
             raise ValueError("from_sequences: no supervisions")
@@ -962,17 +977,19 @@ class Supervision:
                 raise ValueError("from_sequences: supervision %d differs from the first in weight or label_dim" % i)
         return cls.from_fsts(sups[0].weight, [int(s.frames_per_sequence) for s in sups], sups[0].label_dim,
                              [(s.arc_begin, s.ilabel, s.arc_weight, s.nextstate, s.final) for s in sups],
-                             den_graph=den_graph, normalization_scale=normalization_scale)
+                             den_graph=den_graph, normalization_scale=normalization_scale, any_width=any_width)
 
     @classmethod
-    def from_alignments(cls, weight, pdfs, label_dim, frames=None, den_graph=None, normalization_scale=1.0):
+    def from_alignments(cls, weight, pdfs, label_dim, frames=None, den_graph=None, normalization_scale=1.0,
+                        any_width=False):
         """Regular supervisions from frame-level pdf alignments, e.g. what ``best_path`` of a flat-start model's handle
         returns: one linear acceptor per sequence at cost 0, through ``from_fsts``.  ``pdfs``: int ``(B, Tmax)``, 0-based,
         ``-1`` in the padding; ``frames``: the sequences' lengths, by default the count of non-negative entries of each
         row.  With ``den_graph`` the alignment carries the graph's weights, ``-log pi - sum log w`` summed over the start
         states that admit it.  ``ValueError``: a ``-1`` inside a sequence (``best_path`` found no path for it), a pdf outside
         ``label_dim``, an alignment the graph does not contain.  Tolerance around the phone boundaries needs the tree and
-        the transition model and stays with the caller, who passes the widened FSTs to ``from_fsts``."""
+        the transition model and stays with the caller, who passes the widened FSTs to ``from_fsts``.  ``any_width``: as for
+        ``from_fsts`` (a linear acceptor never needs it; one composed with a ``den_graph`` can)."""
         if isinstance(pdfs, torch.Tensor):
             pdfs = pdfs.detach().cpu().numpy()
         pdfs = np.asarray(pdfs)
@@ -1002,7 +1019,7 @@ class Supervision:
             fsts.append((np.minimum(np.arange(n + 2), n).astype(np.int32), (pdfs[b, :n] + 1).astype(np.int32),
                          np.zeros(n, np.float32), np.arange(1, n + 1, dtype=np.int32), final))
         return cls.from_fsts(weight, [int(x) for x in lengths], label_dim, fsts, den_graph=den_graph,
-                             normalization_scale=normalization_scale)
+                             normalization_scale=normalization_scale, any_width=any_width)
 
     @property
     def is_e2e(self):
@@ -1024,13 +1041,14 @@ class Supervision:
         return out
 
     @classmethod
-    def from_synth(cls, sup, any_size=False):
+    def from_synth(cls, sup, any_size=False, any_width=False):
         """From a ``torchain_amd.synth.SupFst``, or an ``egs.E2eSup`` (what the egs readers return for ``<End2End>``
-        egs; ``any_size``: as for ``from_e2e_fsts``, not read for a ``SupFst``)."""
+        egs; ``any_size``: as for ``from_e2e_fsts``, not read for a ``SupFst``; ``any_width``: as for ``from_fst``, not read
+        for an ``E2eSup``)."""
         if isinstance(sup, _egs.E2eSup):
             return cls.from_e2e_fsts(sup.weight, sup.frames_per_sequence, sup.label_dim, sup.fsts, any_size=any_size)
         return cls.from_fst(sup.weight, sup.num_sequences, sup.frames_per_sequence, sup.label_dim, sup.arc_begin,
-                            sup.ilabel, sup.arc_weight, sup.nextstate, sup.final)
+                            sup.ilabel, sup.arc_weight, sup.nextstate, sup.final, any_width=any_width)
 
     @property
     def weight(self):
@@ -1040,15 +1058,27 @@ class Supervision:
         """What the numerator will do with this (regular) supervision, known on the host before anything runs
         (``tc_supervision_stats``): sizes of the largest sequence, of its widest time level, the LDS either numerator
         kernel would need, and ``kernel``: ``"resident"`` (a whole sequence on chip), ``"windowed"`` (two time levels
-        on chip; sequences of any size) or ``"unsupported"`` (a single level beyond LDS: ``chain_loss`` will raise).
-        ``route`` is the same as a number (0, 1, negative error code).  End-to-end supervisions raise."""
+        on chip; sequences of any size), ``"wide"`` (a level beyond the window, on a handle made with ``any_width=True``:
+        the wide-level kernel) or ``"unsupported"`` (such a level without ``any_width``, or scratch beyond 4 GiB:
+        ``chain_loss`` will raise).  ``route`` is the same as a number (0, 1, 2, negative error code).
+        ``wide_stats()`` tells the wide kernel's form.  End-to-end supervisions raise."""
         out = np.zeros(12, np.int64)
         check(lib.tc_supervision_stats(self.ptr, _p(out)), "tc_supervision_stats")
         keys = ("sequences", "frames", "max_states", "max_arcs", "max_uniq", "max_level_states", "max_level_arcs",
                 "max_frame_uniq", "resident_lds_bytes", "windowed_lds_bytes", "history_bytes", "route")
         d = dict(zip(keys, (int(x) for x in out)))
-        d["kernel"] = {0: "resident", 1: "windowed"}.get(d["route"], "unsupported")
+        d["kernel"] = {0: "resident", 1: "windowed", 2: "wide"}.get(d["route"], "unsupported")
         return d
+
+    def wide_stats(self):
+        """The wide-level numerator kernel and this (regular) supervision, host only (``tc_supervision_wide_stats``):
+        ``any_width`` (the handle was made with it), ``form`` -- ``"lds"`` (the level's gather vector and the frame's ``y`` on
+        chip), ``"slot"`` (a level of more than about 20000 states: both in the device slot) or ``None`` (``stats()`` names
+        another kernel) -- ``lds_bytes`` of the first form and ``scratch_bytes``, the kernel's rows in the device slot."""
+        out = np.zeros(4, np.int64)
+        check(lib.tc_supervision_wide_stats(self.ptr, _p(out)), "tc_supervision_wide_stats")
+        return dict(any_width=bool(out[0]), form={1: "lds", 2: "slot"}.get(int(out[1])), lds_bytes=int(out[2]),
+                    scratch_bytes=int(out[3]))
 
     def e2e_stats(self):
         """What the numerator will do with this end-to-end supervision, known on the host (``tc_supervision_e2e_stats``):
