@@ -1194,10 +1194,30 @@ int tc_supervision_path_entropy(tc_supervision *supervision, const void *nnet_ou
  * (tc_supervision_stats: max_level_states, max_frame_uniq, max_level_arcs):
  *     48 * ceil2(L) + 4 * ceil4(U) + 4 * ceil4(A) + 2048 <= 163840,
  * the same for a value-only call.  TC_ERR_UNSUPPORTED, before any launch (the workspace query returns it too): a handle
- * beyond the rule; an end-to-end handle (tc_supervision_path_entropy is theirs).  TC_ERR_INVALID_ARGUMENT and TC_ERR_WORKSPACE
- * as tc_supervision_path_entropy.  Asynchronous on `stream`, no allocation once the supervision is staged, no host
- * synchronisation.  tc_debug_counter("num_entropy_regular_launches") counts the launches. */
+ * beyond the rule that does not allow wide levels; an end-to-end handle (tc_supervision_path_entropy is theirs).
+ * TC_ERR_INVALID_ARGUMENT and TC_ERR_WORKSPACE as tc_supervision_path_entropy.  Asynchronous on `stream`, no allocation once
+ * the supervision is staged, no host synchronisation.  tc_debug_counter("num_entropy_regular_launches") counts the launches.
+ *
+ * Levels of any width (num_entropy_wide_kernels.hip).  A handle of tc_supervision_allow_wide_levels that breaks the rule above
+ * is not refused: it takes the wide-level kernel, as does every regular handle under tc_debug_set("force_num_entropy_wide", 1).
+ * One workgroup of 1024 threads a sequence walks the levels as the wide-level numerator does; LDS holds one level's gather
+ * vector of pairs -- (log alpha, Abar) forward, (log beta, Bbar) backward -- and the frame's y, the rest streams through the
+ * workspace.  Same device functions, same operands, same orders: where both kernels serve a handle they give the same bits in
+ * all three outputs, and every statement above holds for both.  Two forms:
+ *   LDS form  : 16 * ceil2(L) + 4 * ceil4(U) + 2048 <= 163840 (about 10000 states a level);
+ *   slot form : a level beyond that, or "force_num_entropy_wide_streamed": the gather vector and y are addressed in the
+ *               workspace, no dynamic LDS, the LDS form's bits.  No level is refused on its width.
+ *   workspace : POSITIVE FOR THE VALUE ALONE on this route.  With a gradient the history, 16 bytes a state of the handle rounded up
+ *               to 256; then per sequence, rounded up to 256 bytes: two rows of 16 * ceil2(L) bytes (log beta, Bbar; for the
+ *               value alone log alpha, Abar -- no history is kept), with a gradient 4 * ceil4(A) bytes of arc terms, and
+ *               4 * ceil4(U) bytes of y for the slot form.  The only size bound left is that this count fits 64 bits.
+ * tc_supervision_path_entropy_regular_kernel says which kernel a handle takes as the switches stand at the call, from host
+ * arithmetic alone: 0 the level-windowed kernel, 1 the wide-level kernel's LDS form, 2 its slot form; TC_ERR_UNSUPPORTED for a
+ * handle the entry refuses (an end-to-end one included), TC_ERR_INVALID_ARGUMENT for null.
+ * tc_debug_counter("num_entropy_wide_launches") counts the wide-level kernel's launches ("num_entropy_regular_launches" does
+ * not move for them). */
 int64_t tc_supervision_path_entropy_regular_workspace_bytes(const tc_supervision *supervision, int32_t with_grad);
+int tc_supervision_path_entropy_regular_kernel(const tc_supervision *supervision);
 int tc_supervision_path_entropy_regular(tc_supervision *supervision, const void *nnet_output, int dtype, int layout_bct,
                                         int64_t num_rows, int32_t num_cols, int64_t row_stride, double *entropy_dev /* [S] */,
                                         double *logprob_dev /* [S] */, void *grad /* nullable */, int64_t grad_stride,
@@ -1630,6 +1650,11 @@ int tc_rows_scatter(const float *in2d, int64_t in_stride, int dtype, int32_t B, 
  *                     switch was set returns TC_ERR_UNSUPPORTED)
  *   "force_num_wide_streamed" (1: the wide kernel addresses its gather vector and y in the slot for every handle, as it
  *                     does for levels beyond its LDS form; same bits.  Read at every such launch)
+ *   "force_num_entropy_wide" (1: every regular handle, whether it allows wide levels or not, takes num_entropy_wide_kernels.hip
+ *                     in tc_supervision_path_entropy_regular, which otherwise serves only handles of
+ *                     tc_supervision_allow_wide_levels beyond the level-windowed entropy kernel's rule; same bits.  Read at
+ *                     every call of the entry and by its workspace and kernel queries)
+ *   "force_num_entropy_wide_streamed" (1: that kernel takes its slot form whatever the widest level; same bits.  Read with it)
  * Read when a graph first reaches a device (tc_den_graph_prepare, see tc_den_graph_tuning):
  *   "no_pair"        (1: never the two-sequence kernel)        "no_tune" (1: no timing launches; the fused kernel)
  * The same switches can be set from the environment when the library is loaded:
@@ -1677,7 +1702,8 @@ int tc_debug_set(const char *key, int value);
  * "den_entropy_streamed_launches" those of them that kept the per-frame vectors in the workspace;
  * "num_entropy_launches" = tc_supervision_path_entropy calls that launched the resident kernel (not counted in
  * "num_launches"), "num_entropy_large_launches" = those that launched num_entropy_large_kernels.hip (counted in neither), and
- * "num_entropy_regular_launches" = those of tc_supervision_path_entropy_regular;
+ * "num_entropy_regular_launches" = those of tc_supervision_path_entropy_regular that launched the level-windowed kernel,
+ * "num_entropy_wide_launches" = those of it that launched num_entropy_wide_kernels.hip;
  * "num_arc_post_launches" = tc_supervision_arc_posteriors calls that launched the resident form of num_arc_post_kernels.hip,
  * "num_arc_post_large_launches" = those that launched its large form (neither counted in "num_launches").
  * -1 for an unknown key. */

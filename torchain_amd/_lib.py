@@ -221,6 +221,8 @@ def _load():
     L.tc_supervision_path_entropy.argtypes = [vp, vp, C.c_int, C.c_int, i64, i32, i64, vp, vp, vp, i64, vp, vp, i64, C.c_int, vp]
     L.tc_supervision_path_entropy_regular_workspace_bytes.restype = i64
     L.tc_supervision_path_entropy_regular_workspace_bytes.argtypes = [vp, i32]
+    L.tc_supervision_path_entropy_regular_kernel.restype = C.c_int
+    L.tc_supervision_path_entropy_regular_kernel.argtypes = [vp]
     L.tc_supervision_path_entropy_regular.restype = C.c_int
     L.tc_supervision_path_entropy_regular.argtypes = L.tc_supervision_path_entropy.argtypes
     L.tc_supervision_arc_posteriors_workspace_bytes.restype = i64

@@ -613,19 +613,35 @@ int tc_supervision_path_entropy(tc_supervision *sup, const void *y, int dtype, i
   return supervision_mark_use(sup, device, stream);
 }
 
-// tc_supervision_path_entropy_regular's size rule (num_entropy_regular_kernels.hip): regular handles whose widest level
-// keeps three pairs of doubles a state, the frame's y and the terms of the arcs leaving it in LDS
-static int num_entropy_regular_rule(const tc_supervision *sup) {
+// tc_supervision_path_entropy_regular's kernel, per handle (as the switches stand at the call): 0 the level-windowed kernel
+// (num_entropy_regular_kernels.hip), for handles whose widest level keeps three pairs of doubles a state, the frame's y and the
+// terms of the arcs leaving it in LDS; 1 / 2 the wide-level kernel (num_entropy_wide_kernels.hip) in its LDS / slot form, for a
+// handle of tc_supervision_allow_wide_levels beyond that rule, or under "force_num_entropy_wide"; TC_ERR_UNSUPPORTED otherwise.
+static int num_entropy_regular_route(const tc_supervision *sup) {
   if (sup->e2e) return TC_ERR_UNSUPPORTED;
   const NumTables &tb = sup->tab;
-  return num_ent_regular_fits(tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq) ? TC_OK : TC_ERR_UNSUPPORTED;
+  const bool fits = num_ent_regular_fits(tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq);
+  if (!debug_flag(kDbgForceNumEntropyWide) && (fits || !sup->wide_ok)) return fits ? 0 : TC_ERR_UNSUPPORTED;
+  const bool slot = debug_flag(kDbgForceNumEntropyWideStreamed) || !num_ent_wide_lds_fits(tb.max_level_states, tb.max_frame_uniq);
+  return slot ? 2 : 1;
+}
+
+static int64_t num_entropy_regular_need(const tc_supervision *sup, int route, bool grad) {
+  const NumTables &tb = sup->tab;
+  const int64_t total_states = tb.seq_state_off[sup->S];
+  if (route == 0) return num_ent_regular_workspace_bytes(total_states, grad);
+  return num_ent_wide_workspace_bytes(total_states, sup->S, tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq, grad);
+}
+
+int tc_supervision_path_entropy_regular_kernel(const tc_supervision *sup) {
+  return sup ? num_entropy_regular_route(sup) : TC_ERR_INVALID_ARGUMENT;
 }
 
 int64_t tc_supervision_path_entropy_regular_workspace_bytes(const tc_supervision *sup, int32_t with_grad) {
   if (!sup) return TC_ERR_INVALID_ARGUMENT;
-  const int rc = num_entropy_regular_rule(sup);
-  if (rc != TC_OK) return rc;
-  return num_ent_regular_workspace_bytes(sup->tab.seq_state_off[sup->S], with_grad != 0);
+  const int route = num_entropy_regular_route(sup);
+  if (route < 0) return route;
+  return num_entropy_regular_need(sup, route, with_grad != 0);
 }
 
 int tc_supervision_path_entropy_regular(tc_supervision *sup, const void *y, int dtype, int layout_bct, int64_t rows,
@@ -636,9 +652,9 @@ int tc_supervision_path_entropy_regular(tc_supervision *sup, const void *y, int 
   int rc = path_entropy_args(sup, y, dtype, layout_bct, rows, cols, y_stride, entropy_dev, logprob_dev, grad, grad_stride,
                              grad_output_dev);
   if (rc != TC_OK) return rc;
-  rc = num_entropy_regular_rule(sup);
-  if (rc != TC_OK) return rc;
-  const int64_t need = num_ent_regular_workspace_bytes(sup->tab.seq_state_off[sup->S], grad != nullptr);
+  const int route = num_entropy_regular_route(sup);
+  if (route < 0) return route;
+  const int64_t need = num_entropy_regular_need(sup, route, grad != nullptr);
   if (need > 0 && (!workspace || need > workspace_bytes || !aligned16(workspace))) return TC_ERR_WORKSPACE;
   DeviceGuard guard(device);
   if (!guard.ok) return TC_ERR_HIP;
@@ -659,7 +675,14 @@ int tc_supervision_path_entropy_regular(tc_supervision *sup, const void *y, int 
   p.terms = nullptr;
   p.terms_in_lds = 1;
   p.means = nullptr;
-  rc = launch_num_entropy_regular(p, stream);
+  if (route == 0) {
+    rc = launch_num_entropy_regular(p, stream);
+  } else {  // the wide kernel's rows lie in the workspace behind the history, never in the pool slot
+    const NumTables &tb = sup->tab;
+    p.n.wide_rows = (double *)((char *)workspace + num_ent_regular_workspace_bytes(tb.seq_state_off[sup->S], grad != nullptr));
+    p.n.wide_stride = num_ent_wide_seq_doubles(tb.max_level_states, tb.max_level_arcs, tb.max_frame_uniq, grad != nullptr);
+    rc = launch_num_entropy_wide(p, route == 2, stream);
+  }
   if (rc != TC_OK) return rc;
   return supervision_mark_use(sup, device, stream);
 }

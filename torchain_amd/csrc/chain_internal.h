@@ -955,6 +955,31 @@ inline int64_t num_ent_regular_workspace_bytes(int64_t total_states, bool grad) 
   return grad ? ((int64_t)16 * total_states + 255) & ~(int64_t)255 : 0;
 }
 int launch_num_entropy_regular(const NumEntParams &p, hipStream_t stream);  // num_entropy_regular_kernels.hip
+// The same entry's wide-level kernel (num_entropy_wide_kernels.hip): handles of tc_supervision_allow_wide_levels beyond
+// num_ent_regular_fits, or "force_num_entropy_wide".  LDS form: one level's gather vector of pairs and the frame's y,
+// 16 * ceil2(L) + 4 * ceil4(U) + 2048 <= 163840; a level beyond that (or "force_num_entropy_wide_streamed") takes the slot
+// form, which has no dynamic LDS, so no level is refused on its width.  Workspace: with a gradient the history, 16 bytes a
+// state of the handle rounded up to 256; then per sequence num_ent_wide_seq_doubles doubles -- two level-sized rows of pairs
+// (log beta, Bbar; for the value alone log alpha, Abar), with a gradient one float per arc leaving the widest level, and the
+// slot form's y (always there: the switch may move between the query and the call).  The kernel finds the rows through
+// NumEntParams::n.wide_rows / wide_stride, which the entry points at the workspace -- never at the pool slot.
+inline size_t num_ent_wide_lds_bytes(int32_t level_states, int32_t frame_uniq) {
+  return (size_t)((level_states + 1) & ~1) * 16 + (size_t)((frame_uniq + 3) & ~3) * 4;
+}
+inline bool num_ent_wide_lds_fits(int32_t level_states, int32_t frame_uniq) {
+  return num_ent_wide_lds_bytes(level_states, frame_uniq) + kNumEntStaticLds <= (size_t)kLdsLimitBytes;
+}
+inline int64_t num_ent_wide_seq_doubles(int32_t level_states, int32_t level_arcs, int32_t frame_uniq, bool grad) {
+  const int64_t n = (int64_t)4 * ((level_states + 1) & ~1) +
+                    ((grad ? (int64_t)((level_arcs + 3) & ~3) : 0) + ((frame_uniq + 3) & ~3)) / 2;
+  return (n + 31) & ~(int64_t)31;
+}
+inline int64_t num_ent_wide_workspace_bytes(int64_t total_states, int32_t S, int32_t level_states, int32_t level_arcs,
+                                            int32_t frame_uniq, bool grad) {
+  return num_ent_regular_workspace_bytes(total_states, grad) +
+         (int64_t)S * num_ent_wide_seq_doubles(level_states, level_arcs, frame_uniq, grad) * 8;
+}
+int launch_num_entropy_wide(const NumEntParams &p, bool slot, hipStream_t stream);  // num_entropy_wide_kernels.hip
 // The arc occupations of an end-to-end supervision (tc_supervision_arc_posteriors, num_arc_post_kernels.hip).  `n` carries what
 // the numerator's launches carry; the pool slot's scratch is neither read nor written.  Workspace (num_arc_workspace_bytes): the
 // history log alpha_t, t = 0 .. T - 1, one double a (frame, state) at T * state_off[s] doubles; for the large form behind it
@@ -1187,7 +1212,7 @@ extern thread_local int g_last_hip_error;
 // replace what used to be environment variables of the shipping library.
 // bumped whenever a round changes a kernel the per-graph choice is timed on (tuning_cache.cpp: part of the cache key)
 constexpr int kKernelGeneration = 6;
-enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgForceNumArcPostRegularSpill, kDbgForceNumSampleStreamed, kDbgForceNumWide, kDbgForceNumWideStreamed, kDbgCount };
+enum DebugFlag { kDbgForceGeneral = 0, kDbgForceStreamed, kDbgNoSplit, kDbgNoPdfBanks, kDbgNoBankSearch, kDbgSchedTrace, kDbgNoPhaseSplit, kDbgNoNumOverlap, kDbgNoPair, kDbgForcePair, kDbgNoTune, kDbgNoMitm, kDbgForceMitm, kDbgSlabWide, kDbgSlabNarrow, kDbgExpPerFrame, kDbgOldArrange, kDbgNoPlanes, kDbgOldGeneral, kDbgPhantomPdf0, kDbgNoPdfSearch, kDbgNoSplitSrc, kDbgPlanesMeetAt, kDbgForceNumWindowed, kDbgForceDenBestStreamed, kDbgForceNumE2eLarge, kDbgNoFullLayout, kDbgForceDenAccStreamed, kDbgForceDenSampleStreamed, kDbgForceDenArcPostStreamed, kDbgForceDenEntropyStreamed, kDbgForceNumEntropyLarge, kDbgForceNumArcPostLarge, kDbgForceNumArcPostRegularSpill, kDbgForceNumSampleStreamed, kDbgForceNumWide, kDbgForceNumWideStreamed, kDbgForceNumEntropyWide, kDbgForceNumEntropyWideStreamed, kDbgCount };
 bool debug_flag(DebugFlag f);
 int debug_value(DebugFlag f);  // the switch's integer value (0: not set)
 
@@ -1196,7 +1221,7 @@ void pool_release(int device, PoolSlot *slot);
 int64_t pool_counter(int which);  // 0: device allocations made by the pool, 1: slots reused
 // launches enqueued so far, by kind (tc_debug_counter): the evaluation-step tests read them to see that a forward-only
 // call enqueued no backward recursion
-enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntNumArcPostRegular, kCntNumArcPostRegularSpill, kCntNumSample, kCntNumSampleStreamed, kCntNumWide, kCntCount };
+enum LaunchCounter { kCntDen = 0, kCntDenBackward, kCntNum, kCntNumBackward, kCntLayout, kCntDenAsumGlobal, kCntNumE2eStaged, kCntNumWindowed, kCntChannelLast, kCntRagged, kCntRaggedTwoCu, kCntBestPath, kCntDenBestPath, kCntDenBestPathStreamed, kCntXentLogSoftmax, kCntNumE2eLarge, kCntTiedFullLayout, kCntDenAccuracy, kCntDenAccuracyGrad, kCntDenAccuracyGradStreamed, kCntDenAccuracyDense, kCntDenAccuracyDenseGrad, kCntDenSample, kCntDenSampleStreamed, kCntPathEdit, kCntSampledRiskGrad, kCntBoost, kCntDenArcPost, kCntDenArcPostStreamed, kCntDenEntropy, kCntDenEntropyStreamed, kCntNumEntropy, kCntNumEntropyRegular, kCntNumEntropyLarge, kCntNumArcPost, kCntNumArcPostLarge, kCntNumArcPostRegular, kCntNumArcPostRegularSpill, kCntNumSample, kCntNumSampleStreamed, kCntNumWide, kCntNumEntropyWide, kCntCount };
 void count_launch(LaunchCounter c);
 int supervision_mark_use(tc_supervision *sup, int device, hipStream_t stream);
 int stage_e2e_locked(tc_supervision *sup, int device);  // supervision_e2e.cpp (caller holds sup->mu)

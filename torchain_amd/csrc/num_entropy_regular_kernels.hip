@@ -37,6 +37,7 @@
 #include "chain_internal.h"
 #include "half_io.h"
 #include "num_device.h"
+#include "num_entropy_device.h"
 
 namespace tc {
 
@@ -44,33 +45,6 @@ namespace {
 
 constexpr int kEntRegThreads = 256;
 constexpr int kEntRegYRegs = 2;  // unique entries of a frame a thread fetches a frame ahead; further ones load where staged
-
-template <typename El>
-__device__ __forceinline__ void entr_store(void *g, int64_t i, float v) {
-  if constexpr (std::is_same<El, float>::value)
-    reinterpret_cast<float *>(g)[i] = v;
-  else
-    reinterpret_cast<uint16_t *>(g)[i] = Elem<El>::round(v);
-}
-
-// The posterior mean of val(a) = mean(other state of a) + r_a over one state's arc list, `acc` being the list's log-sum
-// (num_state_log_sum over the same list): other(a) gives the other state's pair (log weight, mean).
-template <class ArcAt, class Score, class Other>
-__device__ __forceinline__ double entr_state_mean(int i0, int i1, double acc, ArcAt arc_at, Score score, Other other) {
-  if (!(acc > -INFINITY)) return 0.0;  // no path through the state: its mean is never weighted
-  double num = 0.0, den = 0.0;
-  for (int i = i0; i < i1; ++i) {
-    const int a = arc_at(i);
-    const double r = (double)score(a);
-    const double2 o = other(a);
-    const float sh = __expf((float)(r + o.x - acc));
-    if (sh > 0.f) {  // (a share of 0 may stand before an infinite cost or a state without a path)
-      num += (double)sh * (o.y + r);
-      den += (double)sh;
-    }
-  }
-  return num / den;
-}
 
 }  // namespace
 
@@ -176,19 +150,8 @@ __global__ __launch_bounds__(kEntRegThreads) void num_entropy_regular_kernel(con
   if (tid == 0) {
     const double2 *last = pp + (T & 1) * W;
     const double tot = num_total(f0, f1, final_logw, [&](int st) __attribute__((always_inline)) { return last[st - f0].x; });
-    double num = 0.0, den = 0.0;
-    if (tot > -INFINITY)
-      for (int st = f0; st < f1; ++st) {
-        const double fl = (double)final_logw[st];
-        if (fl == -INFINITY) continue;
-        const float sh = __expf((float)(last[st - f0].x + fl - tot));
-        if (sh > 0.f) {
-          num += (double)sh * (last[st - f0].y + fl);
-          den += (double)sh;
-        }
-      }
     tot_sh[0] = tot;
-    tot_sh[1] = num / den;
+    tot_sh[1] = entr_final_mean(f0, f1, final_logw, tot, [&](int st) __attribute__((always_inline)) { return last[st - f0]; });
   }
   const bool some_bad = __syncthreads_or(bad ? 1 : 0) != 0;
   const double logz = tot_sh[0], elw = tot_sh[1];

@@ -1141,7 +1141,10 @@ class Supervision:
         ``tc_supervision_path_entropy_regular``, which walks level by level and visits every state once per direction.
         An end-to-end handle with a sequence of more than about 5000 states takes the entry's large kernel, which keeps the
         per-state means in a workspace (``path_entropy_kernel()``); every handle ``from_e2e_fsts`` builds is served.
-        ``TorchainHipError`` (unsupported): a regular handle whose widest level breaks ``48 * max_level_states + 4 * max_frame_uniq + 4 * max_level_arcs + 2048 <= 163840`` (``stats()``).
+        ``TorchainHipError`` (unsupported): a regular handle built without ``any_width=True`` whose widest level breaks ``48 * max_level_states + 4 * max_frame_uniq + 4 * max_level_arcs + 2048 <= 163840`` (``stats()``).
+        A handle built with ``any_width=True`` takes the entry's wide-level kernel there instead (``path_entropy_regular_kernel()``):
+        levels of any width, one level's pairs in LDS and the rest in a workspace, which the value needs too and which is
+        allocated here.
 
         The paths of sequence ``b`` are the arc sequences of exactly ``T_b`` arcs from its FST's start state to a final state,
         ``log W = sum_t (y_t(pdf_t) - cost_t) - final cost``, ``logprob[b] = log Z_b = log sum W`` (the numerator's, without the
@@ -1162,12 +1165,23 @@ class Supervision:
         check(min(kernel, 0), "tc_supervision_path_entropy_kernel")
         return kernel
 
+    def path_entropy_regular_kernel(self):
+        """Which kernel ``path_entropy`` / ``functions.num_path_entropy`` run on this regular handle
+        (``tc_supervision_path_entropy_regular_kernel``, host arithmetic only): 0 the level-windowed one; 1 the wide-level one
+        with a level's pairs in LDS, 2 the same with them in the workspace (a level of more than about 10000 states) -- both
+        only for a handle built with ``any_width=True`` whose widest level is beyond the level-windowed kernel.
+        ``TorchainHipError`` for a handle the entry refuses and for an end-to-end handle."""
+        kernel = int(lib.tc_supervision_path_entropy_regular_kernel(self.ptr))
+        check(min(kernel, 0), "tc_supervision_path_entropy_regular_kernel")
+        return kernel
+
     def _path_entropy(self, who, nnet_output, grad_output=None, workspace=None):
         """The checks and one launch of the handle's kind's entry (``tc_supervision_path_entropy`` for an end-to-end handle,
         ``tc_supervision_path_entropy_regular`` for a regular one): ``(entropy, logprob, grad)``.  With ``grad_output``
         (float64 ``(B,)``) the launch also writes ``grad_output[b] * d entropy[b] / d y`` in the prepared input's layout and
         dtype, its history in ``workspace(device, stream, nbytes)``; without it ``grad`` is ``None``, and what the value
-        alone needs (the large end-to-end kernel's mean rows; 0 bytes otherwise) is allocated here."""
+        alone needs (the large end-to-end kernel's mean rows, the wide-level regular kernel's level rows; 0 bytes otherwise) is
+        allocated here."""
         x = nnet_output.detach() if isinstance(nnet_output, torch.Tensor) else nnet_output
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise ValueError("%s: nnet_output must be a CUDA tensor (only the HIP implementation is available)" % who)
